@@ -1,8 +1,12 @@
 #!/usr/bin/env python
 """bench.py — distill-step images/sec of the MI355X build on BASELINE.json's headline workload.
 
-  python bench.py --gpus N --steps K --warmup W          (N=1)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]          (N=1)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W   (N>1)
+
+A plain run sets up, warms up, times K steps, writes the last timed step's outputs if `--dump-outputs DIR` is given (dump_outputs)
+and prints one JSON line whose `value` / `ms_per_step` are those K steps.  Everything else this script measures -- the sustained
+rate, the kernel roofline and student-forward passes, the secondary configurations and the CPU baseline -- runs only with `--full`.
 
 Workload (BASELINE configs[1]): pix2pix InceptionDistiller.optimize_parameters at 256x256, per-GPU batch
 16 -- frozen teacher ngf 64 (BatchNorm, running stats), student pruned by shrink_model to 4.6e9 MACs and re-initialised,
@@ -10,7 +14,7 @@ PatchGAN 6ch ndf 128, hinge GAN + L1*100 + KA*1.3, two Adam steps.  Synthetic N(
 weights of the named architecture, fp32 everywhere.  Data parallel = one process per GPU, batch sharded (weak scaling:
 per-GPU batch fixed), RCCL all-reduce of the gradient buckets.
 
-The JSON line carries `roofline` for the dominant kernel family (the fp32-MFMA implicit-GEMM convolutions; achieved =
+With `--full` the JSON line carries `roofline` for the dominant kernel family (the fp32-MFMA implicit-GEMM convolutions; achieved =
 algorithmic FLOPs / HIP-event time of those launches, measured in a short SERIAL pass after the timed region -- stream-level
 concurrency off -- so the events neither perturb `value` nor see co-running kernels) and `cpu_baseline` (the CPU oracle timed on a bounded sample of the same workload on rank 0)."""
 import argparse
@@ -25,6 +29,8 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 MFMA_F32_PEAK_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32, 256 CUs @ 2.4 GHz
+DUMP_MAX_ELEMS = 1 << 21       # --dump-outputs: a larger array is written as a fixed, seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files together
 
 
 C2 = dict(norm='batch', track=True, ndf=128, dataset_mode='aligned', gan_mode='hinge', lambda_recon=100.0, lambda_distill=1.3)
@@ -191,12 +197,49 @@ def cpu_baseline(opt, model, args):
                       + REFERENCE_VS_PORT}
 
 
+def dump_outputs(model, out_dir):
+    """--dump-outputs: what the last timed step computed, as a caller of optimize_parameters receives it -- the loss values
+    (get_current_losses, float64 scalars: loss_<name>.npy), the generated images (get_current_visuals minus the inputs: <name>.npy) and
+    every parameter optimizer_G and optimizer_D updated, flattened in param_groups order (params_G.npy, params_D.npy), float32.  An
+    array of more than DUMP_MAX_ELEMS elements is written as its elements at a fixed, seeded sample of flat indices (sorted, the same in
+    every run), so that two builds given the same arguments can be compared output for output."""
+    import numpy as np
+    model.finish_pending()
+    arrays = {}
+    for key, v in model.get_current_losses().items():
+        arrays['loss_' + key.split('/')[-1]] = np.float64(v)
+    for key, v in model.get_current_visuals().items():
+        if 'fake' in key:
+            arrays[key] = v
+    for name in ('G', 'D'):
+        o = getattr(model, 'optimizer_' + name)
+        arrays['params_' + name] = torch.cat([p.detach().reshape(-1) for g in o.param_groups for p in g['params']])
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, v in arrays.items():
+        if torch.is_tensor(v):
+            v = v.detach().float()
+            if v.numel() > DUMP_MAX_ELEMS:
+                idx = np.sort(np.random.default_rng(0).choice(v.numel(), DUMP_MAX_ELEMS, replace=False))
+                v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+            v = v.cpu().numpy()
+        total += v.nbytes
+        assert total <= DUMP_MAX_BYTES, f'--dump-outputs: more than {DUMP_MAX_BYTES} bytes'
+        np.save(os.path.join(out_dir, name + '.npy'), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--sustained-steps', type=int, default=100, help='extra steps after the timed region (N=1): the clock-settled rate')
+    ap.add_argument('--full', action='store_true',
+                    help='also take the measurements beyond the headline figure: sustained rate, kernel roofline and student-forward passes, '
+                         'secondary configurations (default 1-GPU headline run) and CPU baseline; the --no-* / --sustained-steps options '
+                         'below select among them')
+    ap.add_argument('--dump-outputs', default=None, dest='dump_outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (dump_outputs)')
+    ap.add_argument('--sustained-steps', type=int, default=100, help='--full: extra steps after the timed region (N=1): the clock-settled rate')
     ap.add_argument('--workload', default='c2', choices=['c2', 'c3', 'spade'],
                     help='c2 = pix2pix InceptionDistiller (BASELINE configs[1], the headline metric); c3 = CycleGAN-style InceptionDistiller '
                          '(configs[2] per GPU: InstanceNorm, lsgan, unaligned, ndf 64, batch 8); spade = GauGAN SPADEDistiller '
@@ -223,7 +266,7 @@ def main():
                     help='bf16x3: the opt-in split-bf16 backward tiles of the wide PatchGAN layers (csrc/conv_split.hip; DESIGN section 6). Reported with its '
                          'own dtype; the f32 line is the graded one')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='skip the short GauGAN (configs[3], batch 4) and CycleGAN-style (configs[2], batch 8) measurements that the default '
+                    help='skip the short GauGAN (configs[3], batch 4) and CycleGAN-style (configs[2], batch 8) measurements that the --full '
                          '1-GPU headline run attaches as `secondary`')
     args = ap.parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -332,11 +375,13 @@ def main():
     losses = model.get_current_losses()
     assert all(v == v for v in losses.values()), 'NaN loss'
     assert ops.STATS['conform_copies'] == 0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
     # sustained rate: `value` above is the contract's K steps (the driver asks for 20: ~1 s of GPU work, inside the boost window and below an
     # external utilisation sampler's cadence).  A second, longer run of the SAME step shows the clock-settled rate and keeps the GPU busy
     # for several seconds; reported beside `value`, never instead of it.
     sustained = None
-    if world == 1 and args.sustained_steps > 0:
+    if args.full and world == 1 and args.sustained_steps > 0:
         barrier()
         t1 = time.perf_counter()
         for i in range(args.sustained_steps):
@@ -349,7 +394,7 @@ def main():
     # the measurement passes run the step / the student forward again: with N > 1 ranks those contain collectives (gradient buckets,
     # SynchronizedBatchNorm statistics), so EVERY rank executes them; rank 0 reports
     roofline = student_fwd = None
-    if not args.no_kernel_profile and (rank == 0 or world > 1):
+    if args.full and not args.no_kernel_profile and (rank == 0 or world > 1):
         roofline = kernel_roofline(model, eager_step, args)
         if dp and hasattr(model, 'finish_pending'):
             model.finish_pending()
@@ -388,16 +433,16 @@ def main():
         out['sustained'] = sustained
     if rank == 0:
         headline = world == 1 and args.workload == 'c2' and args.size == 256 and args.batch == 16 and not args.dp_schedule and args.mfma == 'f32'
-        if headline and not args.no_secondary:
+        if args.full and headline and not args.no_secondary:
             out['secondary'] = secondary_measurements()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = (cpu_baseline_spade if spade else cpu_baseline)(opt, model, args)
         print(json.dumps(out), file=json_out, flush=True)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
 
 
-# child runs of the default 1-GPU headline invocation: (key, extra argv, what it is)
+# child runs of the --full 1-GPU headline invocation: (key, extra argv, what it is)
 SECONDARY = (
     ('spade', ['--workload', 'spade'], 'GauGAN SPADEDistiller, BASELINE configs[3] per GPU: 512x256, batch 4'),
     ('c3', ['--workload', 'c3'], 'CycleGAN-style InceptionDistiller, BASELINE configs[2] per GPU: batch 8'),
@@ -415,12 +460,12 @@ SECONDARY = (
 def secondary_measurements():
     """The other single-GPU measurements BASELINE.json / north_star name, taken by the SAME invocation after the headline's timed region so
     that they appear in the driver-timed record (SECONDARY above).  Each is a short child run of this script (own process: own
-    caching-allocator pools and hipGraph; 8 timed steps after 3 warm-up steps, the same barrier / synchronize bracket, no CPU baseline)
-    whose JSON line is condensed here.  The headline fields of the parent line are untouched."""
+    caching-allocator pools and hipGraph; 8 timed steps after 3 warm-up steps, the same barrier / synchronize bracket, its kernel roofline and
+    student-forward passes, no CPU baseline) whose JSON line is condensed here.  The headline fields of the parent line are untouched."""
     import subprocess
     out = {}
     for key, extra, what in SECONDARY:
-        cmd = [sys.executable, os.path.abspath(__file__)] + extra + ['--steps', '8', '--warmup', '3', '--sustained-steps', '0',
+        cmd = [sys.executable, os.path.abspath(__file__)] + extra + ['--steps', '8', '--warmup', '3', '--full', '--sustained-steps', '0',
                                                                      '--no-cpu-baseline', '--no-secondary']
         t0 = time.perf_counter()
         try:

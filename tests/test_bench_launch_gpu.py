@@ -47,7 +47,7 @@ def _check_line(j, batch, steps, warmup):
 
 @pytest.mark.timeout(1800)
 def test_bench_gpus2_c2_through_its_own_launcher():
-    j, err = _bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--batch', '4'], TWO_RANKS_ONE_GPU)
+    j, err = _bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--batch', '4'], TWO_RANKS_ONE_GPU)
     _check_line(j, 4, 2, 1)
     assert 'hipGraph segments around the collectives' in j['config']['launch'], j['config']['launch']      # not the eager fallback
     assert 'capture failed' not in err
@@ -74,7 +74,26 @@ def test_bench_gpus2_spade_through_its_own_launcher():
 @pytest.mark.timeout(900)
 def test_bench_dp_schedule_on_one_gpu_over_rccl():
     """The N = 1 point of the scaling curve in the data-parallel launch mode: a world_size-1 RCCL group (library load, device_id= init,
-    all-reduce of the real buckets), hipGraph segments, deferred Adam G.  This is the `secondary.dp1` leg of the default headline run."""
+    all-reduce of the real buckets), hipGraph segments, deferred Adam G.  This is the `secondary.dp1` leg of the --full headline run."""
     j, err = _bench(['--dp-schedule', '1', '--steps', '3', '--warmup', '2', '--no-cpu-baseline', '--no-kernel-profile', '--no-secondary'])
     assert j['n_gpus'] == 1 and j['config']['schedule'] == 'data-parallel' and j['config']['collectives'].startswith('rccl')
     assert 'hipGraph segments around the collectives' in j['config']['launch'], (j['config']['launch'], err[-1500:])
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_run_times_only_the_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) carries the headline fields only; --dump-outputs writes what the last timed step computed: the losses
+    (float64 scalars), the generated images and the updated parameters (float32; large arrays as a seeded sample), 64 MB at most."""
+    import numpy as np
+    j, _ = _bench(['--steps', '3', '--warmup', '1', '--batch', '4', '--dump-outputs', str(tmp_path)])
+    assert j['n_gpus'] == 1 and j['steps'] == 3 and j['warmup'] == 1 and j['dtype'] == 'f32' and j['unit'] == 'images/sec'
+    assert j['higher_is_better'] is True and abs(j['value'] - 4 * 1e3 / j['ms_per_step']) <= 2e-3 * j['value']
+    assert j['roofline'] is None and j['student_forward'] is None
+    assert not {'sustained', 'secondary', 'cpu_baseline'} & set(j), sorted(j)
+    files = {p.name: np.load(p) for p in tmp_path.glob('*.npy')}
+    losses = {k: v for k, v in files.items() if k.startswith('loss_')}
+    assert {'Sfake_B.npy', 'Tfake_B.npy', 'params_G.npy', 'params_D.npy'} <= set(files) and len(losses) >= 5, sorted(files)
+    assert all(v.dtype == np.float64 and v.shape == () and np.isfinite(v) for v in losses.values())
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for k, v in files.items() if k not in losses)
+    assert files['Sfake_B.npy'].shape == (4, 3, 256, 256)
+    assert sum(p.stat().st_size for p in tmp_path.glob('*.npy')) <= 64 << 20

@@ -174,6 +174,47 @@ def test_bench_measured_path_does_not_touch_the_oracle():
                 assert 'oracle' not in imports(ast.parse(open(os.path.join(dirpath, f)).read())), f
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample():
+    """bench.py --dump-outputs (dump_outputs, host side): losses as float64 scalars, generated images (not the inputs) and the optimizers'
+    parameters as float32, an array above DUMP_MAX_ELEMS as the same seeded sample in every run, 64 MB at most."""
+    import tempfile
+    import numpy as np
+    import bench
+
+    class Stub:
+        def __init__(self):
+            torch.manual_seed(3)
+            self.netG, self.netD = torch.nn.Linear(10, 10), torch.nn.Linear(1100, bench.DUMP_MAX_ELEMS // 1000)
+            self.optimizer_G, self.optimizer_D = torch.optim.Adam(self.netG.parameters()), torch.optim.Adam(self.netD.parameters())
+            self.optimizers = [self.optimizer_G, self.optimizer_D]
+
+        def finish_pending(self):
+            pass
+
+        def get_current_losses(self):
+            return {'G_loss/G_gan': 1.5, 'D_loss/D_real': 0.25, 'Specific_loss/G_distill0': 2.0}
+
+        def get_current_visuals(self):
+            return {'real_A': torch.ones(2, 3, 8, 8), 'Sfake_B': torch.full((2, 3, 8, 8), 0.5, dtype=torch.float64)}
+
+    got = []
+    for _ in range(2):
+        with tempfile.TemporaryDirectory() as d:
+            bench.dump_outputs(Stub(), d)
+            got.append({f: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+            assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= bench.DUMP_MAX_BYTES
+    a, b = got
+    assert sorted(a) == ['Sfake_B.npy', 'loss_D_real.npy', 'loss_G_distill0.npy', 'loss_G_gan.npy', 'params_D.npy', 'params_G.npy']
+    assert a['loss_G_gan.npy'].dtype == np.float64 and float(a['loss_G_gan.npy']) == 1.5
+    assert a['Sfake_B.npy'].dtype == np.float32 and a['Sfake_B.npy'].shape == (2, 3, 8, 8)
+    net = Stub().netD
+    full = torch.cat([net.weight.detach().reshape(-1), net.bias.detach()]).numpy()
+    assert full.size > bench.DUMP_MAX_ELEMS and a['params_D.npy'].shape == (bench.DUMP_MAX_ELEMS,)
+    assert np.isin(a['params_D.npy'], full).all()
+    assert a['params_G.npy'].shape == (110,)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def test_no_undefined_names_in_gpu_only_code():
     """Most of cat_amd/ only executes on an MI355X; a scope-aware undefined-name pass over the sources (tools/lint_names.py) keeps
     typos in those branches from surfacing first on the GPU box."""

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-5 fallback of tools/profile_round.sh (whose PMC passes no longer fit the round's GPU budget): the default bench line, the rocprofv3
+# Round-5 fallback of tools/profile_round.sh (whose PMC passes no longer fit the round's GPU budget): the --full bench line, the rocprofv3
 # --kernel-trace --stats summary of the same (serial) C2 command and of the student forward.  Every step carries its own time limit; raw traces
 # are summarised on the box and deleted (gpurun returns <= 64 MiB).   COMMIT=<head> bash tools/profile_quick.sh
 export TMPDIR=/tmp
@@ -13,8 +13,8 @@ print(json.dumps({'commit': '${COMMIT:-unknown}', 'csrc_sha': m.csrc_fingerprint
                   'command': 'COMMIT=<head> bash tools/profile_quick.sh (one MI355X, through gpurun)'}, indent=1))
 PYEOF
 S=$(date +%s)
-timeout 330 python bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err
-echo "default bench.py: rc $? in $(( $(date +%s) - S )) s" > $OUT/timing.txt
+timeout 330 python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+echo "bench.py --full: rc $? in $(( $(date +%s) - S )) s" > $OUT/timing.txt
 export CAT_BRANCH_STREAMS=0
 B="python $PWD/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-kernel-profile --no-secondary --graph 0 --sustained-steps 0"
 (cd /tmp && timeout 160 rocprofv3 --kernel-trace --stats -d $OUT/prof_c2 -o bench -- $B > $OUT/prof_c2.log 2>&1)

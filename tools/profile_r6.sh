@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-6 evidence pass, run ON THE GPU BOX through gpurun from the repo root; every step carries its own time limit and only summaries
 # travel back (gpurun returns <= 64 MiB).            COMMIT=<head> [PMC=0] [SPADE=1] bash tools/profile_r6.sh
-#   bench_c2.json              the default `python bench.py` line (roofline, cpu_baseline, secondary)
+#   bench_c2.json              the `python bench.py --full` line (roofline, cpu_baseline, secondary)
 #   kernel_stats_c2.txt        rocprofv3 --kernel-trace --stats of the serial C2 command, LIBRARY kernels only (model construction's
 #                              ATen fills / copies are filtered out of the table), per step
 #   kernel_stats_student_fwd.txt   the same for replays of the captured student forward
@@ -22,7 +22,7 @@ S=$(date +%s)
 T() { echo "$1: $(( $(date +%s) - S )) s" >> $OUT/timing.txt; }
 : > $OUT/timing.txt
 if [ -z "$SKIP_BENCH" ]; then
-timeout 400 python bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err; T "default bench.py rc $?"
+timeout 400 python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err; T "bench.py --full rc $?"
 fi
 export CAT_BRANCH_STREAMS=0
 B="python $PWD/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-kernel-profile --no-secondary --graph 0 --sustained-steps 0"

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run ON THE GPU BOX (through gpurun) from the repo root: the round's measured artefacts -> gpurun_out/round/
-#   bench lines (c2 default incl. roofline + cpu_baseline, spade), rocprofv3 kernel-trace stats of the same commands,
+#   bench lines (c2 --full incl. roofline + cpu_baseline, spade), rocprofv3 kernel-trace stats of the same commands,
 #   PMC passes (FETCH_SIZE / WRITE_SIZE separately, kernel-trace only -- never combined with sys/hip traces).
 # ROUND 5 NOTE: the whole-step PMC passes (FETCH_SIZE, WRITE_SIZE, SQ_*) take ~10 minutes EACH on this pool; the full script ran into a
 # 50-minute limit with nothing copied back.  They are therefore opt-in (WITH_PMC=1, give gpurun --timeout 4500); without it this script takes
@@ -21,9 +21,9 @@ print(json.dumps({'commit': '${COMMIT:-unknown}', 'csrc_sha': m.csrc_fingerprint
                   'command': 'COMMIT=<head> bash tools/profile_round.sh (one MI355X, through gpurun)'}, indent=1))
 PYEOF
 if [ -z "$SKIP_BENCH" ]; then
-python bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err
-python bench.py --workload spade > $OUT/bench_spade.json 2> $OUT/bench_spade.err
-python bench.py --size 512 --batch 16 --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench_c2_512.json 2> $OUT/bench_c2_512.err
+python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+python bench.py --full --workload spade > $OUT/bench_spade.json 2> $OUT/bench_spade.err
+python bench.py --full --size 512 --batch 16 --steps 6 --warmup 2 --no-cpu-baseline > $OUT/bench_c2_512.json 2> $OUT/bench_c2_512.err
 python -c 'import __graft_entry__ as g; g.smoke()' > $OUT/smoke.log 2>&1
 python tools/qconv_bench.py > $OUT/qconv_layers.txt 2>&1
 fi
