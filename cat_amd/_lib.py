@@ -104,6 +104,19 @@ class PrepJob(C.Structure):
                                                                                 'nt_total', 'col0', 'cs', 'block0', 'nblocks')]
 
 
+DROP_MAXSEG = 8
+DROP_PLAIN, DROP_NORM = 0, 1
+
+
+class DropSeg(C.Structure):
+    _fields_ = [(n, c_i) for n in ('c0', 'c', 'j')]
+
+
+class DropGeom(C.Structure):
+    _fields_ = [(n, c_i) for n in ('npix', 'hw', 'width', 'xcs', 'ycs', 'mode', 'rest', 'sstride', 'act')] + \
+               [('slope', c_f), ('thresh', C.c_uint), ('s', c_f), ('drop_all', c_i), ('nseg', c_i), ('seg', DropSeg * DROP_MAXSEG)]
+
+
 PAD_ZERO, PAD_REFLECT = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_RELU6 = 0, 1, 2, 3, 4
 NORM_INSTANCE, NORM_BATCH = 0, 1
@@ -216,6 +229,8 @@ SIGNATURES = {
     'cat_spectral_norm_ws_bytes': (C.c_size_t, [c_i, c_i, c_i, c_i]),
     'cat_spectral_norm_fwd': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, c_p]),
     'cat_spectral_norm_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p]),
+    'cat_rng_draw': (c_i, [c_p, c_p, c_p]),
+    'cat_dropout_apply': (c_i, [C.POINTER(DropGeom), c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

@@ -56,7 +56,9 @@ def applicable(block, x):
         return False
     if block.padding_type not in ('reflect', 'zero'):      # 'replicate' is a materialised pad: general path
         return False
-    return block.dropout_rate == 0 and len(block.dw_ops) + sum(1 for op in block.res_ops if op[1][0].kernel_size[0] == 1) >= 2
+    if any(isinstance(m, cnn.Dropout) and m.training and m.p != 0 for m in block.modules()):
+        return False        # (a Dropout in eval mode is the identity, whatever the block's dropout_rate)
+    return len(block.dw_ops) + sum(1 for op in block.res_ops if op[1][0].kernel_size[0] == 1) >= 2
 
 
 def _tensors(block):

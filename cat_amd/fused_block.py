@@ -28,6 +28,7 @@ from . import _lib as L
 from . import nn as cnn
 from . import ops
 from . import optim
+from . import rng
 from . import tconv
 
 _ENABLED = os.environ.get('CAT_FUSED_BLOCK', '1') != '0'
@@ -53,8 +54,20 @@ def _has_hooks(mod):
     return False
 
 
+def _dropout(block):
+    """-> (p, {j of the branches whose Dropout is active}) -- Dropout j = res branches first, then dw branches -- or None when the active
+    Dropouts of the block disagree on p (general path).  p == 0: no Dropout is active (eval mode or rate 0) and nothing is launched."""
+    mods = [op[2] for op in block.res_ops] + [op[3] for op in block.dw_ops]
+    act = {j: float(m.p) for j, m in enumerate(mods) if isinstance(m, cnn.Dropout) and m.training and m.p != 0}
+    if len(set(act.values())) > 1:
+        return None
+    return (next(iter(act.values())) if act else 0.0), frozenset(act)
+
+
 def applicable(block, x):
-    if not _ENABLED or not block.training or not x.is_cuda or block.dropout_rate != 0 or block.padding_type not in ('reflect', 'zero'):
+    if not _ENABLED or not block.training or not x.is_cuda or block.padding_type not in ('reflect', 'zero'):
+        return False
+    if _dropout(block) is None:
         return False
     if torch.is_grad_enabled() and not _BACKWARD_READY:
         return False
@@ -101,9 +114,11 @@ class _Plan:
         self.eps, self.momentum = float(pw.eps), float(pw.momentum if pw.momentum is not None else 0.0)
         # branches; stage-1 channel order: [res k=1 | dw ... | res k=3 | res k=5] so that same-kernel first convs are adjacent (N concat)
         # and the depthwise inputs are one contiguous slice range
-        res = [dict(kind='res', k=op[1][0].kernel_size[0], m=op[1][0].out_channels, conv1=op[1][0], bn1=op[1][1], conv2=op[4]) for op in block.res_ops]
-        dws = [dict(kind='dw', k=1, kd=op[2][0].kernel_size[0], m=op[0][0].out_channels, conv1=op[0][0], bn1=op[0][1], dconv=op[2][0], bn2=op[2][1],
-                    conv2=op[4]) for op in block.dw_ops]
+        # j: the branch's Dropout index inside the block (res branches first, then dw branches; the general path's order)
+        res = [dict(kind='res', j=i, k=op[1][0].kernel_size[0], m=op[1][0].out_channels, conv1=op[1][0], bn1=op[1][1], conv2=op[4])
+               for i, op in enumerate(block.res_ops)]
+        dws = [dict(kind='dw', j=len(res) + i, k=1, kd=op[2][0].kernel_size[0], m=op[0][0].out_channels, conv1=op[0][0], bn1=op[0][1],
+                    dconv=op[2][0], bn2=op[2][1], conv2=op[4]) for i, op in enumerate(block.dw_ops)]
         order = [b for b in res if b['k'] == 1] + dws + [b for b in res if b['k'] == 3] + [b for b in res if b['k'] == 5]
         off = 0
         for b in order:
@@ -397,6 +412,8 @@ def forward(block, x, save=None):
     dev = x.device
     tiles = n * ((h + 7) // 8) * ((w + 15) // 16)
     sstride_of = lambda scs: scs if p.instance else 0
+    pdrop, djs = _dropout(block)
+    ticket = rng.draw(dev) if pdrop else None       # one draw per block forward, as on the general path
     # ---- stage 1: first convs -> Z1 (pre-norm, concatenated) + tile statistics
     z1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
     part1 = torch.empty((tiles, 2, p.hc1), device=dev, dtype=torch.float32)
@@ -434,10 +451,21 @@ def forward(block, x, save=None):
         L.call('cat_dwm_fwd', C.byref(gd), C.c_void_p(z1.data_ptr() + 4 * o), C.c_void_p(st1[0][0].data_ptr() + 4 * o),
                C.c_void_p(st1[0][1].data_ptr() + 4 * o), ops._p(p.w25), ops._p(p.biasd) if p.has_biasd else None, ops._p(zd), ops._p(partd), ops._stream())
         std = _finalize(p, partd, p.hcd, n, h, w, p.gammad, p.betad, [(b['od'], b['m'], b['bn2']) for b in p.dws])
+    # ---- dropout: the stage-2 operands are materialised (normalise + activation + mask) -- res slices of act(norm(Z1)) into A1, all of
+    # act(norm(Zd)) into Ad -- and stage 2 stages them as they are
+    a1 = ad = None
+    if ticket is not None:
+        a1, ad = _materialise(p, n, h, w, z1, st1, zd, std, pdrop, djs, ticket, dw_slices=False)
     # ---- stage 2: the branch sum, K-concatenated, normalise + activation applied while staging
     segs = []
     for b in p.branches:
-        if b['kind'] == 'res':
+        if a1 is not None:
+            res = b['kind'] == 'res'
+            src, scs_, o = (a1, p.hc1, b['o1']) if res else (ad, p.hcd, b['od'])
+            k = b['k2']
+            segs.append(tconv.Segment(None, k, (k - 1) // 2, p.reflect and k > 1, b['p2off'], c4=b['w1'], cin=b['m'], xcs=scs_,
+                                      ptr=src.data_ptr() + 4 * o))
+        elif b['kind'] == 'res':
             k = b['k']
             segs.append(tconv.Segment(None, k, (k - 1) // 2, p.reflect and k > 1, b['p2off'], c4=b['w1'], cin=b['m'], xcs=p.hc1,
                                       ptr=z1.data_ptr() + 4 * b['o1'], scale=st1[0][0].data_ptr() + 4 * b['o1'], shift=st1[0][1].data_ptr() + 4 * b['o1'],
@@ -457,8 +485,33 @@ def forward(block, x, save=None):
     L.call('cat_affine_res_fwd', ops._p(t), p.cs, ops._p(stp[0][0]), ops._p(stp[0][1]), sstride_of(p.cs), ops._p(x), ops.act_cs(x), ops._p(y), p.cs, G,
            (n // G) * h * w, p.cs, L.ACT_NONE, 0.0, ops._stream())
     if save is not None:
-        save.update(plan=p, z1=z1, zd=zd, t=t, st1=st1, std=std, stp=stp)
+        save.update(plan=p, z1=z1, zd=zd, t=t, st1=st1, std=std, stp=stp, drop=(pdrop, djs, ticket))
     return y
+
+
+def _drop_segs(p, djs, kind):
+    key = ('o1', 'res') if kind == 'res' else ('od', 'dw')
+    return [(b[key[0]], b['m'], b['j']) for b in p.branches if b['kind'] == key[1] and b['j'] in djs]
+
+
+def _materialise(p, n, h, w, z1, st1, zd, std, pdrop, djs, ticket, dw_slices):
+    """A1 = act(norm(Z1)) with the res slices dropped (dw slices: written undropped iff dw_slices -- the backward pass's depthwise input
+    gradient needs them, stage 2 does not) and Ad = act(norm(Zd)) dropped; one cat_dropout_apply launch each."""
+    dev, npix = z1.device, n * h * w
+    sstride_of = lambda scs: scs if p.instance else 0
+    a1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
+    rest = dw_slices or any(b['j'] not in djs for b in p.res)      # (res slices whose Dropout is off are written too)
+    g = ops.dropout_geom(npix, p.hc1, p.hc1, p.hc1, pdrop, _drop_segs(p, djs, 'res'), mode=L.DROP_NORM, rest=int(rest), hw=h * w,
+                         sstride=sstride_of(p.hc1), act=p.act, slope=p.slope)
+    if p.res or dw_slices:
+        ops.dropout_apply(g, z1, a1, ticket, st1[0][0], st1[0][1])
+    ad = None
+    if p.dws:
+        ad = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
+        g = ops.dropout_geom(npix, p.hcd, p.hcd, p.hcd, pdrop, _drop_segs(p, djs, 'dw'), mode=L.DROP_NORM, rest=1, hw=h * w, sstride=sstride_of(p.hcd),
+                             act=p.act, slope=p.slope)
+        ops.dropout_apply(g, zd, ad, ticket, std[0][0], std[0][1])
+    return a1, ad
 
 
 
@@ -486,9 +539,12 @@ class _BlockFn(torch.autograd.Function):
         y = forward(block, x, save)
         ctx.block, ctx.plan = block, save['plan']
         ctx.has_dw = save['zd'] is not None
+        ctx.pdrop, ctx.djs, ticket = save['drop']
         tensors = [x, save['z1'], save['t'], save['st1'][0], save['st1'][1], save['stp'][0], save['stp'][1]]
         if ctx.has_dw:
             tensors += [save['zd'], save['std'][0], save['std'][1]]
+        if ticket is not None:
+            tensors.append(ticket)
         ctx.save_for_backward(*tensors)
         return y
 
@@ -497,7 +553,8 @@ class _BlockFn(torch.autograd.Function):
         p, block = ctx.plan, ctx.block
         saved = ctx.saved_tensors
         x, z1, t, ss1, mr1, ssp, mrp = saved[:7]
-        zd, ssd, mrd = saved[7:] if ctx.has_dw else (None, None, None)
+        zd, ssd, mrd = saved[7:10] if ctx.has_dw else (None, None, None)
+        ticket = saved[-1] if ctx.pdrop else None
         dy = ops.conform(dy)
         p.prepare(backward=True)
         n, c, h, w = x.shape
@@ -557,17 +614,24 @@ class _BlockFn(torch.autograd.Function):
                 grads[id(pw.weight)], grads[id(pw.bias)] = dgp, dbp
         else:
             dt = _norm_bwd(p, n, hw, c, p.cs, t, dy, None, None, mrp, L.ACT_NONE, 0.0, None, None)
-        # ---- 2. re-materialise the hidden activations (inputs of the second convs / of the depthwise convs)
-        a1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
-        L.call('cat_affine_res_fwd', ops._p(z1), p.hc1, ops._p(ss1[0]), ops._p(ss1[1]), sstr(p.hc1), None, 0, ops._p(a1), p.hc1, G, (n // G) * hw, p.hc1,
-               p.act, p.slope, st)
+        # ---- 2. re-materialise the hidden activations (inputs of the second convs / of the depthwise convs); with dropout the forward's
+        # masks are re-derived from its ticket: res slices of A1 and all of Ad dropped, the dw slices of A1 (depthwise inputs) not
+        if ticket is not None:
+            a1, ad = _materialise(p, n, h, w, z1, (ss1, None), zd, (ssd, None), ctx.pdrop, ctx.djs, ticket, dw_slices=True)
+        else:
+            a1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
+            L.call('cat_affine_res_fwd', ops._p(z1), p.hc1, ops._p(ss1[0]), ops._p(ss1[1]), sstr(p.hc1), None, 0, ops._p(a1), p.hc1, G, (n // G) * hw,
+                   p.hc1, p.act, p.slope, st)
         da1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
-        ad = dad = None
+        dad = None
         if ctx.has_dw:
-            ad = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
-            L.call('cat_affine_res_fwd', ops._p(zd), p.hcd, ops._p(ssd[0]), ops._p(ssd[1]), sstr(p.hcd), None, 0, ops._p(ad), p.hcd, G, (n // G) * hw,
-                   p.hcd, p.act, p.slope, st)
+            if ticket is None:
+                ad = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
+                L.call('cat_affine_res_fwd', ops._p(zd), p.hcd, ops._p(ssd[0]), ops._p(ssd[1]), sstr(p.hcd), None, 0, ops._p(ad), p.hcd, G,
+                       (n // G) * hw, p.hcd, p.act, p.slope, st)
             dad = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
+        else:
+            ad = None
         # ---- 3. second convs: weight gradients from (hidden activation slice, dT); input gradients into slices of dA1 / dAd
         side.fork()
         for b in p.branches:
@@ -597,6 +661,13 @@ class _BlockFn(torch.autograd.Function):
         if ctx.has_dw and p.dpack2_dw is not None:
             seg = tconv.Segment(None, 1, 0, False, 0, c4=p.cs, cin=c, xcs=p.cs, ptr=dt.data_ptr())
             tconv.run([seg], p.dpack2_dw, None, None, p.hcd, n, h, w, h, w, ycs=p.hcd, ycw=p.hcd, yptr=dad.data_ptr(), nvalid=sum(b['m'] for b in p.dws))
+        if ticket is not None:      # gradients of the dropped activations -> of the activations: x keep * s (in place, before the norms)
+            segs_r = _drop_segs(p, ctx.djs, 'res')
+            if segs_r:
+                ops.dropout_apply(ops.dropout_geom(m_pix, p.hc1, p.hc1, p.hc1, ctx.pdrop, segs_r, rest=0), da1, da1, ticket)
+            segs_d = _drop_segs(p, ctx.djs, 'dw')
+            if ctx.has_dw and segs_d:
+                ops.dropout_apply(ops.dropout_geom(m_pix, p.hcd, p.hcd, p.hcd, ctx.pdrop, segs_d, rest=0), dad, dad, ticket)
         if p.merge2:      # d W2 of all depthwise branches: dT^T x Ad as ONE 1x1 weight-gradient launch over the concatenated hidden buffer
             put_wgrad_into(p.gv['w2'], ops._conv_geom(n, h, w, p.hcd, p.hcd, h, w, c, p.cs, 1, 1, 1, 0, L.PAD_ZERO, wcs=p.hcd), ops._p(ad), ops._p(dt))
         if p.has_bias2:

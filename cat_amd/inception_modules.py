@@ -12,6 +12,7 @@ from . import frozen
 from . import fused_block
 from . import nn as cnn
 from . import ops
+from . import rng
 
 
 def add_prefix(name, prefix=None, split='.'):
@@ -155,13 +156,25 @@ class InvertedResidualChannels(nn.Module):
             return frozen.block_forward(self, x)
         if fused_block.applicable(self, x):     # train-mode norms: 9 launches per block, norms folded into producers / consumers
             return fused_block.apply(self, x)
-        # one alias of x per consumer (branches + residual); their gradients are summed by one add_n kernel
-        xs = ops.fanout(x, nb + 1)
-        branch_ops = list(self.res_ops) + list(self.dw_ops)
-        if ops.branch_streams_enabled() and x.is_cuda and nb > 1:
-            branches = ops.run_on_side_streams(branch_ops, xs[:nb])
-        else:
-            branches = [op(xi) for op, xi in zip(branch_ops, xs[:nb])]
+        # dropout: ONE draw per block forward, before any side-stream fork; Dropout module j (res branches first, then dw branches) masks
+        # with (ticket, j) -- the fused path draws once too and uses the same j, so both paths produce the same masks
+        drops = [(m, j) for j, op in enumerate(list(self.res_ops) + list(self.dw_ops)) for m in op.modules()
+                 if isinstance(m, cnn.Dropout) and m.training and m.p != 0]
+        if drops:
+            ticket = rng.draw(x.device)
+            for m, j in drops:
+                m._cat_ticket = (ticket, j)
+        try:
+            # one alias of x per consumer (branches + residual); their gradients are summed by one add_n kernel
+            xs = ops.fanout(x, nb + 1)
+            branch_ops = list(self.res_ops) + list(self.dw_ops)
+            if ops.branch_streams_enabled() and x.is_cuda and nb > 1:
+                branches = ops.run_on_side_streams(branch_ops, xs[:nb])
+            else:
+                branches = [op(xi) for op, xi in zip(branch_ops, xs[:nb])]
+        finally:
+            for m, _ in drops:
+                m._cat_ticket = None
         tmp = branches[0] if nb == 1 else ops.AddNFn.apply(*branches)
         tmp = self.pw_bn(tmp)
         return ops.AddNFn.apply(xs[nb], tmp)

@@ -15,6 +15,7 @@ from torch import nn
 from . import _lib as L
 from . import ops
 from . import optim
+from . import rng
 
 
 class Padded:
@@ -72,11 +73,15 @@ class Identity(nn.Module):
 
 
 class Dropout(nn.Dropout):
-    """The distillation scripts all run with dropout_rate 0; a non-zero rate is not on the path."""
+    """nn.Dropout on the dropout kernels (csrc/dropout.hip).  Inside an InvertedResidualChannels block the block draws ONE ticket per
+    forward and hands every Dropout its (ticket, j) through `_cat_ticket`; a Dropout used on its own draws its own ticket with j = 0."""
+
+    _cat_ticket = None
 
     def forward(self, x):
         if self.p != 0 and self.training:
-            raise NotImplementedError('dropout with p > 0 is outside the accelerated hot path')
+            ticket, j = self._cat_ticket if self._cat_ticket is not None else (rng.draw(x.device), 0)
+            return ops.DropoutFn.apply(x, float(self.p), ticket, j)
         return x
 
 

@@ -836,6 +836,58 @@ class ActFn(torch.autograd.Function):
         return _act_bwd(y, conform(dy), ctx.act, ctx.slope), None, None
 
 
+def dropout_geom(npix, width, xcs, ycs, p, segs, mode=L.DROP_PLAIN, rest=1, hw=1, sstride=0, act=L.ACT_NONE, slope=0.0):
+    """cat_drop_t for cat_dropout_apply.  segs: (channel offset in the buffer, the module's logical channel count, its index j in the block)."""
+    if len(segs) > L.DROP_MAXSEG:
+        raise RuntimeError('dropout: too many segments')
+    g = L.DropGeom()
+    g.npix, g.hw, g.width, g.xcs, g.ycs, g.mode, g.rest, g.sstride, g.act, g.slope = npix, hw, width, xcs, ycs, mode, rest, sstride, act, slope
+    g.drop_all = int(p >= 1.0)
+    if not g.drop_all:
+        from . import rng
+        g.thresh, g.s = rng.threshold(p), 1.0 / (1.0 - p)      # (the c_float field rounds s to float32)
+    g.nseg = len(segs)
+    for k, (c0, c, j) in enumerate(segs):
+        g.seg[k].c0, g.seg[k].c, g.seg[k].j = c0, c, j
+    return g
+
+
+def dropout_apply(g, x, y, ticket, scale=None, shift=None):
+    """Enqueue cat_dropout_apply (x, y: device pointers or tensors; y may be x)."""
+    ptr = lambda t: C.c_void_p(t) if isinstance(t, int) else _p(t)
+    L.call('cat_dropout_apply', C.byref(g), ptr(x), ptr(scale) if scale is not None else None, ptr(shift) if shift is not None else None,
+           _p(ticket), ptr(y), _stream())
+
+
+class DropoutFn(torch.autograd.Function):
+    """nn.Dropout(p) in training mode on an NHWC activation: y = keep ? x * s : 0 with the mask of (ticket, j) (csrc/dropout.hip); the
+    backward pass re-derives the same mask from the saved ticket: dx = dy * keep * s."""
+
+    @staticmethod
+    def forward(ctx, x, p, ticket, j):
+        _require_cuda(x)
+        x = conform(x)
+        n, c, h, w = x.shape
+        cs = act_cs(x)
+        ticket.record_stream(torch.cuda.current_stream())      # drawn on the block's stream, read here (possibly a branch stream)
+        y = empty_act(n, c, h, w, x.device, cs)
+        dropout_apply(dropout_geom(n * h * w, cs, cs, cs, p, [(0, c, j)]), x, y, ticket)
+        ctx.p, ctx.j = p, j
+        ctx.save_for_backward(ticket)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (ticket,) = ctx.saved_tensors
+        dy = conform(dy)
+        n, c, h, w = dy.shape
+        cs = act_cs(dy)
+        ticket.record_stream(torch.cuda.current_stream())
+        dx = empty_act(n, c, h, w, dy.device, cs)
+        dropout_apply(dropout_geom(n * h * w, cs, cs, cs, ctx.p, [(0, c, ctx.j)]), dy, dx, ticket)
+        return dx, None, None, None
+
+
 class ReplicatePadFn(torch.autograd.Function):
     """nn.ReplicationPad2d(pad): materialised (reference inception_modules.py:114-115; no launch script selects it)."""
 

@@ -559,6 +559,42 @@ int cat_tnorm_finalize2(const float* part, int scs, int G, int N, int Ho, int Wo
                         const float* beta, int nslices, const cat_nslice_t* slices, float eps, float momentum, float* scale, float* shift,
                         float* mean, float* rstd, int mstride, cat_stream_t stream);
 
+/* Dropout (dropout.hip).  Replaces the nn.Dropout(dropout_rate) of every InvertedResidualChannels branch, models/modules/inception_modules.py:144
+ * (res branch, after the first ConvBNReLU) and :174 (dw branch, after the depthwise ConvBNReLU).  Masks come from Philox4x32-10; element
+ * e = ((n*H + h)*W + w)*C + c of a module with C (unpadded) channels is kept iff
+ *   philox(counter = (lo32(e >> 2), hi32(e >> 2), j, d), key = (lo32(seed), hi32(seed)))[e & 3] >= thresh,   thresh = floor(p * 2^32)
+ * and a kept element is scaled by s = float(1 / (1 - p)).  (d, seed) come from a ticket that cat_rng_draw wrote on the device: a captured
+ * graph draws a fresh d at every replay, and the backward pass reads the ticket its forward drew.
+ *
+ * cat_rng_draw: state = {seed, counter} (int64, device memory); one thread writes ticket[0..3] = {lo32(counter), lo32(seed), hi32(seed), 0}
+ * and increments the counter. */
+int cat_rng_draw(int64_t* state, int* ticket, cat_stream_t stream);
+#define CAT_DROP_MAXSEG 8
+enum { CAT_DROP_PLAIN = 0, CAT_DROP_NORM = 1 };
+typedef struct {
+  int c0; /* first channel of the module's slice inside the buffer (multiple of 4) */
+  int c;  /* the module's logical channel count C (mask index e = pixel * C + channel); channels [c, round_up(c, 4)) are not masked */
+  int j;  /* the module's index inside its block (res branches first, then dw branches): Philox counter word 2 */
+} cat_dropseg_t;
+typedef struct {
+  int npix;          /* N * H * W pixels */
+  int hw;            /* H * W: pixels per image (per-image scale / shift) */
+  int width;         /* channels processed per pixel, from channel 0 of x and y (multiple of 4) */
+  int xcs, ycs;      /* pixel strides of x and y (multiples of 4); y may alias x */
+  int mode;          /* CAT_DROP_PLAIN: y = x * keep * s;  CAT_DROP_NORM: y = act(x * scale + shift) * keep * s */
+  int rest;          /* channels outside every segment: 1 = written without dropout, 0 = left untouched */
+  int sstride;       /* CAT_DROP_NORM: scale / shift of image n start at n * sstride (0: one vector, BatchNorm) */
+  int act;           /* CAT_DROP_NORM: activation after the affine */
+  float slope;
+  unsigned int thresh; /* floor(p * 2^32) */
+  float s;             /* float(1 / (1 - p)) */
+  int drop_all;        /* p == 1: every masked element is 0 */
+  int nseg;
+  cat_dropseg_t seg[CAT_DROP_MAXSEG];
+} cat_drop_t;
+int cat_dropout_apply(const cat_drop_t* g, const float* x, const float* scale, const float* shift, const int* ticket, float* y,
+                      cat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
