@@ -15,6 +15,7 @@
 // Ragged channel counts (pruned students: 4..17, 56, 82 ...) never touch HBM layout beyond the 4-float pixel
 // stride: the N edge is handled by 16-wide tile variants chosen per layer, the K edge by zero-filled quads.
 #include "common.h"
+#include <limits.h>
 #include <stdlib.h>
 
 namespace {
@@ -68,6 +69,29 @@ __device__ __forceinline__ f4 ldw4_or_zero(bool valid, bool vec, const float* wp
   return v;
 }
 
+// ------------------------------------------------------------------------------------------------ shared tile code
+template <int MT, int NT>
+__device__ __forceinline__ void zero_acc(f4 (&acc)[MT][NT]) {
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+}
+
+// The 16-deep MFMA block of one wave tile; fragments are f4 (K-contiguous tiles) or float[4] (N-contiguous tiles) per 16 rows.
+// BFIRST: the B fragment goes in as the MFMA's FIRST operand, which leaves the accumulators transposed (see store_pixel_t).
+template <bool BFIRST, int MT, int NT, typename FA, typename FB>
+__device__ __forceinline__ void mfma_block(const FA (&fa)[MT], const FB (&fb)[NT], f4 (&acc)[MT][NT]) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+        acc[i][j] = BFIRST ? __builtin_amdgcn_mfma_f32_16x16x4f32(fb[j][t], fa[i][t], acc[i][j], 0, 0, 0)
+                           : __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][t], fb[j][t], acc[i][j], 0, 0, 0);
+}
+
 template <int MT, int NT>
 __device__ __forceinline__ void mma_kcontig_a_kcontig_b(const float* A, const float* B, int arow0, int brow0, int lane,
                                                        f4 (&acc)[MT][NT]) {
@@ -77,12 +101,171 @@ __device__ __forceinline__ void mma_kcontig_a_kcontig_b(const float* A, const fl
   for (int i = 0; i < MT; ++i) fa[i] = *reinterpret_cast<const f4*>(A + swz(arow0 + i * 16 + lr, lq));
 #pragma unroll
   for (int j = 0; j < NT; ++j) fb[j] = *reinterpret_cast<const f4*>(B + swz(brow0 + j * 16 + lr, lq));
+  mfma_block<false>(fa, fb, acc);
+}
+
+// [row][32 k] tiles of the BK = 32 kernels: same XOR swizzle idea as swz over the eight quads of a row
+__device__ __forceinline__ int swz32(int r, int q) { return (r * 8 + (q ^ ((r >> 1) & 7))) * 4; }
+
+// fragments of 16-deep half h of a [row][32 k] tile (ds_read_b128)
+template <int N>
+__device__ __forceinline__ void read_kcontig32(const float* T, int row0, int lane, int h, f4 (&f)[N]) {
+  const int lr = lane & 15, lq = lane >> 4;
 #pragma unroll
-  for (int t = 0; t < 4; ++t)
+  for (int i = 0; i < N; ++i) f[i] = *reinterpret_cast<const f4*>(T + swz32(row0 + i * 16 + lr, lq + 4 * h));
+}
+
+// fragments of k-rows row0 .. row0 + 15 of an N-contiguous tile [k][LD] without row padding (ds_read_b32): the 16-column group of row r is
+// XOR-ed with (r >> 2) & 3 (== lq for the four rows a lane reads) instead
+template <int LD, int N>
+__device__ __forceinline__ void read_ncontig(const float* T, int row0, int col0, int lane, float (&f)[N][4]) {
+  const int lr = lane & 15, lq = lane >> 4;
 #pragma unroll
-    for (int i = 0; i < MT; ++i)
+  for (int j = 0; j < N; ++j)
 #pragma unroll
-      for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][t], fb[j][t], acc[i][j], 0, 0, 0);
+    for (int t = 0; t < 4; ++t) f[j][t] = T[(row0 + lq * 4 + t) * LD + ((col0 + j * 16 + lr) ^ (lq << 4))];
+}
+
+// one 32-deep chunk, A and B tiles [row][32 k]
+template <bool BFIRST, int MT, int NT>
+__device__ __forceinline__ void mma32_kcontig_a_kcontig_b(const float* A, const float* B, int arow0, int brow0, int lane, f4 (&acc)[MT][NT]) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    f4 fa[MT], fb[NT];
+    read_kcontig32(A, arow0, lane, h, fa);
+    read_kcontig32(B, brow0, lane, h, fb);
+    mfma_block<BFIRST>(fa, fb, acc);
+  }
+}
+
+// one 32-deep chunk, A tile [row][32 k], B tile [32 k][BN] with XOR-ed column groups
+template <bool BFIRST, int BN, int MT, int NT>
+__device__ __forceinline__ void mma32_kcontig_a_ncontig_b(const float* A, const float* B, int arow0, int bcol0, int lane, f4 (&acc)[MT][NT]) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    f4 fa[MT];
+    float fb[NT][4];
+    read_kcontig32(A, arow0, lane, h, fa);
+    read_ncontig<BN>(B, h * 16, bcol0, lane, fb);
+    mfma_block<BFIRST>(fa, fb, acc);
+  }
+}
+
+// the filter-tap walk moves one tap on, row-major over (ky, kx)
+__device__ __forceinline__ void next_tap(int& ky, int& kx, int kw) {
+  if (++kx == kw) {
+    kx = 0;
+    ++ky;
+  }
+}
+
+// m -> (n, y, x) of a pixel-major [N][H][W] index space (HW = H * W).  Rows beyond the tile's M are decoded as pixel 0 by the callers
+// (`rv ? m : 0`): their loads are parked or masked, but the address arithmetic stays in range.
+struct Pixel { int n, y, x; };
+__device__ __forceinline__ Pixel decode_pixel(int m, int HW, int W) {
+  const int n = m / HW, rem = m - n * HW;
+  const int y = rem / W;
+  return Pixel{n, y, rem - y * W};
+}
+
+// One chunk of both operand tiles DMA-ed straight into LDS (buffer_load_dwordx4 ... lds): wave w's instruction i writes the 256 floats
+// (64 lanes x 16 bytes, lane-linear) at tile + (w * 4 + i) * 256.  voff = per-lane byte offsets (0x80000000: beyond num_records, the
+// buffer unit returns zeros), so = wave-uniform byte offset of the chunk.
+typedef __attribute__((address_space(3))) void* lds_t;
+__device__ __forceinline__ void dma_chunk(__amdgpu_buffer_rsrc_t rA, __amdgpu_buffer_rsrc_t rB, float* tA, float* tB, int wave,
+                                          const unsigned (&voffA)[4], const unsigned (&voffB)[4], unsigned soA, unsigned soB) {
+  float* dA = tA + wave * 4 * 256;
+  float* dB = tB + wave * 4 * 256;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_t)(dA + i * 256), 16, voffA[i], soA, 0, 0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_t)(dB + i * 256), 16, voffB[i], soB, 0, 0);
+}
+
+// Row-major accumulators (lane (lr, lq) holds rows i * 16 + lq * 4 + 0..3 of column j * 16 + lr) of the forward kernels:
+// out[m][col] = act(acc + bias[col]) for col < Cout, zeros for Cout <= col < cw.  m0 / n0 = first row / column of the WAVE tile.
+template <int MT, int NT>
+__device__ __forceinline__ void store_rows(const IgemmArgs& p, const f4 (&acc)[MT][NT], int m0, int n0, int lane) {
+  const int lr = lane & 15, lq = lane >> 4;
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int col = n0 + j * 16 + lr;
+    const bool cvalid = col < p.Cout;
+    const float bias = (cvalid && p.bias) ? p.bias[col] : 0.f;
+    if (!cvalid && col >= p.cw) continue;
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        const int m = m0 + i * 16 + lq * 4 + rg;
+        if (m < p.M) p.out[(int64_t)m * p.ycs + col] = cvalid ? cat::apply_act(acc[i][j][rg] + bias, p.act, p.slope) : 0.f;
+      }
+    }
+  }
+}
+
+// Transposed accumulators (mfma_block<true>): lane (lr, lq) holds channels j * 16 + lq * 4 + 0..3 of tile row (pixel) i * 16 + lr -- one
+// pixel address and one float4 store per tile instead of four of each (round 6: -3.7 % on a 256 -> 256 3x3 forward).
+// orow = the pixel of tile row i, c0 = first channel of the wave tile + lq * 4, C = valid channels; zeros for C <= c < cw.
+template <int MT, int NT>
+__device__ __forceinline__ void store_pixel_t(const IgemmArgs& p, float* orow, const f4 (&acc)[MT][NT], int i, int c0, int C, bool vec) {
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int cj = c0 + j * 16;
+    if (cj >= p.cw) continue;
+    if (vec && cj + 3 < C) {
+      f4 v = acc[i][j];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = cat::apply_act(v[e] + (p.bias ? p.bias[cj + e] : 0.f), p.act, p.slope);
+      *reinterpret_cast<f4*>(orow + cj) = v;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = cj + e;
+        if (c < C) orow[c] = cat::apply_act(acc[i][j][e] + (p.bias ? p.bias[c] : 0.f), p.act, p.slope);
+        else if (c < p.cw) orow[c] = 0.f;
+      }
+    }
+  }
+}
+
+// Stride-parity class of a dgrad problem (blockIdx.y = py * stride + px): the input pixels (iyf + a * s, ixf + b * s), a < Hc, b < Wc,
+// of the (possibly padded) input plane receive only the filter taps (py + jy * s, px + jx * s), jy < nty, jx < ntx; class pixel (a, b)
+// and class tap (jy, jx) meet at dy pixel (cy0 + a - jy, cx0 + b - jx).
+struct DgradClass { int s, py, px, iyf, ixf, Hc, Wc, cy0, cx0, nty, ntx, Mc; };
+__device__ __forceinline__ DgradClass dgrad_class(const IgemmArgs& p, int cls) {
+  DgradClass c;
+  c.s = p.stride;
+  c.py = cls / c.s;
+  c.px = cls % c.s;
+  c.iyf = ((c.py - p.pad_eff) % c.s + c.s) % c.s;
+  c.ixf = ((c.px - p.pad_eff) % c.s + c.s) % c.s;
+  c.Hc = c.iyf < p.Hin ? (p.Hin - c.iyf + c.s - 1) / c.s : 0;
+  c.Wc = c.ixf < p.Win ? (p.Win - c.ixf + c.s - 1) / c.s : 0;
+  c.cy0 = (c.iyf + p.pad_eff - c.py) / c.s;
+  c.cx0 = (c.ixf + p.pad_eff - c.px) / c.s;
+  c.nty = c.py < p.kh ? (p.kh - c.py + c.s - 1) / c.s : 0;
+  c.ntx = c.px < p.kw ? (p.kw - c.px + c.s - 1) / c.s : 0;
+  c.Mc = p.N * c.Hc * c.Wc;
+  return c;
+}
+// output pixel of class pixel m (< Mc) in the input plane, in pixels
+__device__ __forceinline__ int64_t dgrad_out_pixel(const IgemmArgs& p, const DgradClass& c, int m) {
+  const Pixel px = decode_pixel(m, c.Hc * c.Wc, c.Wc);
+  return ((int64_t)px.n * p.Hin + (c.iyf + px.y * c.s)) * p.Win + (c.ixf + px.x * c.s);
+}
+
+// One weight-gradient element (filter co, column k = (tap, ci)): straight into dw (`direct`, optionally accumulating) or into this pixel
+// slice's (blockIdx.y) workspace [slice][Cout][K]
+__device__ __forceinline__ void store_dw(const IgemmArgs& p, int co, int k, int tap, int ci, int taps, float v) {
+  if (p.direct) {
+    if (ci < p.cval) {   // cval = writable channels per tap (Cin, or the padded extent when the storage is padded)
+      float* dst = p.out + ((int64_t)co * taps + tap) * p.wcs + ci;
+      *dst = p.accumulate ? *dst + v : v;
+    }
+  } else {
+    p.out[((int64_t)blockIdx.y * p.Cout + co) * p.K + k] = v;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ forward
@@ -109,12 +292,10 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(IgemmArgs p) {
   for (int i = 0; i < AI; ++i) {
     const int m = m0 + r0 + 64 * i;
     rv[i] = m < p.M;
-    const int mm = rv[i] ? m : 0;
-    const int n = mm / HoWo, rem = mm - n * HoWo;
-    const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-    iy0[i] = oy * p.stride - p.pad;
-    ix0[i] = ox * p.stride - p.padw;
-    xoff[i] = (int64_t)n * p.H * p.W * p.xcs;
+    const Pixel o = decode_pixel(rv[i] ? m : 0, HoWo, p.Wo);
+    iy0[i] = o.y * p.stride - p.pad;
+    ix0[i] = o.x * p.stride - p.padw;
+    xoff[i] = (int64_t)o.n * p.H * p.W * p.xcs;
   }
   const float* wrow[BI];
   bool bv[BI];
@@ -168,10 +349,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(IgemmArgs p) {
     if (aligned) {   // c4 % 16 == 0: all quads of a chunk sit in one tap, so this branch is wave-uniform (and rare)
       if (ci >= p.c4) {
         ci -= p.c4;
-        if (++kx == p.kw) {
-          kx = 0;
-          ++ky;
-        }
+        next_tap(ky, kx, p.kw);
         locate();
 #pragma unroll
         for (int i = 0; i < BI; ++i) pb[i] += 16 + p.wcs - p.c4;
@@ -204,10 +382,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(IgemmArgs p) {
   };
 
   f4 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   const int nk = (p.K + 15) >> 4;
   gload();
@@ -248,22 +423,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(IgemmArgs p) {
   if (dbg) { p.dbg[0] = t_load; p.dbg[1] = t_mma; p.dbg[2] = t_store; p.dbg[3] = t_bar; p.dbg[4] = nk - 1; }
   mma_kcontig_a_kcontig_b<MT, NT>(sA + ((nk - 1) & 1) * BM * 16, sB + ((nk - 1) & 1) * BN * 16, wm * MT * 16, wn * NT * 16, lane, acc);
 
-  const int lr = lane & 15, lq = lane >> 4;
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const int col = n0 + wn * NT * 16 + j * 16 + lr;
-    const bool cvalid = col < p.Cout;
-    const float bias = (cvalid && p.bias) ? p.bias[col] : 0.f;
-    if (!cvalid && col >= p.cw) continue;
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const int m = m0 + wm * MT * 16 + i * 16 + lq * 4 + rg;
-        if (m < p.M) p.out[(int64_t)m * p.ycs + col] = cvalid ? cat::apply_act(acc[i][j][rg] + bias, p.act, p.slope) : 0.f;
-      }
-    }
-  }
+  store_rows(p, acc, m0 + wm * MT * 16, n0 + wn * NT * 16, lane);
 }
 
 // ------------------------------------------------------------------------------------------------ forward, BK = 32
@@ -272,8 +432,6 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(IgemmArgs p) {
 // multiple of 32 (so a chunk never straddles taps and the walk is wave-uniform) and the filter rows are float4-readable.
 // Invalid rows / padding taps keep their pointer parked on the zero page (increment 0), so the steady state is one 64-bit add per
 // load and nothing else on the vector ALU.
-__device__ __forceinline__ int swz32(int r, int q) { return (r * 8 + (q ^ ((r >> 1) & 7))) * 4; }
-
 template <int MT, int NT, int WM, int WN>
 __global__ __launch_bounds__(256) void conv_fwd32_kernel(IgemmArgs p) {
   constexpr int BM = WM * MT * 16, BN = WN * NT * 16;
@@ -300,12 +458,10 @@ __global__ __launch_bounds__(256) void conv_fwd32_kernel(IgemmArgs p) {
   for (int i = 0; i < AI; ++i) {
     const int m = m0 + r0 + 32 * i;
     rv[i] = m < p.M;
-    const int mm = rv[i] ? m : 0;
-    const int n = mm / HoWo, rem = mm - n * HoWo;
-    const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-    iy0[i] = oy * p.stride - p.pad;
-    ix0[i] = ox * p.stride - p.padw;
-    xoff[i] = (int64_t)n * p.H * p.W * p.xcs;
+    const Pixel o = decode_pixel(rv[i] ? m : 0, HoWo, p.Wo);
+    iy0[i] = o.y * p.stride - p.pad;
+    ix0[i] = o.x * p.stride - p.padw;
+    xoff[i] = (int64_t)o.n * p.H * p.W * p.xcs;
   }
   const int nk_all = (p.K + 31) >> 5;   // a trailing half chunk reads zeros (tap >= taps)
   const int kbeg = p.ksplit > 1 ? (int)blockIdx.y * p.kchunks : 0;
@@ -369,10 +525,7 @@ __global__ __launch_bounds__(256) void conv_fwd32_kernel(IgemmArgs p) {
     while (ci >= p.c4) {   // wave-uniform
       ci -= p.c4;
       ++tap;
-      if (++kx == p.kw) {
-        kx = 0;
-        ++ky;
-      }
+      next_tap(ky, kx, p.kw);
       moved = true;
     }
     if (moved) {
@@ -394,27 +547,9 @@ __global__ __launch_bounds__(256) void conv_fwd32_kernel(IgemmArgs p) {
   };
   const int lr = lane & 15, lq = lane >> 4;
   f4 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   auto mma = [&](int buf) {
-    const float* A = sA + buf * BM * 32;
-    const float* B = sB + buf * BN * 32;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      f4 fa[MT], fb[NT];
-#pragma unroll
-      for (int i = 0; i < MT; ++i) fa[i] = *reinterpret_cast<const f4*>(A + swz32(wm * MT * 16 + i * 16 + lr, lq + 4 * h));
-#pragma unroll
-      for (int j = 0; j < NT; ++j) fb[j] = *reinterpret_cast<const f4*>(B + swz32(wn * NT * 16 + j * 16 + lr, lq + 4 * h));
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][t], fb[j][t], acc[i][j], 0, 0, 0);
-    }
+    mma32_kcontig_a_kcontig_b<false>(sA + buf * BM * 32, sB + buf * BN * 32, wm * MT * 16, wn * NT * 16, lane, acc);
   };
 
   gload();
@@ -447,21 +582,7 @@ __global__ __launch_bounds__(256) void conv_fwd32_kernel(IgemmArgs p) {
     }
     return;
   }
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const int col = n0 + wn * NT * 16 + j * 16 + lr;
-    const bool cvalid = col < p.Cout;
-    const float bias = (cvalid && p.bias) ? p.bias[col] : 0.f;
-    if (!cvalid && col >= p.cw) continue;
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const int m = m0 + wm * MT * 16 + i * 16 + lq * 4 + rg;
-        if (m < p.M) p.out[(int64_t)m * p.ycs + col] = cvalid ? cat::apply_act(acc[i][j][rg] + bias, p.act, p.slope) : 0.f;
-      }
-    }
-  }
+  store_rows(p, acc, m0 + wm * MT * 16, n0 + wn * NT * 16, lane);
 }
 
 // ------------------------------------------------------------------------------------------------ forward, BK = 32, direct-to-LDS staging
@@ -473,11 +594,10 @@ __global__ __launch_bounds__(256) void conv_fwd32_kernel(IgemmArgs p) {
 // tiles is applied to the SOURCE quad each lane fetches (guide rule 21); the fragment reads keep conv_fwd32_kernel's swz32.
 // Out-of-image / padding / tail lanes carry voffset 0x80000000: beyond num_records, the buffer unit returns zeros.
 // Preconditions (host): Cin % 32 == 0 (a 32-chunk never straddles taps), float4-readable filters, tensors < 2 GB.
-template <int WMW>   // dummy parameter keeps the kernel a template like its siblings (2 x 2 waves of 4 x 4 MFMA tiles)
+// 2 x 2 waves of 4 x 4 MFMA tiles.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_fwd32d_kernel(IgemmArgs p) {
   constexpr int MT = 4, NT = 4, WN = 2, BM = 128, BN = 128;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  typedef __attribute__((address_space(3))) void* lds_t;
   float* sA = smem;
   float* sB = smem + 2 * BM * 32;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -499,12 +619,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const unsigned q = (unsigned)(slot ^ ((row >> 1) & 7));
     const int m = m0 + row;
     rv[i] = m < p.M;
-    const int mm = rv[i] ? m : 0;
-    const int n = mm / HoWo, rem = mm - n * HoWo;
-    const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-    iy0[i] = oy * p.stride - p.pad;
-    ix0[i] = ox * p.stride - p.padw;
-    abase[i] = (unsigned)n * (unsigned)(p.H * p.W) * (unsigned)p.xcs * 4u;
+    const Pixel o = decode_pixel(rv[i] ? m : 0, HoWo, p.Wo);
+    iy0[i] = o.y * p.stride - p.pad;
+    ix0[i] = o.x * p.stride - p.padw;
+    abase[i] = (unsigned)o.n * (unsigned)(p.H * p.W) * (unsigned)p.xcs * 4u;
     aq[i] = q * 16u;
     const int co = n0 + row;
     voffB[i] = co < p.Cout ? (unsigned)co * (unsigned)(taps * p.wcs) * 4u + q * 16u : 0x80000000u;
@@ -525,46 +643,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   locate(0, 0);
   auto issue = [&](int buf) {
     const unsigned soA = (unsigned)ci * 4u, soB = (unsigned)(tap * p.wcs + ci) * 4u;
-    float* dA = sA + buf * BM * 32 + wave * 4 * 256;
-    float* dB = sB + buf * BN * 32 + wave * 4 * 256;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_t)(dA + i * 256), 16, voffA[i], soA, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_t)(dB + i * 256), 16, voffB[i], soB, 0, 0);
+    dma_chunk(rA, rB, sA + buf * BM * 32, sB + buf * BN * 32, wave, voffA, voffB, soA, soB);
     ci += 32;
     if (ci >= p.c4) {      // next tap (wave-uniform, once per Cin / 32 chunks)
       ci = 0;
       ++tap;
-      if (++kx == p.kw) {
-        kx = 0;
-        ++ky;
-      }
+      next_tap(ky, kx, p.kw);
       if (tap < taps) locate(ky, kx);
     }
   };
   const int lr = lane & 15, lq = lane >> 4;
   f4 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-  auto mma = [&](int buf) {
-    const float* A = sA + buf * BM * 32;
-    const float* B = sB + buf * BN * 32;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      f4 fa[MT], fb[NT];
-#pragma unroll
-      for (int i = 0; i < MT; ++i) fa[i] = *reinterpret_cast<const f4*>(A + swz32(wm * MT * 16 + i * 16 + lr, lq + 4 * h));
-#pragma unroll
-      for (int j = 0; j < NT; ++j) fb[j] = *reinterpret_cast<const f4*>(B + swz32(wn * NT * 16 + j * 16 + lr, lq + 4 * h));
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[j][t], fa[i][t], acc[i][j], 0, 0, 0);   // D^T: see the epilogue
-    }
+  zero_acc(acc);
+  auto mma = [&](int buf) {   // filters first: transposed accumulators, see the epilogue
+    mma32_kcontig_a_kcontig_b<true>(sA + buf * BM * 32, sB + buf * BN * 32, wm * MT * 16, wn * NT * 16, lane, acc);
   };
   const int nk = taps * (p.c4 >> 5);
   issue(0);
@@ -579,32 +671,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
   mma((nk - 1) & 1);
 
-  // The filter fragment went in as the MFMA's FIRST operand: the accumulators are transposed, lane (lr, lq) holds output channels
-  // j * 16 + lq * 4 + 0..3 of pixel i * 16 + lr -- one float4 store per tile instead of four scalar ones (round 6: -3.7 % on a 256 -> 256 3x3)
+  // The filter fragment went in as the MFMA's FIRST operand: the accumulators are transposed (store_pixel_t)
   const bool vec = (p.ycs & 3) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0;
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
     const int m = m0 + wm * MT * 16 + i * 16 + lr;
     if (m >= p.M) continue;
-    float* yo = p.out + (int64_t)m * p.ycs;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int c0 = n0 + wn * NT * 16 + j * 16 + lq * 4;
-      if (c0 >= p.cw) continue;
-      if (vec && c0 + 3 < p.Cout) {
-        f4 v = acc[i][j];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = cat::apply_act(v[e] + (p.bias ? p.bias[c0 + e] : 0.f), p.act, p.slope);
-        *reinterpret_cast<f4*>(yo + c0) = v;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int c = c0 + e;
-          if (c < p.Cout) yo[c] = cat::apply_act(acc[i][j][e] + (p.bias ? p.bias[c] : 0.f), p.act, p.slope);
-          else if (c < p.cw) yo[c] = 0.f;
-        }
-      }
-    }
+    store_pixel_t(p, p.out + (int64_t)m * p.ycs, acc, i, n0 + wn * NT * 16 + lq * 4, p.Cout, vec);
   }
 }
 
@@ -621,21 +694,14 @@ __global__ __launch_bounds__(256) void conv_dgrad_kernel(IgemmArgs p) {
   float* sB = smem + 2 * BM * 16;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  const int s = p.stride;
-  const int py = blockIdx.y / s, px = blockIdx.y % s;
-  // pixels of this class in the (possibly padded) input plane
-  const int iyf = ((py - p.pad_eff) % s + s) % s, ixf = ((px - p.pad_eff) % s + s) % s;
-  const int Hc = iyf < p.Hin ? (p.Hin - iyf + s - 1) / s : 0, Wc = ixf < p.Win ? (p.Win - ixf + s - 1) / s : 0;
-  const int cy0 = (iyf + p.pad_eff - py) / s, cx0 = (ixf + p.pad_eff - px) / s;
-  const int nty = py < p.kh ? (p.kh - py + s - 1) / s : 0, ntx = px < p.kw ? (p.kw - px + s - 1) / s : 0;
-  const int K = nty * ntx * p.c4;
-  const int Mc = p.N * Hc * Wc;
+  const DgradClass cls = dgrad_class(p, blockIdx.y);
+  const int K = cls.nty * cls.ntx * p.c4;
   const int ntn = (p.Cin + BN - 1) / BN;
   const int bid = cat::xcd_remap(blockIdx.x, gridDim.x);
   const int m0 = (bid / ntn) * BM, n0 = (bid % ntn) * BN;
-  if (m0 >= Mc) return;
+  if (m0 >= cls.Mc) return;
   const int q = tid & 3, r0 = tid >> 2;
-  const int HcWc = Hc * Wc;
+  const int HcWc = cls.Hc * cls.Wc;
   const int taps = p.kh * p.kw;
 
   int cy[AI], cx[AI];
@@ -644,13 +710,11 @@ __global__ __launch_bounds__(256) void conv_dgrad_kernel(IgemmArgs p) {
 #pragma unroll
   for (int i = 0; i < AI; ++i) {
     const int m = m0 + r0 + 64 * i;
-    rv[i] = m < Mc;
-    const int mm = rv[i] ? m : 0;
-    const int n = mm / HcWc, rem = mm - n * HcWc;
-    const int a = rem / Wc, b = rem - a * Wc;
-    cy[i] = cy0 + a;
-    cx[i] = cx0 + b;
-    aoff[i] = (int64_t)n * p.Ho * p.Wo * p.ycs;
+    rv[i] = m < cls.Mc;
+    const Pixel cp = decode_pixel(rv[i] ? m : 0, HcWc, cls.Wc);
+    cy[i] = cls.cy0 + cp.y;
+    cx[i] = cls.cx0 + cp.x;
+    aoff[i] = (int64_t)cp.n * p.Ho * p.Wo * p.ycs;
   }
 
   // incremental K walk (see conv_fwd_kernel): A quad = (tap (jy,jx), co..co+3) of dy; B rows = 16 consecutive k of the chunk
@@ -662,8 +726,8 @@ __global__ __launch_bounds__(256) void conv_dgrad_kernel(IgemmArgs p) {
   {
     const int tj = p.c4 ? ka / p.c4 : 0;
     aco = ka - tj * p.c4;
-    ajy = ntx ? tj / ntx : 0;
-    ajx = tj - ajy * ntx;
+    ajy = cls.ntx ? tj / cls.ntx : 0;
+    ajx = tj - ajy * cls.ntx;
   }
   const float* pa[AI];
   bool va[AI];
@@ -681,7 +745,7 @@ __global__ __launch_bounds__(256) void conv_dgrad_kernel(IgemmArgs p) {
   const float* pb[BI];
   bool vb[BI];
   auto locate_b = [&](int i) {
-    const int ky = py + bjy[i] * s, kx = px + bjx[i] * s;
+    const int ky = cls.py + bjy[i] * cls.s, kx = cls.px + bjx[i] * cls.s;
     vb[i] = bco[i] < p.Cout && bci[i] < p.Cin;
     pb[i] = p.b + ((int64_t)(vb[i] ? bco[i] : 0) * taps + ky * p.kw + kx) * p.wcs + bci[i];
   };
@@ -693,8 +757,8 @@ __global__ __launch_bounds__(256) void conv_dgrad_kernel(IgemmArgs p) {
     const int kk = kr < 16 ? kr + kbeg * 16 : 0;
     const int tj = p.c4 ? kk / p.c4 : 0;
     bco[i] = kk - tj * p.c4;
-    bjy[i] = ntx ? tj / ntx : 0;
-    bjx[i] = tj - bjy[i] * ntx;
+    bjy[i] = cls.ntx ? tj / cls.ntx : 0;
+    bjx[i] = tj - bjy[i] * cls.ntx;
     bci[i] = n0 + nq * 4;
     locate_b(i);
   }
@@ -716,18 +780,12 @@ __global__ __launch_bounds__(256) void conv_dgrad_kernel(IgemmArgs p) {
     if (aligned) {   // wave-uniform: every quad / row of the chunk wraps to the next tap together
       if (aco >= p.c4) {
         aco -= p.c4;
-        if (++ajx == ntx) {
-          ajx = 0;
-          ++ajy;
-        }
+        next_tap(ajy, ajx, cls.ntx);
         locate_a();
 #pragma unroll
         for (int i = 0; i < BI; ++i) {
           bco[i] -= p.c4;
-          if (++bjx[i] == ntx) {
-            bjx[i] = 0;
-            ++bjy[i];
-          }
+          next_tap(bjy[i], bjx[i], cls.ntx);
           locate_b(i);
         }
       } else {
@@ -742,7 +800,7 @@ __global__ __launch_bounds__(256) void conv_dgrad_kernel(IgemmArgs p) {
     } else {
       while (aco >= p.c4) {
         aco -= p.c4;
-        const bool w = ++ajx == ntx;
+        const bool w = ++ajx == cls.ntx;
         ajx = w ? 0 : ajx;
         ajy += w ? 1 : 0;
       }
@@ -751,7 +809,7 @@ __global__ __launch_bounds__(256) void conv_dgrad_kernel(IgemmArgs p) {
       for (int i = 0; i < BI; ++i) {
         while (bco[i] >= p.c4) {
           bco[i] -= p.c4;
-          const bool w = ++bjx[i] == ntx;
+          const bool w = ++bjx[i] == cls.ntx;
           bjx[i] = w ? 0 : bjx[i];
           bjy[i] += w ? 1 : 0;
         }
@@ -771,10 +829,7 @@ __global__ __launch_bounds__(256) void conv_dgrad_kernel(IgemmArgs p) {
   };
 
   f4 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   const int lr = lane & 15, lq = lane >> 4;
   if (nk > 0) {
@@ -813,10 +868,8 @@ __global__ __launch_bounds__(256) void conv_dgrad_kernel(IgemmArgs p) {
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg) {
       const int m = m0 + wm * MT * 16 + i * 16 + lq * 4 + rg;
-      if (m >= Mc) continue;
-      const int n = m / HcWc, rem = m - n * HcWc;
-      const int a = rem / Wc, b = rem - a * Wc;
-      const int64_t opix = (((int64_t)n * p.Hin + (iyf + a * s)) * p.Win + (ixf + b * s)) * p.ocs;
+      if (m >= cls.Mc) continue;
+      const int64_t opix = dgrad_out_pixel(p, cls, m) * p.ocs;
       if (p.ksplit > 1) {   // raw partial sums of this K slice
         float* prow = p.part + (int64_t)blockIdx.z * p.N * p.Hin * p.Win * p.ocs + opix;
 #pragma unroll
@@ -860,22 +913,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   float* sB = smem + 2 * BM * 32;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  const int s = p.stride;
-  const int py = blockIdx.y / s, px = blockIdx.y % s;
-  const int iyf = ((py - p.pad_eff) % s + s) % s, ixf = ((px - p.pad_eff) % s + s) % s;
-  const int Hc = iyf < p.Hin ? (p.Hin - iyf + s - 1) / s : 0, Wc = ixf < p.Win ? (p.Win - ixf + s - 1) / s : 0;
-  const int cy0 = (iyf + p.pad_eff - py) / s, cx0 = (ixf + p.pad_eff - px) / s;
-  const int nty = py < p.kh ? (p.kh - py + s - 1) / s : 0, ntx = px < p.kw ? (p.kw - px + s - 1) / s : 0;
-  const int ntaps = nty * ntx, ntxd = ntx > 0 ? ntx : 1;
+  const DgradClass cls = dgrad_class(p, blockIdx.y);
+  const int ntaps = cls.nty * cls.ntx, ntxd = cls.ntx > 0 ? cls.ntx : 1;
   const int K = ntaps * p.c4;
-  const int Mc = p.N * Hc * Wc;
   const int ntn = (p.Cin + BN - 1) / BN;
   const int bid = cat::xcd_remap(blockIdx.x, gridDim.x);
   const int m0 = (bid / ntn) * BM, n0 = (bid % ntn) * BN;
-  if (m0 >= Mc) return;
+  if (m0 >= cls.Mc) return;
   const int half = __builtin_amdgcn_readfirstlane(wave >> 1);
   const int q4 = tid & 3, q = half * 4 + q4, r0 = (tid & 127) >> 2;
-  const int HcWc = Hc * Wc;
+  const int HcWc = cls.Hc * cls.Wc;
   const int taps = p.kh * p.kw;
 
   int cy[AI], cx[AI];
@@ -884,13 +931,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
   for (int i = 0; i < AI; ++i) {
     const int m = m0 + r0 + 32 * i;
-    rv[i] = m < Mc;
-    const int mm = rv[i] ? m : 0;
-    const int n = mm / HcWc, rem = mm - n * HcWc;
-    const int a = rem / Wc, b = rem - a * Wc;
-    cy[i] = cy0 + a;
-    cx[i] = cx0 + b;
-    aoff[i] = (int64_t)n * p.Ho * p.Wo * p.ycs;
+    rv[i] = m < cls.Mc;
+    const Pixel cp = decode_pixel(rv[i] ? m : 0, HcWc, cls.Wc);
+    cy[i] = cls.cy0 + cp.y;
+    cx[i] = cls.cx0 + cp.x;
+    aoff[i] = (int64_t)cp.n * p.Ho * p.Wo * p.ycs;
   }
 
   // A walk: this thread's quad = (class tap atj = (ajy, ajx), channels aco .. aco+3 of dy), advanced by 32 per chunk
@@ -924,7 +969,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   int incb[BI];
   auto locate_b = [&](int i) {
     const int jy = btj[i] / ntxd, jx = btj[i] - jy * ntxd;
-    const int ky = py + jy * s, kx = px + jx * s;
+    const int ky = cls.py + jy * cls.s, kx = cls.px + jx * cls.s;
     const bool v = bcv && btj[i] < ntaps;
     pb[i] = v ? p.b + ((int64_t)bco[i] * taps + ky * p.kw + kx) * p.wcs + bci : g_zero_page;
     incb[i] = v ? bstep : 0;
@@ -948,10 +993,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       do {
         aco -= p.c4;
         ++atj;
-        if (++ajx == ntxd) {
-          ajx = 0;
-          ++ajy;
-        }
+        next_tap(ajy, ajx, ntxd);
       } while (aco >= p.c4);
       locate_a();
     } else {
@@ -983,32 +1025,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   };
 
   f4 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   const int lr = lane & 15, lq = lane >> 4;
   auto mma = [&](int buf) {
-    const float* A = sA + buf * BM * 32;
-    const float* B = sB + buf * 32 * BN;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      f4 fa[MT];
-      float fb[NT][4];
-#pragma unroll
-      for (int i = 0; i < MT; ++i) fa[i] = *reinterpret_cast<const f4*>(A + swz32(wm * MT * 16 + i * 16 + lr, lq + 4 * h));
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) fb[j][t] = B[(h * 16 + lq * 4 + t) * BN + ((wn * NT * 16 + j * 16 + lr) ^ (lq << 4))];
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][t], fb[j][t], acc[i][j], 0, 0, 0);
-    }
+    mma32_kcontig_a_ncontig_b<false, BN>(sA + buf * BM * 32, sB + buf * 32 * BN, wm * MT * 16, wn * NT * 16, lane, acc);
   };
 
   const int nk = (K + 31) >> 5;   // a trailing half chunk has tap == ntaps: parked on the zero page
@@ -1032,10 +1053,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg) {
       const int m = m0 + wm * MT * 16 + i * 16 + lq * 4 + rg;
-      if (m >= Mc) continue;
-      const int n = m / HcWc, rem = m - n * HcWc;
-      const int a = rem / Wc, b = rem - a * Wc;
-      float* orow = p.out + (((int64_t)n * p.Hin + (iyf + a * s)) * p.Win + (ixf + b * s)) * p.ocs;
+      if (m >= cls.Mc) continue;
+      float* orow = p.out + dgrad_out_pixel(p, cls, m) * p.ocs;
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
         const int col = n0 + wn * NT * 16 + j * 16 + lr;
@@ -1061,24 +1080,17 @@ template <bool BT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_dgrad32d_kernel(IgemmArgs p) {
   constexpr int MT = 4, NT = 4, WN = 2, BM = 128, BN = 128;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  typedef __attribute__((address_space(3))) void* lds_t;
   float* sA = smem;
   float* sB = smem + 2 * BM * 32;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
-  const int s = p.stride;
-  const int py = blockIdx.y / s, px = blockIdx.y % s;
-  const int iyf = ((py - p.pad_eff) % s + s) % s, ixf = ((px - p.pad_eff) % s + s) % s;
-  const int Hc = iyf < p.Hin ? (p.Hin - iyf + s - 1) / s : 0, Wc = ixf < p.Win ? (p.Win - ixf + s - 1) / s : 0;
-  const int cy0 = (iyf + p.pad_eff - py) / s, cx0 = (ixf + p.pad_eff - px) / s;
-  const int nty = py < p.kh ? (p.kh - py + s - 1) / s : 0, ntx = px < p.kw ? (p.kw - px + s - 1) / s : 0;
-  const int ntaps = nty * ntx;
-  const int Mc = p.N * Hc * Wc;
+  const DgradClass cls = dgrad_class(p, blockIdx.y);
+  const int ntaps = cls.nty * cls.ntx;
   const int ntn = (p.Cin + BN - 1) / BN;
   const int bid = cat::xcd_remap(blockIdx.x, gridDim.x);
   const int m0 = (bid / ntn) * BM, n0 = (bid % ntn) * BN;
-  if (m0 >= Mc) return;
-  const int HcWc = Hc * Wc, taps = p.kh * p.kw;
+  if (m0 >= cls.Mc) return;
+  const int HcWc = cls.Hc * cls.Wc, taps = p.kh * p.kw;
   const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a), 0, 0x7fffffff, 0x00020000);
   const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(BT ? p.bt : p.b), 0, 0x7fffffff, 0x00020000);
   // A staging map as in conv_fwd32d_kernel; B: wave w, instruction i -> k-rows (w * 4 + i) * 2 + (lane >> 5), float4 column lane & 31
@@ -1091,13 +1103,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   for (int i = 0; i < 4; ++i) {
     const int row = (wave * 4 + i) * 8 + lrow;
     const int m = m0 + row;
-    rv[i] = m < Mc;
-    const int mm = rv[i] ? m : 0;
-    const int n = mm / HcWc, rem = mm - n * HcWc;
-    const int a = rem / Wc, b = rem - a * Wc;
-    cy[i] = cy0 + a;
-    cx[i] = cx0 + b;
-    abase[i] = (unsigned)n * (unsigned)(p.Ho * p.Wo) * (unsigned)p.ycs * 4u;
+    rv[i] = m < cls.Mc;
+    const Pixel cp = decode_pixel(rv[i] ? m : 0, HcWc, cls.Wc);
+    cy[i] = cls.cy0 + cp.y;
+    cx[i] = cls.cx0 + cp.x;
+    abase[i] = (unsigned)cp.n * (unsigned)(p.Ho * p.Wo) * (unsigned)p.ycs * 4u;
     aq[i] = (unsigned)(slot ^ ((row >> 1) & 7)) * 16u;
     if (BT) {
       const int cin = n0 + row;
@@ -1120,58 +1130,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   locate(0, 0);
   auto issue = [&](int buf) {
     const unsigned soA = (unsigned)co * 4u;
-    const unsigned tapi = (unsigned)((py + jy * s) * p.kw + px + jx * s);
+    const unsigned tapi = (unsigned)((cls.py + jy * cls.s) * p.kw + cls.px + jx * cls.s);
     const unsigned soB = BT ? (tapi * (unsigned)p.Cout + (unsigned)co) * 4u : ((unsigned)co * (unsigned)taps + tapi) * (unsigned)p.wcs * 4u;
-    float* dA = sA + buf * BM * 32 + wave * 4 * 256;
-    float* dB = sB + buf * 32 * BN + wave * 4 * 256;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_t)(dA + i * 256), 16, voffA[i], soA, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_t)(dB + i * 256), 16, voffB[i], soB, 0, 0);
+    dma_chunk(rA, rB, sA + buf * BM * 32, sB + buf * 32 * BN, wave, voffA, voffB, soA, soB);
     co += 32;
     if (co >= p.c4) {
       co = 0;
       ++tj;
-      if (++jx == ntx) {
-        jx = 0;
-        ++jy;
-      }
+      next_tap(jy, jx, cls.ntx);
       if (tj < ntaps) locate(jy, jx);
     }
   };
   const int lr = lane & 15, lq = lane >> 4;
   f4 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-  auto mma = [&](int buf) {
+  zero_acc(acc);
+  auto mma = [&](int buf) {   // filters first: transposed accumulators, see the epilogue
     const float* A = sA + buf * BM * 32;
     const float* B = sB + buf * 32 * BN;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      f4 fa[MT];
-      float fb[NT][4];
-#pragma unroll
-      for (int i = 0; i < MT; ++i) fa[i] = *reinterpret_cast<const f4*>(A + swz32(wm * MT * 16 + i * 16 + lr, lq + 4 * h));
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        if (BT) {
-          const f4 v = *reinterpret_cast<const f4*>(B + swz32(wn * NT * 16 + j * 16 + lr, lq + 4 * h));
-#pragma unroll
-          for (int t = 0; t < 4; ++t) fb[j][t] = v[t];
-        } else {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) fb[j][t] = B[(h * 16 + lq * 4 + t) * BN + ((wn * NT * 16 + j * 16 + lr) ^ (lq << 4))];
-        }
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[j][t], fa[i][t], acc[i][j], 0, 0, 0);   // D^T: see the epilogue
-    }
+    if (BT) mma32_kcontig_a_kcontig_b<true>(A, B, wm * MT * 16, wn * NT * 16, lane, acc);
+    else mma32_kcontig_a_ncontig_b<true, BN>(A, B, wm * MT * 16, wn * NT * 16, lane, acc);
   };
   const int nk = ntaps * (p.c4 >> 5);
   if (nk > 0) {
@@ -1187,34 +1164,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     mma((nk - 1) & 1);
   }
-  // transposed accumulators (filter fragment = the MFMA's first operand): lane (lr, lq) holds input channels j * 16 + lq * 4 + 0..3 of class
-  // pixel i * 16 + lr -- one pixel address and one float4 store per tile instead of four of each
+  // transposed accumulators (filter fragment = the MFMA's first operand): one class pixel per lane and tile row (store_pixel_t)
   const bool vec = (p.ocs & 3) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0;
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
     const int m = m0 + wm * MT * 16 + i * 16 + lr;
-    if (m >= Mc) continue;
-    const int n = m / HcWc, rem = m - n * HcWc;
-    const int a = rem / Wc, b = rem - a * Wc;
-    float* orow = p.out + (((int64_t)n * p.Hin + (iyf + a * s)) * p.Win + (ixf + b * s)) * p.ocs;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int c0 = n0 + wn * NT * 16 + j * 16 + lq * 4;
-      if (c0 >= p.cw) continue;
-      if (vec && c0 + 3 < p.Cin) {
-        f4 v = acc[i][j];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = cat::apply_act(v[e] + (p.bias ? p.bias[c0 + e] : 0.f), p.act, p.slope);
-        *reinterpret_cast<f4*>(orow + c0) = v;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int c = c0 + e;
-          if (c < p.Cin) orow[c] = cat::apply_act(acc[i][j][e] + (p.bias ? p.bias[c] : 0.f), p.act, p.slope);
-          else if (c < p.cw) orow[c] = 0.f;
-        }
-      }
-    }
+    if (m >= cls.Mc) continue;
+    store_pixel_t(p, p.out + dgrad_out_pixel(p, cls, m) * p.ocs, acc, i, n0 + wn * NT * 16 + lq * 4, p.Cin, vec);
   }
 }
 
@@ -1269,11 +1225,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(IgemmArgs p) {
   int pn[BI], poy[BI], pox[BI];
 #pragma unroll
   for (int i = 0; i < BI; ++i) {
-    const int m = min(mbeg + bpix[i], p.M - 1);
-    pn[i] = m / HoWo;
-    const int rem = m - pn[i] * HoWo;
-    poy[i] = rem / p.Wo;
-    pox[i] = rem - poy[i] * p.Wo;
+    const Pixel o = decode_pixel(min(mbeg + bpix[i], p.M - 1), HoWo, p.Wo);
+    pn[i] = o.n;
+    poy[i] = o.y;
+    pox[i] = o.x;
   }
   // NB: gload must be called with kc = 0, 1, 2, ... exactly once each, in order
   const float* pa[AI];
@@ -1321,10 +1276,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(IgemmArgs p) {
   };
 
   f4 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   const int lr = lane & 15, lq = lane >> 4;
   const int nk = mend > mbeg ? (mend - mbeg + 15) >> 4 : 0;
@@ -1369,15 +1321,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(IgemmArgs p) {
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) {
         const int co = c0 + wm * MT * 16 + i * 16 + lq * 4 + rg;
-        if (co >= p.Cout) continue;
-        if (p.direct) {
-          if (ci < p.cval) {   // cval = writable channels per tap (Cin, or the padded extent when the storage is padded)
-            float* dst = p.out + ((int64_t)co * taps + tap) * p.wcs + ci;
-            *dst = p.accumulate ? *dst + acc[i][j][rg] : acc[i][j][rg];
-          }
-        } else {
-          p.out[((int64_t)blockIdx.y * p.Cout + co) * p.K + k] = acc[i][j][rg];
-        }
+        if (co < p.Cout) store_dw(p, co, k, tap, ci, taps, acc[i][j][rg]);
       }
     }
   }
@@ -1391,11 +1335,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(IgemmArgs p) {
 // address arithmetic; both tiles are DMA-ed into LDS (see conv_fwd32d_kernel).  Chunks whose input row falls into the zero padding are
 // skipped.  Tiles are [32 pixels][128] with the 16-column groups XOR-ed by (pixel >> 2) & 3 (applied to the source column), read with
 // ds_read_b32 like conv_wgrad_kernel.  blockIdx.y = slice of output rows; partial sums go to ws[slice][co][K] (or straight to dw).
-template <int WMW>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_wgrad32d_kernel(IgemmArgs p, int rows_per, int cpr) {
   constexpr int MT = 4, NT = 4, WN = 2, BM = 128, BN = 128;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  typedef __attribute__((address_space(3))) void* lds_t;
   float* sA = smem;                   // dy tile   [2][32][128]
   float* sB = smem + 2 * 32 * BM;     // x  tile   [2][32][128]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1451,12 +1393,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int iy = oy * p.stride - p.pad + ky;
     const unsigned soA = (unsigned)((n * p.Ho + oy) * p.Wo + sg * 32) * (unsigned)p.ycs * 4u;
     const unsigned soB = (unsigned)((n * p.H + iy) * p.W + sg * 32 * p.stride) * (unsigned)p.xcs * 4u;      // "- pad" lives in rB's base
-    float* dA = sA + buf * 32 * BM + wave * 4 * 256;
-    float* dB = sB + buf * 32 * BN + wave * 4 * 256;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_t)(dA + i * 256), 16, voffA[i], soA, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_t)(dB + i * 256), 16, voffB[i], soB, 0, 0);
+    dma_chunk(rA, rB, sA + buf * 32 * BM, sB + buf * 32 * BN, wave, voffA, voffB, soA, soB);
     if (++sg == cpr) {
       sg = 0;
       ++rr;
@@ -1465,10 +1402,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   };
   const int lr = lane & 15, lq = lane >> 4;
   f4 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   auto mma = [&](int buf) {
     const float* A = sA + buf * 32 * BM;
     const float* B = sB + buf * 32 * BN;
@@ -1515,15 +1449,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) {
         const int co = c0 + wm * MT * 16 + i * 16 + lq * 4 + rg;
-        if (co >= p.Cout) continue;
-        if (p.direct) {
-          if (ci < p.cval) {
-            float* dst = p.out + ((int64_t)co * taps + tap) * p.wcs + ci;
-            *dst = p.accumulate ? *dst + acc[i][j][rg] : acc[i][j][rg];
-          }
-        } else {
-          p.out[((int64_t)blockIdx.y * p.Cout + co) * p.K + k] = acc[i][j][rg];
-        }
+        if (co < p.Cout) store_dw(p, co, k, tap, ci, taps, acc[i][j][rg]);
       }
     }
   }
@@ -1546,67 +1472,16 @@ __global__ __launch_bounds__(256) void weight_transpose_kernel(const float* __re
   }
 }
 
-// dw[co][tap][ci] (+)= sum_z ws[z][co][tap*c4 + ci].  Workgroup = 16 channel quads x 16 split lanes: every thread sums its slices' float4 in
-// increasing z (fixed order), the 16 lanes of a quad are then combined pairwise through LDS -- deterministic, and 16-byte loads with 16
-// slices in flight per output instead of 4-byte loads with 4.
-// wlim = channels written per tap (Cin for dense storage, the padded extent otherwise), wcs = storage stride per tap
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int nsplit,
-                                                           int Cout, int taps, int wlim, int wcs, int c4, int K, int accumulate) {
-  __shared__ f4 red[256];
-  const int cq = c4 >> 2;
-  const int64_t total = (int64_t)Cout * taps * cq;
-  const int64_t e = (int64_t)blockIdx.x * 16 + (threadIdx.x & 15);
-  const int zl = threadIdx.x >> 4;
-  f4 s = {0.f, 0.f, 0.f, 0.f};
-  int q = 0, tap = 0, co = 0;
-  if (e < total) {
-    q = (int)(e % cq);
-    const int64_t ct = e / cq;
-    tap = (int)(ct % taps);
-    co = (int)(ct / taps);
-    const float* src = ws + (int64_t)co * K + tap * c4 + q * 4;
-    const int64_t zs = (int64_t)Cout * K;
-    int z = zl;
-    for (; z + 48 < nsplit; z += 64) {
-      const f4 v0 = *reinterpret_cast<const f4*>(src + z * zs), v1 = *reinterpret_cast<const f4*>(src + (z + 16) * zs);
-      const f4 v2 = *reinterpret_cast<const f4*>(src + (z + 32) * zs), v3 = *reinterpret_cast<const f4*>(src + (z + 48) * zs);
-      s += v0;
-      s += v1;
-      s += v2;
-      s += v3;
-    }
-    for (; z < nsplit; z += 16) s += *reinterpret_cast<const f4*>(src + z * zs);
-  }
-  red[threadIdx.x] = s;
-  __syncthreads();
-#pragma unroll
-  for (int st = 8; st >= 1; st >>= 1) {
-    if (zl < st) red[threadIdx.x] += red[threadIdx.x + st * 16];
-    __syncthreads();
-  }
-  if (zl == 0 && e < total) {
-    const f4 r = red[threadIdx.x];
-    float* d = dw + ((int64_t)co * taps + tap) * wcs + q * 4;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      if (q * 4 + c < wlim) d[c] = accumulate ? d[c] + r[c] : r[c];
-  }
-}
-
-// The partial sums of SEVERAL weight gradients reduced by one launch (cat_conv2d_wgrad_batch: the narrow layers of a fused block -- seven
-// 5 - 8 us reduce launches per block were launch latency, not data).  Same arithmetic per item as wgrad_reduce_kernel (same lane / slice
-// order): blocks [start[i], start[i + 1]) serve item i.
 struct RedItem {
   const float* ws;
   float* dw;
   int nsplit, Cout, taps, wlim, wcs, c4, K, accumulate;
 };
-struct RedMany {
-  RedItem it[CAT_WGRAD_BATCH_MAX];
-  int start[CAT_WGRAD_BATCH_MAX + 1];
-  int n;
-};
 
+// dw[co][tap][ci] (+)= sum_z ws[z][co][tap*c4 + ci].  Workgroup = 16 channel quads x 16 split lanes: every thread sums its slices' float4 in
+// increasing z (fixed order), the 16 lanes of a quad are then combined pairwise through LDS -- deterministic, and 16-byte loads with 16
+// slices in flight per output instead of 4-byte loads with 4.
+// wlim = channels written per tap (Cin for dense storage, the padded extent otherwise), wcs = storage stride per tap
 __device__ __forceinline__ void wgrad_reduce_body(const RedItem& r, int64_t blk, f4* red) {
   const int cq = r.c4 >> 2;
   const int64_t total = (int64_t)r.Cout * r.taps * cq;
@@ -1648,6 +1523,21 @@ __device__ __forceinline__ void wgrad_reduce_body(const RedItem& r, int64_t blk,
   }
 }
 
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int nsplit,
+                                                           int Cout, int taps, int wlim, int wcs, int c4, int K, int accumulate) {
+  __shared__ f4 red[256];
+  wgrad_reduce_body(RedItem{ws, dw, nsplit, Cout, taps, wlim, wcs, c4, K, accumulate}, blockIdx.x, red);
+}
+
+// The partial sums of SEVERAL weight gradients reduced by one launch (cat_conv2d_wgrad_batch: the narrow layers of a fused block -- seven
+// 5 - 8 us reduce launches per block were launch latency, not data).  Same arithmetic per item as wgrad_reduce_kernel (same lane / slice
+// order): blocks [start[i], start[i + 1]) serve item i.
+struct RedMany {
+  RedItem it[CAT_WGRAD_BATCH_MAX];
+  int start[CAT_WGRAD_BATCH_MAX + 1];
+  int n;
+};
+
 __global__ __launch_bounds__(256) void wgrad_reduce_many_kernel(const RedMany m) {
   __shared__ f4 red[256];
   int i = 0;
@@ -1658,49 +1548,50 @@ __global__ __launch_bounds__(256) void wgrad_reduce_many_kernel(const RedMany m)
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// N = 130 .. 192 (the frozen teacher's 176-wide fused GEMM, SPADE's 170-wide heads) fills two 96-wide tiles better than two 128-wide
-// ones (8 % instead of 31 % padding at 176); kept switched off (`on`): the 176-wide layer is the frozen teacher's merged 1 x 1, served by the
-// direct-to-LDS 128 x 128 tile ahead of this dispatch.
-static bool prefer_96_wide(int n) {
-  constexpr int on = 0;
-  return on && n > 96 && (int64_t)cat::cdiv(n, 96) * 96 * 10 <= (int64_t)cat::cdiv(n, 128) * 128 * 9;
-}
-
-#define DISPATCH_TILE_N(n, LAUNCH)   \
-  do {                               \
-    if ((n) <= 16) {                 \
-      LAUNCH(4, 1, 4, 1);            \
-    } else if ((n) <= 32) {          \
-      LAUNCH(4, 2, 4, 1);            \
-    } else if ((n) <= 48) {          \
-      LAUNCH(2, 3, 4, 1);            \
-    } else if ((n) <= 64) {          \
-      LAUNCH(2, 4, 4, 1);            \
-    } else if ((n) <= 96 || prefer_96_wide(n)) { \
-      LAUNCH(2, 6, 4, 1);            \
-    } else {                         \
-      LAUNCH(4, 4, 2, 2);            \
-    }                                \
-  } while (0)
-
-// Few output pixels (e.g. the student's 64x64 trunk at batch 16 = 256 tiles of 256 rows): halve the M tile so that every CU
+// The tiles of the generic forward / dgrad kernels by GEMM width n (Cout / Cin): ROW(n <=, MT, MT when M is small, NT, WM, WN).
+// ONE table for the dispatch, default_bm and split_plan, so a tile rule cannot change in one of them only.
+// Small M = few output pixels (e.g. the student's 64x64 trunk at batch 16 = 256 tiles of 256 rows): halve the M tile so that every CU
 // holds 2+ workgroups and the per-chunk load / LDS / barrier latencies of one overlap the MFMA stream of another.
-#define DISPATCH_TILE_N_SMALLM(n, LAUNCH) \
-  do {                               \
-    if ((n) <= 16) {                 \
-      LAUNCH(2, 1, 4, 1);            \
-    } else if ((n) <= 32) {          \
-      LAUNCH(2, 2, 4, 1);            \
-    } else if ((n) <= 48) {          \
-      LAUNCH(1, 3, 4, 1);            \
-    } else if ((n) <= 64) {          \
-      LAUNCH(1, 4, 4, 1);            \
-    } else if ((n) <= 96) {          \
-      LAUNCH(1, 6, 4, 1);            \
-    } else {                         \
-      LAUNCH(4, 4, 2, 2);            \
-    }                                \
-  } while (0)
+// (N = 130 .. 192 -- the frozen teacher's 176-wide fused GEMM, SPADE's 170-wide heads -- would fill two 96-wide tiles better than two
+// 128-wide ones, 8 % instead of 31 % padding at 176; not taken: the 176-wide layer is the frozen teacher's merged 1 x 1, served by the
+// direct-to-LDS 128 x 128 tile ahead of this dispatch.)
+#define CONV_TILES(ROW, ...)         \
+  ROW(16, 4, 2, 1, 4, 1, __VA_ARGS__) \
+  ROW(32, 4, 2, 2, 4, 1, __VA_ARGS__) \
+  ROW(48, 2, 1, 3, 4, 1, __VA_ARGS__) \
+  ROW(64, 2, 1, 4, 4, 1, __VA_ARGS__) \
+  ROW(96, 2, 1, 6, 4, 1, __VA_ARGS__) \
+  ROW(INT_MAX, 4, 4, 4, 2, 2, __VA_ARGS__)
+// ... and of conv_wgrad_kernel by Cout: ROW(Cout <=, MT, NT, WM, WN), for the launch and wgrad_plan
+#define WGRAD_TILES(ROW, ...)         \
+  ROW(16, 1, 4, 1, 4, __VA_ARGS__)    \
+  ROW(32, 2, 4, 1, 4, __VA_ARGS__)    \
+  ROW(48, 3, 4, 1, 4, __VA_ARGS__)    \
+  ROW(64, 4, 4, 1, 4, __VA_ARGS__)    \
+  ROW(96, 6, 2, 1, 4, __VA_ARGS__)    \
+  ROW(INT_MAX, 4, 4, 2, 2, __VA_ARGS__)
+
+#define CONV_TILE_LAUNCH(NMAX, MT, MTS, NT, WM, WN, n, smallm, LAUNCH) \
+  if ((n) <= NMAX) {                                                   \
+    if (smallm) LAUNCH(MTS, NT, WM, WN) else LAUNCH(MT, NT, WM, WN)     \
+  } else
+#define DISPATCH_TILE_N(n, smallm, LAUNCH) CONV_TILES(CONV_TILE_LAUNCH, n, smallm, LAUNCH) {}
+
+struct TileShape { int bm, bn; };
+static TileShape conv_tile(int n, bool smallm) {
+#define CONV_TILE_SHAPE(NMAX, MT, MTS, NT, WM, WN, ...) \
+  if (n <= NMAX) return TileShape{WM * (smallm ? MTS : MT) * 16, WN * NT * 16};
+  CONV_TILES(CONV_TILE_SHAPE, )
+#undef CONV_TILE_SHAPE
+  return TileShape{};
+}
+static TileShape wgrad_tile(int cout) {
+#define WGRAD_TILE_SHAPE(NMAX, MT, NT, WM, WN, ...) \
+  if (cout <= NMAX) return TileShape{WM * MT * 16, WN * NT * 16};
+  WGRAD_TILES(WGRAD_TILE_SHAPE, )
+#undef WGRAD_TILE_SHAPE
+  return TileShape{};
+}
 
 // out[pix][c] = act(sum_z part[z][pix][c] + bias[c]) for c < C; zeros for C <= c < cw
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias,
@@ -1723,10 +1614,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
-static int default_bm(int n) { return n <= 32 ? 256 : 128; }
+static int default_bm(int n) { return conv_tile(n, false).bm; }
 static bool use_small_m(int M, int n) {
-  constexpr int mode = 1;
-  if (!mode || n > 32) return false;   // measured: helps the 16/32-wide tiles (256-row default), not the 48..96-wide ones
+  if (n > 32) return false;   // measured: helps the 16/32-wide tiles (256-row default), not the 48..96-wide ones
   return cdiv(M, default_bm(n)) < 768;
 }
 
@@ -1735,12 +1625,9 @@ static bool use_small_m(int M, int n) {
 struct SplitPlan { int ksplit, kchunks; };
 static SplitPlan split_plan(int M, int n, int nk) {
   SplitPlan p{1, nk};
-  constexpr int off = 0;
-  const bool smallm = use_small_m(M, n);
-  const int bn = n <= 16 ? 16 : n <= 32 ? 32 : n <= 48 ? 48 : n <= 64 ? 64 : n <= 96 ? 96 : 128;
-  const int bm = n > 96 ? 128 : (smallm ? (n <= 32 ? 128 : 64) : (n <= 32 ? 256 : 128));
-  const int tiles = cdiv(M, bm) * cdiv(n, bn);
-  if (off || tiles >= 128 || nk < 16) return p;
+  const TileShape t = conv_tile(n, use_small_m(M, n));
+  const int tiles = cdiv(M, t.bm) * cdiv(n, t.bn);
+  if (tiles >= 128 || nk < 16) return p;
   int ks = cdiv(512, tiles);
   if (ks > nk / 4) ks = nk / 4;
   if (ks < 2) return p;
@@ -1750,10 +1637,14 @@ static SplitPlan split_plan(int M, int n, int nk) {
   return p;
 }
 
-static int reduce_grid(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+static void launch_splitk_reduce(const float* part, const float* bias, float* out, int64_t P, int C, int cw, int cs, int ksplit, int act,
+                                 float slope, hipStream_t s) {
+  const int64_t b = (P * ((cw + 3) / 4) + 255) / 256;
+  splitk_reduce_kernel<<<(int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)), 256, 0, s>>>(part, bias, out, P, C, cw, cs, ksplit, act, slope);
 }
+
+// the direct-to-LDS kernels address a tensor with 32-bit byte offsets
+static bool fits_2gb(int64_t floats) { return floats * 4 < (int64_t)2147483647; }
 
 int fill_common(IgemmArgs& a, const cat_conv_t* g, int pad_w = -1) {
   const int padw = pad_w >= 0 ? pad_w : g->pad;
@@ -1785,11 +1676,9 @@ int walk_extent(int c4) {
 struct WgradPlan { int nsplit, mchunk, tiles; };
 WgradPlan wgrad_plan(const cat_conv_t* g) {
   const int Cout = g->Cout, K = g->kh * g->kw * ((g->Cin + 3) & ~3);
-  int BM, BN;
-  if (Cout <= 16) { BM = 16; BN = 256; } else if (Cout <= 32) { BM = 32; BN = 256; } else if (Cout <= 48) { BM = 48; BN = 256; }
-  else if (Cout <= 64) { BM = 64; BN = 256; } else if (Cout <= 96) { BM = 96; BN = 128; } else { BM = 128; BN = 128; }
+  const TileShape t = wgrad_tile(Cout);
   WgradPlan pl;
-  pl.tiles = cdiv(Cout, BM) * cdiv(K, BN);
+  pl.tiles = cdiv(Cout, t.bm) * cdiv(K, t.bn);
   const int M = g->N * g->Ho * g->Wo;
   const char* tenv = getenv("CAT_WGRAD_BLOCKS");   // workgroups the pixel split aims for (tuning knob, read per call)
   const int target = tenv ? atoi(tenv) : 1024;
@@ -1807,14 +1696,22 @@ WgradPlan wgrad_plan(const cat_conv_t* g) {
   return pl;
 }
 
+// CAT_SCHED scheduling experiments of the 128 x 128 tile: instantiated by the diagnostic build only
+template <bool DIAG>
+void launch_fwd_sched(int sched, int grid, const IgemmArgs& a, hipStream_t s) {
+  if constexpr (DIAG) {
+    if (sched == 1) conv_fwd_kernel<4, 4, 2, 2, true, 1><<<grid, 256, 0, s>>>(a);
+    else conv_fwd_kernel<4, 4, 2, 2, true, 2><<<grid, 256, 0, s>>>(a);
+  }
+}
+
 }  // namespace
 
 extern "C" {
 
 static bool fwd_bk32_ok(const IgemmArgs& a) {
-  constexpr int no_bk32 = 0;
   static const bool dbg_on = cat::kDiag && getenv("CAT_DBG");
-  return !no_bk32 && a.wvec && (a.c4 & 15) == 0 && !dbg_on;
+  return a.wvec && (a.c4 & 15) == 0 && !dbg_on;
 }
 
 static int fwd_setup(IgemmArgs& a, const cat_conv_t* g, int pad_w = -1) {
@@ -1870,8 +1767,7 @@ static int conv_fwd_impl(const cat_conv_t* g, const float* x, const float* w, co
     const int ks = ws ? cat::smallco_fwd_ksplit(g) : 1;
     if (int e = cat::smallco_fwd(g, x, w, bias, y, (float*)ws, ks, s)) return e;
     if (ks > 1) {
-      splitk_reduce_kernel<<<reduce_grid((int64_t)a.M * ((a.cw + 3) / 4)), 256, 0, s>>>((const float*)ws, bias, y, a.M, a.Cout, a.cw, a.ycs, ks, a.act,
-                                                                                         a.slope);
+      launch_splitk_reduce((const float*)ws, bias, y, a.M, a.Cout, a.cw, a.ycs, ks, a.act, a.slope, s);
       return cat::check_launch("conv2d_fwd_smallco_reduce");
     }
     return 0;
@@ -1892,8 +1788,7 @@ static int conv_fwd_impl(const cat_conv_t* g, const float* x, const float* w, co
     cat::ProfScope prof("conv_fwd_" #MT "x" #NT "x" #WM "x" #WN, prof_flops, 0.0, stream); \
     const int grid = cdiv(a.M, WM * MT * 16) * cdiv(a.Cout, WN * NT * 16);                 \
     if (!a.wvec) conv_fwd_kernel<MT, NT, WM, WN, false, 0><<<grid, 256, 0, s>>>(a);         \
-    else if (WN == 2 && sched == 1) conv_fwd_kernel<MT, NT, WM, WN, true, (WN == 2 ? 1 : 0)><<<grid, 256, 0, s>>>(a); \
-    else if (WN == 2 && sched == 2) conv_fwd_kernel<MT, NT, WM, WN, true, (WN == 2 ? 2 : 0)><<<grid, 256, 0, s>>>(a); \
+    else if (WN == 2 && sched) launch_fwd_sched<cat::kDiag>(sched, grid, a, s);             \
     else conv_fwd_kernel<MT, NT, WM, WN, true, 0><<<grid, 256, lds_pad, s>>>(a);            \
   }
   // BK = 32 path: per-tap K extent a multiple of 32 (allowing <= 12.5 % zero padding) and float4-readable filter rows
@@ -1914,30 +1809,23 @@ static int conv_fwd_impl(const cat_conv_t* g, const float* x, const float* w, co
     static cat::LdsOptIn optin;                                                                       \
     cat::lds_optin(optin, (const void*)conv_fwd32_kernel<MT, NT, WM, WN>, (int)lds);                  \
     conv_fwd32_kernel<MT, NT, WM, WN><<<grid, 256, lds, s>>>(a);                                       \
-    if (a.ksplit > 1)                                                                                 \
-      splitk_reduce_kernel<<<reduce_grid((int64_t)a.M * ((a.cw + 3) / 4)), 256, 0, s>>>(a.part, a.bias, a.out, a.M, a.Cout, a.cw, a.ycs,   \
-                                                                                         a.ksplit, a.act, a.slope);                    \
+    if (a.ksplit > 1) launch_splitk_reduce(a.part, a.bias, a.out, a.M, a.Cout, a.cw, a.ycs, a.ksplit, a.act, a.slope, s);   \
   }
   // direct-to-LDS variant of the 128 x 128 tile: Cin % 32 == 0 (a chunk never straddles taps), no K split, 32-bit byte offsets
   static const int fwd_direct = getenv("CAT_FWD_DIRECT") ? atoi(getenv("CAT_FWD_DIRECT")) : 1;
   if (fwd_direct && bk32 && a.ksplit == 1 && a.Cout > 96 && (g->Cin & 31) == 0 && a.c4 == g->Cin && a.wcs >= g->Cin &&
-      (int64_t)g->N * g->H * g->W * g->xcs * 4 < (int64_t)2147483647 && (int64_t)g->Cout * g->kh * g->kw * a.wcs * 4 < (int64_t)2147483647) {
+      fits_2gb((int64_t)g->N * g->H * g->W * g->xcs) && fits_2gb((int64_t)g->Cout * g->kh * g->kw * a.wcs)) {
     cat::ProfScope prof("conv_fwd32d_4x4x2x2", prof_flops, 0.0, stream);
     const int grid = cdiv(a.M, 128) * cdiv(a.Cout, 128);
     const size_t lds = (size_t)2 * (128 + 128) * 32 * sizeof(float);
     static cat::LdsOptIn optin;
-    cat::lds_optin(optin, (const void*)conv_fwd32d_kernel<2>, (int)lds);
-    conv_fwd32d_kernel<2><<<grid, 256, lds, s>>>(a);
+    cat::lds_optin(optin, (const void*)conv_fwd32d_kernel, (int)lds);
+    conv_fwd32d_kernel<<<grid, 256, lds, s>>>(a);
     return cat::check_launch("conv2d_fwd");
   }
   const bool smallm = use_small_m(a.M, a.Cout);
-  if (bk32) {
-    if (smallm) DISPATCH_TILE_N_SMALLM(a.Cout, LAUNCH32);
-    else DISPATCH_TILE_N(a.Cout, LAUNCH32);
-  } else {
-    if (smallm) DISPATCH_TILE_N_SMALLM(a.Cout, LAUNCH);
-    else DISPATCH_TILE_N(a.Cout, LAUNCH);
-  }
+  if (bk32) DISPATCH_TILE_N(a.Cout, smallm, LAUNCH32)
+  else DISPATCH_TILE_N(a.Cout, smallm, LAUNCH)
 #undef LAUNCH32
   if (a.dbg) {
     long long h[8];
@@ -1987,7 +1875,7 @@ static bool dgrad32d_ok(const cat_conv_t* g) {
   static const int on = getenv("CAT_DGRAD_DIRECT") ? atoi(getenv("CAT_DGRAD_DIRECT")) : 1;
   const int wcs = g->wcs > 0 ? g->wcs : g->Cin;
   return on && g->Cin > 96 && (wcs & 3) == 0 && g->Cout % 32 == 0 && g->Cin % 4 == 0 &&
-         (int64_t)g->N * g->Ho * g->Wo * g->ycs * 4 < (int64_t)2147483647 && (int64_t)g->Cout * g->kh * g->kw * wcs * 4 < (int64_t)2147483647;
+         fits_2gb((int64_t)g->N * g->Ho * g->Wo * g->ycs) && fits_2gb((int64_t)g->Cout * g->kh * g->kw * wcs);
 }
 
 int cat_conv2d_dgrad_t_applicable(const cat_conv_t* g) {
@@ -2037,19 +1925,15 @@ static int conv_dgrad_impl(const cat_conv_t* g, const float* dy, const float* w,
                         stream);                                                           \
     dim3 grid(cdiv(mmax, WM * MT * 16) * cdiv(a.Cin, WN * NT * 16), st * st, a.ksplit);    \
     conv_dgrad_kernel<MT, NT, WM, WN><<<grid, 256, 0, s>>>(a);                              \
-    if (a.ksplit > 1) {                                                                    \
-      const int64_t P = (int64_t)g->N * a.Hin * a.Win;                                     \
-      splitk_reduce_kernel<<<reduce_grid(P * ((a.cw + 3) / 4)), 256, 0, s>>>(a.part, a.bias, a.out, P, a.Cin, a.cw, a.ocs, a.ksplit, a.act,  \
-                                                                            a.slope);      \
-    }                                                                                      \
+    if (a.ksplit > 1)                                                                      \
+      launch_splitk_reduce(a.part, a.bias, a.out, (int64_t)g->N * a.Hin * a.Win, a.Cin, a.cw, a.ocs, a.ksplit, a.act, a.slope, s); \
   }
   if (a.ksplit == 1 && !bias && a.act == CAT_ACT_NONE && cat::smallci_dgrad_applicable(g)) {
     cat::ProfScope prof("conv_dgrad_smallci", prof_flops, 0.0, stream);
     return cat::smallci_dgrad(g, dy, w, dx, dxcs, a.cw, s);
   }
   // BK = 32 variant of the 128 x 128 tile (the discriminator's and the teacher's wide layers)
-  constexpr int bk32 = 1;
-  if (bk32 && a.ksplit == 1 && dgrad32d_ok(g) && a.c4 == g->Cout) {
+  if (a.ksplit == 1 && dgrad32d_ok(g) && a.c4 == g->Cout) {
     cat::ProfScope prof(wt ? "conv_dgrad32dt_4x4x2x2" : "conv_dgrad32d_4x4x2x2", prof_flops, 0.0, stream);
     const dim3 grid(cdiv(mmax, 128) * cdiv(a.Cin, 128), st * st);
     const size_t lds = (size_t)2 * (128 + 128) * 32 * sizeof(float);
@@ -2060,7 +1944,7 @@ static int conv_dgrad_impl(const cat_conv_t* g, const float* dy, const float* w,
     else conv_dgrad32d_kernel<false><<<grid, 256, lds, s>>>(a);
     return cat::check_launch("conv2d_dgrad");
   }
-  if (bk32 && a.ksplit == 1 && a.Cin > 96 && a.wvec && g->Cout % 16 == 0 && g->Cin % 4 == 0) {
+  if (a.ksplit == 1 && a.Cin > 96 && a.wvec && g->Cout % 16 == 0 && g->Cin % 4 == 0) {
     cat::ProfScope prof("conv_dgrad32_4x4x2x2", prof_flops, 0.0, stream);
     const dim3 grid(cdiv(mmax, 128) * cdiv(a.Cin, 128), st * st);
     const size_t lds = (size_t)2 * (128 + 128) * 32 * sizeof(float);
@@ -2069,8 +1953,7 @@ static int conv_dgrad_impl(const cat_conv_t* g, const float* dy, const float* w,
     conv_dgrad32_kernel<4, 4, 2, 2><<<grid, 256, lds, s>>>(a);
     return cat::check_launch("conv2d_dgrad");
   }
-  if (use_small_m(mmax, a.Cin)) DISPATCH_TILE_N_SMALLM(a.Cin, LAUNCH);
-  else DISPATCH_TILE_N(a.Cin, LAUNCH);
+  DISPATCH_TILE_N(a.Cin, use_small_m(mmax, a.Cin), LAUNCH)
 #undef LAUNCH
   return cat::check_launch("conv2d_dgrad");
 }
@@ -2080,10 +1963,9 @@ static int conv_dgrad_impl(const cat_conv_t* g, const float* dy, const float* w,
 static int wgrad32d_nsplit(const cat_conv_t* g, int* rows_per) {
   static const int on = getenv("CAT_WGRAD_DIRECT") ? atoi(getenv("CAT_WGRAD_DIRECT")) : 1;
   const int wcs = g->wcs > 0 ? g->wcs : g->Cin;
-  constexpr int ragged = 1;   // output rows that end in a partial 32-pixel segment
-  if (!on || g->Cout <= 96 || (g->Cin & 127) || g->pad_mode != CAT_PAD_ZERO || (!ragged && g->Wo > 32 && (g->Wo & 31)) || cat::smallco_applicable(g) ||
-      (int64_t)g->N * g->H * g->W * g->xcs * 4 >= (int64_t)2147483647 || (int64_t)g->N * g->Ho * g->Wo * g->ycs * 4 >= (int64_t)2147483647 ||
-      wcs < g->Cin)
+  // (output rows that end in a partial 32-pixel segment are served: the segment's tail lanes are parked out of range)
+  if (!on || g->Cout <= 96 || (g->Cin & 127) || g->pad_mode != CAT_PAD_ZERO || cat::smallco_applicable(g) ||
+      !fits_2gb((int64_t)g->N * g->H * g->W * g->xcs) || !fits_2gb((int64_t)g->N * g->Ho * g->Wo * g->ycs) || wcs < g->Cin)
     return 0;
   const int tiles = cdiv(g->Cout, 128) * (g->kh * g->kw * g->Cin / 128);
   const int R = g->N * g->Ho;
@@ -2166,8 +2048,8 @@ static int wgrad_impl(const cat_conv_t* g, const float* x, const float* dy, floa
       const dim3 grid(cdiv(a.Cout, 128) * (a.K / 128), nsd);
       const size_t lds = (size_t)2 * 2 * 32 * 128 * sizeof(float);
       static cat::LdsOptIn optin_w;
-      cat::lds_optin(optin_w, (const void*)conv_wgrad32d_kernel<2>, (int)lds);
-      conv_wgrad32d_kernel<2><<<grid, 256, lds, s>>>(a, rows_per, cdiv(g->Wo, 32));
+      cat::lds_optin(optin_w, (const void*)conv_wgrad32d_kernel, (int)lds);
+      conv_wgrad32d_kernel<<<grid, 256, lds, s>>>(a, rows_per, cdiv(g->Wo, 32));
     }
     if (int e = cat::check_launch("conv2d_wgrad")) return e;
     if (!a.direct) {
@@ -2182,12 +2064,9 @@ static int wgrad_impl(const cat_conv_t* g, const float* x, const float* dy, floa
     dim3 grid(cdiv(a.Cout, WM * MT * 16) * cdiv(a.K, WN * NT * 16), pl.nsplit);                        \
     conv_wgrad_kernel<MT, NT, WM, WN><<<grid, 256, 0, s>>>(a);                                          \
   }
-  if (a.Cout <= 16) LAUNCH(1, 4, 1, 4)
-  else if (a.Cout <= 32) LAUNCH(2, 4, 1, 4)
-  else if (a.Cout <= 48) LAUNCH(3, 4, 1, 4)
-  else if (a.Cout <= 64) LAUNCH(4, 4, 1, 4)
-  else if (a.Cout <= 96) LAUNCH(6, 2, 1, 4)
-  else LAUNCH(4, 4, 2, 2)
+#define WGRAD_TILE_LAUNCH(NMAX, MT, NT, WM, WN, ...) if (a.Cout <= NMAX) LAUNCH(MT, NT, WM, WN) else
+  WGRAD_TILES(WGRAD_TILE_LAUNCH, ) {}
+#undef WGRAD_TILE_LAUNCH
 #undef LAUNCH
   if (int e = cat::check_launch("conv2d_wgrad")) return e;
   if (!a.direct) {
