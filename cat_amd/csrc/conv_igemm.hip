@@ -1643,6 +1643,27 @@ static void launch_splitk_reduce(const float* part, const float* bias, float* ou
   splitk_reduce_kernel<<<(int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)), 256, 0, s>>>(part, bias, out, P, C, cw, cs, ksplit, act, slope);
 }
 
+// The tile kernels zero the lanes [C, cw) that fall inside their own column tiles, which always covers [C, round_up(C, 4)) -- every in-tree
+// caller's cw.  A wider cw (the C-ABI allows any cw <= the pixel stride) can reach past the last tile: those quads are zeroed here.
+__global__ __launch_bounds__(256) void zero_lanes_kernel(float* __restrict__ out, int64_t P, int cs, int c_lo, int cw) {
+  const int nq = (cw - c_lo + 3) >> 2;
+  const int64_t total = P * nq;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c = c_lo + (int)(i % nq) * 4;
+    float* o = out + (i / nq) * cs;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (c + e < cw) o[c + e] = 0.f;
+  }
+}
+
+static void zero_lanes_past_c4(float* out, int64_t P, int C, int cw, int cs, hipStream_t s) {
+  const int c4 = (C + 3) & ~3;
+  if (cw <= c4) return;
+  const int64_t b = (P * ((cw - c4 + 3) / 4) + 255) / 256;
+  zero_lanes_kernel<<<(int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)), 256, 0, s>>>(out, P, cs, c4, cw);
+}
+
 // the direct-to-LDS kernels address a tensor with 32-bit byte offsets
 static bool fits_2gb(int64_t floats) { return floats * 4 < (int64_t)2147483647; }
 
@@ -1762,6 +1783,7 @@ static int conv_fwd_impl(const cat_conv_t* g, const float* x, const float* w, co
   a.cw = g->ycw > g->Cout ? g->ycw : g->Cout;
   CAT_REQUIRE(a.cw <= g->ycs, "conv fwd: ycw > ycs");
   hipStream_t s = (hipStream_t)stream;
+  zero_lanes_past_c4(y, a.M, a.Cout, a.cw, a.ycs, s);
   if (!rect && cat::smallco_applicable(g)) {
     cat::ProfScope prof("conv_fwd_smallco", 2.0 * (double)g->N * g->Ho * g->Wo * g->Cout * g->kh * g->kw * g->Cin, 0.0, stream);
     const int ks = ws ? cat::smallco_fwd_ksplit(g) : 1;
@@ -1911,6 +1933,7 @@ static int conv_dgrad_impl(const cat_conv_t* g, const float* dy, const float* w,
   const int st = g->stride;
   const int mmax = g->N * cdiv(a.Hin, st) * cdiv(a.Win, st);
   hipStream_t s = (hipStream_t)stream;
+  zero_lanes_past_c4(dx, (int64_t)g->N * a.Hin * a.Win, a.Cin, a.cw, a.ocs, s);
   const double prof_flops = 2.0 * (double)g->N * g->Ho * g->Wo * g->Cout * g->kh * g->kw * g->Cin;
   a.ksplit = 1;
   if (ws) {
