@@ -1,0 +1,1356 @@
+"""The kernels of the fused units (cat_amd/fused_block.py, cat_amd/fused_spade.py; csrc/conv_pk.hip and csrc/block_norm.hip) one by one through
+the C ABI against float64 ATen on the host: every buffer a block-level test never reads (the stage-1 pre-norm buffer, the tile statistics, the
+scale / shift rows, the depthwise filter-gradient partials) and every instantiation a pruned student's ragged widths can select.
+
+A (host): the CAT_S1(...) rows of conv_pk.hip, the tstage1_kernel symbols of tests/golden/codegen_conv_pk.json and the case tables below must
+          agree (a new row without a case fails without a GPU); for every case of B-F the float64 reference and the same computation in float32
+          ATen must agree to TOL / 10, so a correct fp32 kernel has ten-fold room under the bar.
+B (GPU):  cat_tstage1_fwd, the 12 instantiations cat_tstage1_supported admits: slices, zero columns, sentinels, per-tile sum / M2, then
+          cat_tnorm_finalize over that table (batch and instance statistics, running statistics).
+C (GPU):  cat_tstage1_dgrad, all 16 instantiations, three output buffers with their own strides.
+D (GPU):  cat_tnorm_finalize / cat_tnorm_finalize2 / cat_tnorm_sums + cat_tnorm_finalize_sums on synthetic tables chosen by the kernel's own
+          thresholds (one wave per channel up to 1024 tiles, one workgroup above, the tail loop above 4096, whole-multiple planes).
+E (GPU):  cat_dwm_fwd and cat_dwm_bwd on the edges of their quad counts, on planes smaller than a tile, with the reflect fold.
+F (GPU):  every tconv_kernel<NT, TW> instantiation, cat_affine_res_fwd, cat_reflect_pad_bwd2, cat_prep_run, host-side argument refusals.
+
+Every bar is TOL = 1e-4 with rel() of test_kernels_gpu.py, exact equality for zero and sentinel lanes, or 1e-6 for the reflect fold (sums of
+at most ten terms).  Workspaces and fresh-write destinations start as NaN, everything a kernel must not touch as the sentinel 7.0."""
+import ctypes as C
+import functools
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import detfill
+from test_kernels_gpu import TOL, _families, rel
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PK_SRC = os.path.join(ROOT, 'cat_amd', 'csrc', 'conv_pk.hip')
+PK_GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'codegen_conv_pk.json')
+SENTINEL = 7.0
+NAN = float('nan')
+EPS, MOM = 1e-5, 0.1
+ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_RELU6 = 0, 1, 2, 3, 4
+FWD, DGRAD = 0, 1
+MAXREL = {}      # section -> largest distance from the float64 reference seen in this process (printed by every case)
+
+
+def cs4(c):
+    return (c + 3) // 4 * 4
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def _act(v, act, slope=0.2):
+    return {ACT_NONE: v, ACT_RELU: F.relu(v), ACT_LRELU: F.leaky_relu(v, slope), ACT_TANH: torch.tanh(v), ACT_RELU6: torch.clamp(v, 0.0, 6.0)}[act]
+
+
+def _pad(v, p, reflect):
+    return v if p == 0 else F.pad(v, (p,) * 4, mode='reflect' if reflect else 'constant')
+
+
+def _cmp(section, what, got, want, bar=TOL):
+    """every tensor of the reference dict `want` against the same key of `got`, rel() < bar"""
+    bad = []      # every figure is printed before the first one fails the case
+    for key in sorted(want):
+        assert tuple(got[key].shape) == tuple(want[key].shape), (what, key, tuple(got[key].shape), tuple(want[key].shape))
+        assert bool(torch.isfinite(got[key].double()).all()), (what, key)
+        d = rel(got[key], want[key])
+        MAXREL[section] = max(MAXREL.get(section, 0.0), d)
+        print('%s %s %s rel %.3g' % (section, what, key, d))
+        if not d < bar:
+            bad.append((key, d))
+    print('%s largest rel so far %.3g' % (section, MAXREL.get(section, 0.0)))
+    assert not bad, (section, what, bad)
+
+
+def _host(section, what, ref):
+    """reachability of the bar: the float32 ATen twin of the reference within TOL / 10 of the float64 one"""
+    r64, r32 = ref(torch.float64), ref(torch.float32)
+    assert sorted(r64) == sorted(r32)
+    for key in sorted(r64):
+        d = rel(r32[key], r64[key])
+        print('host %s %s %s fp32-vs-fp64 rel %.3g' % (section, what, key, d))
+        assert d <= TOL / 10, (section, what, key, d)
+
+
+def _tile_stats(y, th=8, tw=16):
+    """per-tile sum and M2 (squared deviations from the TILE mean, true pixel count of ragged tiles) of y [N, C, H, W], in y's dtype:
+    -> sum, M2 [N * tiles][C], pixels per tile [tiles]"""
+    n, c, h, w = y.shape
+    ty, tx = cdiv(h, th), cdiv(w, tw)
+    yp = F.pad(y, (0, tx * tw - w, 0, ty * th - h)).view(n, c, ty, th, tx, tw)
+    mk = F.pad(torch.ones(h, w, dtype=y.dtype), (0, tx * tw - w, 0, ty * th - h)).view(ty, th, tx, tw)
+    cnt = mk.sum((1, 3))
+    s = yp.sum((3, 5))
+    d = (yp - (s / cnt)[:, :, :, None, :, None]) * mk
+    m2 = (d * d).sum((3, 5))
+    flat = lambda t: t.permute(0, 2, 3, 1).reshape(n * ty * tx, c)
+    return flat(s), flat(m2), cnt.reshape(-1)
+
+
+def _norm_ref(v, inst, gamma, beta, rm0=None, rv0=None):
+    """train-mode norm statistics of v [N, C, ...] in v's dtype: scale / shift / mean / rstd [G][C] (+ the running statistics updated once)"""
+    dt = v.dtype
+    red = tuple(range(2, v.dim())) if inst else (0,) + tuple(range(2, v.dim()))
+    mean = v.mean(red, keepdim=True)
+    var = ((v - mean) ** 2).mean(red)
+    mean = mean.reshape(var.shape)
+    if not inst:
+        mean, var = mean[None], var[None]
+    rstd = (var + EPS) ** -0.5
+    scale = gamma.to(dt) * rstd
+    out = {'scale': scale, 'shift': beta.to(dt) - mean * scale, 'mean': mean, 'rstd': rstd}
+    if rm0 is not None:
+        cnt = v.numel() // v.shape[1]
+        out['rm'] = (1 - MOM) * rm0.to(dt) + MOM * mean[0]
+        out['rv'] = (1 - MOM) * rv0.to(dt) + MOM * var[0] * cnt / (cnt - 1)
+    return out
+
+
+# ================================================================================================ case tables
+def s1_supported(w5, w3, w1):
+    """mirror of cat_tstage1_supported (csrc/conv_pk.hip)"""
+    a, b, c = cdiv(w5, 16), cdiv(w3, 16), cdiv(w1, 16)
+    return w5 > 0 and w3 > 0 and w1 > 0 and a <= 2 and b <= 2 and 2 <= c <= 4
+
+
+def s1_dgrad_supported(w5, w3, w1):
+    """mirror of cat_tstage1_dgrad_supported"""
+    a, b, c = cdiv(w5, 16), cdiv(w3, 16), cdiv(w1, 16)
+    return w5 > 0 and w3 > 0 and w1 > 0 and a <= 2 and b <= 2 and c <= 4
+
+
+def _s1_widths(w5, w3, w1c):
+    """slot widths as the plans lay them out: every branch padded to a multiple of 4, the 1 x 1 branches concatenated"""
+    return cs4(w5), cs4(w3), sum(cs4(m) for m in w1c)
+
+
+def _s1_row(w5, w3, w1c):
+    return tuple(cdiv(v, 16) for v in _s1_widths(w5, w3, w1c))
+
+
+# (cin, w5, w3, 1 x 1 composition, reflect, bias, N, H, W, extra pixel stride of x): one case per <NA, NB, NC, true> the forward can reach
+S1_FWD_CASES = [
+    (23, 11, 12, (7, 9), 1, 1, 2, 13, 21, 0),
+    (9, 16, 5, (15, 15, 5), 0, 0, 1, 5, 7, 0),
+    (3, 3, 16, (11, 15, 15, 12), 1, 1, 3, 5, 7, 4),
+    (20, 18, 12, (11, 15), 0, 1, 1, 24, 40, 0),
+    (77, 23, 9, (16, 16, 1), 1, 0, 1, 17, 33, 0),
+    (77, 18, 12, (11, 15, 15, 12), 1, 1, 2, 24, 40, 0),
+    (40, 12, 18, (5, 13), 0, 1, 2, 9, 30, 8),
+    (16, 7, 32, (10, 10, 10), 1, 0, 1, 16, 32, 0),
+    (33, 16, 17, (13, 14, 15, 6), 0, 1, 1, 11, 19, 0),
+    (12, 32, 29, (30,), 1, 1, 1, 8, 16, 0),
+    (52, 17, 21, (9, 9, 9, 9), 0, 0, 2, 15, 17, 0),
+    (29, 30, 20, (16, 16, 16, 16), 1, 1, 1, 20, 23, 0),
+]
+S1_MSTRIDE_CASE = S1_FWD_CASES[3]      # finalize with mstride < scs
+# rows the forward cannot take: cat_tstage1_supported wants at least two N tiles in the 1 x 1 slot
+UNREACHABLE = {(1, 1, 1), (2, 1, 1), (1, 2, 1), (2, 2, 1)}
+
+# (dy channels, m5, m3, 1 x 1 composition, N, H, W, layout): one case per <NA, NB, NC, false>; layout 'sep' = three buffers, 'spade' = slots
+# 0 and 1 write two slices of one buffer and slot 2 another (fused_spade.py)
+S1_DGRAD_CASES = [
+    (77, 11, 12, (15,), 2, 13, 21, 'sep'),
+    (40, 18, 12, (12,), 1, 24, 40, 'spade'),
+    (9, 7, 20, (3, 9), 1, 5, 7, 'sep'),
+    (23, 17, 32, (16,), 1, 17, 33, 'sep'),
+    (20, 16, 16, (15, 15), 2, 9, 30, 'spade'),
+    (3, 5, 9, (15, 15, 12), 3, 4, 3, 'sep'),
+    (64, 12, 3, (16, 16, 16, 5), 1, 16, 32, 'sep'),
+    (77, 18, 12, (15, 12), 1, 11, 19, 'spade'),
+    (54, 21, 15, (15, 15, 12), 2, 24, 40, 'spade'),
+    (33, 32, 8, (13, 13, 13, 13), 1, 8, 16, 'sep'),
+    (12, 9, 18, (8, 10), 1, 20, 23, 'sep'),
+    (52, 14, 25, (20, 14), 1, 15, 17, 'spade'),
+    (29, 16, 17, (24, 30), 1, 10, 35, 'sep'),
+    (16, 20, 20, (20,), 2, 7, 13, 'sep'),
+    (77, 30, 31, (33,), 1, 9, 18, 'sep'),
+    (21, 17, 17, (21, 21, 10), 1, 19, 37, 'spade'),
+]
+
+
+def tconv_launch(nn, n, ho, wo, stats):
+    """mirror of nt / nblk / tw of cat_tconv_fwd with the default thresholds (8 x 32 tiles from 4096 workgroups of ONE N tile, never with stats)"""
+    nt_total = cdiv(nn, 16)
+    nblk = cdiv(nt_total, 8)
+    nt = cdiv(nt_total, nblk)
+    nblk = cdiv(nt_total, nt)
+    wg16 = n * cdiv(ho, 8) * cdiv(wo, 16) * nblk
+    tw = 16 if stats else (32 if (wg16 >= 4096 and nt <= 1) else 16)
+    return nt, nblk, tw
+
+
+# (NT, TW, stats) -> (cin, cout, k, reflect, N, H, W)
+TCONV_NT_CASES = {}
+for _nt, (_cin, _cout, _k, _refl) in enumerate([(23, 13, 3, 1), (9, 30, 5, 0), (40, 35, 1, 0), (18, 54, 3, 1), (12, 77, 5, 1), (77, 90, 3, 0),
+                                                (20, 100, 1, 0), (7, 120, 3, 1)], 1):
+    TCONV_NT_CASES[(_nt, 16, 0)] = (_cin, _cout, _k, _refl, 2, 19, 37)
+    TCONV_NT_CASES[(_nt, 16, 1)] = (_cin, _cout, _k, _refl, 1, 21, 50)
+TCONV_NT_CASES[(1, 32, 0)] = (16, 16, 3, 0, 2, 509, 520)
+TCONV_MULTI_NN = {4: 54, 6: 90, 7: 100}      # NT -> output channels of the multi-segment case
+
+# name -> N, H, W (lattice), th, tw, ncls, instance statistics, slices (c0, c), scs, mstride
+D_CASES = {
+    'narrow-ragged-batch': (2, 37, 70, 8, 16, 1, 0, [(0, 5), (8, 7)], 20, 20),
+    'narrow-ragged-instance': (2, 37, 70, 8, 16, 1, 1, [(0, 5), (8, 7)], 20, 16),
+    'narrow-1024-full': (2, 128, 512, 8, 16, 1, 0, [(4, 3), (8, 4)], 12, 12),
+    'wide-1025-ragged': (1, 197, 650, 8, 16, 1, 0, [(0, 2), (4, 6)], 12, 12),
+    'wide-2112-full-instance': (2, 264, 1024, 8, 16, 1, 1, [(0, 3), (4, 1)], 8, 8),
+    'tail-4224-full': (2, 264, 1024, 8, 16, 1, 0, [(0, 3), (4, 1)], 8, 8),
+    'tail-4225-ragged': (1, 517, 1030, 8, 16, 1, 0, [(0, 2), (4, 3)], 8, 7),
+    'f2-narrow-ragged-batch': (2, 10, 40, 4, 32, 4, 0, [(0, 6), (8, 2)], 12, 12),
+    'f2-narrow-ragged-instance': (2, 10, 40, 4, 32, 4, 1, [(0, 6), (8, 2)], 12, 12),
+    'f2-wide-ragged': (2, 33, 70, 2, 8, 4, 0, [(0, 5)], 8, 8),
+    'f2-full': (2, 16, 64, 4, 32, 4, 0, [(0, 4), (4, 4)], 8, 8),
+}
+# (N, H, W, th, tw, ncls, clamp, ranks): cat_tnorm_sums + cat_tnorm_finalize_sums
+SUMS_CASES = [(2, 37, 70, 8, 16, 1, 1, 1), (2, 37, 70, 8, 16, 1, 0, 1), (2, 37, 70, 8, 16, 1, 1, 2), (2, 10, 40, 4, 32, 4, 0, 2), (1, 197, 650, 8, 16, 1, 1, 1)]
+
+PLANES = [(2, 3, 3), (1, 7, 13), (2, 19, 37)]      # smaller than the 5 x 5 window under reflect padding, one partial tile, ragged multi-tile
+KS_CYCLE = (3, 1, 5)      # kernel size per channel quad, interleaved: mixed and not sorted
+# (nq, plane, first index into KS_CYCLE, reflect, per-image affine, act, bias, stats, extra strides (x, y, table))
+DWM_FWD_CASES = [
+    (1, 0, 2, 1, 1, ACT_RELU, 1, 1, (4, 8, 4)), (1, 1, 0, 0, 0, ACT_LRELU, 0, 1, (0, 0, 0)), (1, 2, 1, 1, 0, ACT_NONE, 1, 0, (8, 4, 0)),
+    (3, 0, 0, 1, 0, ACT_LRELU, 1, 1, (0, 4, 8)), (3, 1, 1, 1, 1, ACT_NONE, 0, 1, (4, 0, 4)), (3, 2, 2, 0, 1, ACT_RELU, 1, 1, (8, 8, 8)),
+    (16, 0, 0, 1, 1, ACT_RELU, 0, 1, (0, 0, 0)), (16, 1, 3, 0, 0, ACT_RELU, 1, 0, (4, 4, 0)), (16, 2, 1, 1, 1, ACT_LRELU, 1, 1, (8, 4, 4)),
+    (17, 0, 2, 0, 0, ACT_NONE, 1, 1, (4, 4, 4)), (17, 1, 0, 1, 1, ACT_RELU, 1, 1, (0, 8, 0)), (17, 2, 4, 0, 0, ACT_LRELU, 0, 1, (4, 0, 8)),
+    (24, 0, 1, 1, 0, ACT_LRELU, 1, 1, (8, 0, 4)), (24, 1, 2, 0, 1, ACT_RELU, 0, 1, (0, 4, 0)), (24, 2, 0, 1, 1, ACT_RELU, 1, 1, (4, 8, 8)),
+]
+# nq -> branches (channels, kernel size): every branch padded to whole quads, a one-channel branch next to wider ones
+DWM_BWD_BRANCHES = {1: None, 3: [(1, 3), (7, 5)], 16: [(15, 1), (1, 3), (16, 5), (12, 3), (13, 5)], 18: [(21, 5), (21, 3), (23, 1)]}
+# (nq, plane, reflect)
+DWM_BWD_CASES = [(nq, pl, refl) for nq in (1, 3, 16, 18) for pl in range(3) for refl in (1, 0)]
+
+# (G = N?, residual, (xcs, rcs, ycs) beyond C4, act, N, H, W, C4)
+AFFINE_CASES = [(0, 0, (0, 0, 0), ACT_NONE, 2, 9, 11, 12), (1, 1, (4, 8, 12), ACT_RELU, 3, 9, 11, 20), (0, 1, (8, 4, 0), ACT_LRELU, 2, 7, 5, 8),
+                (1, 0, (4, 0, 8), ACT_TANH, 2, 6, 6, 16), (0, 1, (0, 4, 8), ACT_RELU6, 1, 12, 10, 4), (0, 1, (4, 0, 4), ACT_RELU, 2, 300, 300, 32)]
+# (pad, add, (pcs, dcs, acs) beyond C4, N, H, W, C4)
+REFLECT_CASES = [(1, 0, (0, 0, 0), 2, 9, 11, 8), (2, 1, (4, 8, 12), 1, 7, 5, 12), (2, 0, (8, 0, 0), 2, 3, 3, 4), (1, 1, (0, 4, 4), 2, 2, 2, 4),
+                 (2, 1, (4, 0, 8), 2, 520, 520, 16)]
+
+
+# ================================================================================================ A: host
+def _s1_rows_of_source():
+    rows = []
+    for line in open(PK_SRC).read().splitlines():
+        if line.lstrip().startswith('#'):
+            continue
+        rows += [tuple(int(v) for v in m) for m in re.findall(r'CAT_S1\((\d+), (\d+), (\d+)\)', line)]
+    return rows
+
+
+def test_case_tables_cover_the_stage1_instantiations():
+    rows = _s1_rows_of_source()
+    assert len(rows) == 16 and len(set(rows)) == 16, rows
+    syms = {}
+    for name in json.load(open(PK_GOLDEN)):
+        m = re.search(r'tstage1_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])E', name)
+        if m:
+            syms.setdefault(tuple(int(v) for v in m.groups()[:3]), set()).add(int(m.group(4)))
+    assert set(syms) == set(rows), (sorted(set(rows) - set(syms)), sorted(set(syms) - set(rows)))
+    assert all(v == {0, 1} for v in syms.values()), syms
+    # forward: every row the support predicate admits has a case, the others are exactly the four NC == 1 rows
+    fwd = {_s1_row(c[1], c[2], c[3]): c for c in S1_FWD_CASES}
+    assert len(fwd) == len(S1_FWD_CASES)
+    for c in S1_FWD_CASES:
+        assert s1_supported(*_s1_widths(c[1], c[2], c[3])), c
+    reach = {r for r in rows if s1_supported(*(16 * v for v in r))}
+    assert UNREACHABLE == {r for r in rows if r[2] == 1} and len(UNREACHABLE) == 4
+    assert set(rows) - reach == UNREACHABLE
+    assert set(fwd) == reach, (sorted(reach - set(fwd)), sorted(set(fwd) - reach))
+    dg = {_s1_row(c[1], c[2], c[3]): c for c in S1_DGRAD_CASES}
+    assert len(dg) == len(S1_DGRAD_CASES) and set(dg) == set(rows), (sorted(set(rows) - set(dg)), sorted(set(dg) - set(rows)))
+    for c in S1_DGRAD_CASES:
+        assert s1_dgrad_supported(*_s1_widths(c[1], c[2], c[3])), c
+    assert any(c[7] == 'spade' for c in S1_DGRAD_CASES) and any(c[7] == 'sep' for c in S1_DGRAD_CASES)
+    # the edges the issue names, across the forward table
+    cins = [c[0] for c in S1_FWD_CASES]
+    assert any(c % 4 for c in cins) and any(c < 16 for c in cins) and {cs4(c) % 16 for c in cins} >= {4, 8, 12}
+    assert any(c[7] % 8 and c[8] % 16 for c in S1_FWD_CASES) and any(c[4] and c[7] < 8 and c[8] < 16 for c in S1_FWD_CASES)
+    assert {c[4] for c in S1_FWD_CASES} == {0, 1} and {c[5] for c in S1_FWD_CASES} == {0, 1}
+    assert any(c[6] > 1 for c in S1_FWD_CASES) and any(c[9] for c in S1_FWD_CASES)
+    assert all(not c[4] or (c[7] >= 5 and c[8] >= 5) for c in S1_FWD_CASES)
+    assert any(any(m % 4 for m in c[3]) for c in S1_FWD_CASES)      # zero columns inside the 1 x 1 slot
+
+
+def test_case_tables_cover_the_tconv_instantiations():
+    want = {(nt, 16, st) for nt in range(1, 9) for st in (0, 1)} | {(1, 32, 0)}
+    assert set(TCONV_NT_CASES) == want
+    for (nt, tw, st), (cin, cout, k, refl, n, h, w) in TCONV_NT_CASES.items():
+        got = tconv_launch(cout, n, h, w, st)
+        assert (got[0], got[2]) == (nt, tw), ((nt, tw, st), got)
+    assert sorted(TCONV_MULTI_NN) == [4, 6, 7]
+    for nt, nn in TCONV_MULTI_NN.items():
+        assert tconv_launch(nn, 2, 24, 40, 0) == (nt, 1, 16)
+    assert not any(k.startswith('CAT_PK_TW') for k in os.environ), 'the tile width must come from the default thresholds'
+
+
+def test_case_tables_cover_the_norm_and_depthwise_edges():
+    tiles = {}
+    for name, (n, h, w, th, tw, ncls, inst, slices, scs, mstride) in D_CASES.items():
+        per = cdiv(h, th) * cdiv(w, tw) * ncls
+        tiles[name] = (per if inst else per * n, h % th == 0 and w % tw == 0, inst, th, tw, ncls)
+        assert scs % 4 == 0 and all(c0 + c <= mstride <= scs for c0, c in slices), name
+    first = [v for v in tiles.values() if (v[3], v[4], v[5]) == (8, 16, 1)]
+    assert any(t <= 64 for t, *_ in first) and any(t == 1024 for t, *_ in first) and any(1024 < t <= 4096 for t, *_ in first)
+    assert any(t > 4096 and full for t, full, *_ in first) and any(t > 4096 and not full for t, full, *_ in first)
+    for name, (n, h, w, th, tw, *_r) in D_CASES.items():      # 'ragged' means along H and W: both factors of a tile's pixel count are exercised
+        assert ('ragged' in name) == (h % th != 0 and w % tw != 0) and ('full' in name or 'ragged' in name), name
+    assert all(c[1] % c[3] and c[2] % c[4] for c in SUMS_CASES)
+    assert any(1024 < t and inst for t, full, inst, *_ in first) and any(t <= 1024 and inst for t, full, inst, *_ in first)
+    second = [v for v in tiles.values() if v[5] == 4]
+    assert any(t > 1024 for t, *_ in second) and any(t <= 1024 and inst for t, f, inst, *_ in second) and any(f for t, f, *_ in second)
+    assert any(scs > 4 for *_, scs, _m in D_CASES.values()) and any(m < scs for *_, scs, m in D_CASES.values())
+    assert {c[6] for c in SUMS_CASES} == {0, 1} and {c[7] for c in SUMS_CASES} == {1, 2}
+    assert {c[0] for c in DWM_FWD_CASES} == {1, 3, 16, 17, 24} and {c[0] for c in DWM_BWD_CASES} == {1, 3, 16, 18}
+    for nq in (1, 3, 16, 17, 24):
+        assert {c[1] for c in DWM_FWD_CASES if c[0] == nq} == {0, 1, 2}
+    assert {c[3] for c in DWM_FWD_CASES} == {0, 1} and {c[4] for c in DWM_FWD_CASES} == {0, 1} and {c[6] for c in DWM_FWD_CASES} == {0, 1}
+    assert {c[5] for c in DWM_FWD_CASES} == {ACT_NONE, ACT_RELU, ACT_LRELU} and {c[7] for c in DWM_FWD_CASES} == {0, 1}
+    assert any(c[1] == 0 and c[3] and 5 in _dwm_ks(c[0], c[2]) for c in DWM_FWD_CASES)      # 3 x 3 plane, reflect, 5 x 5 filter
+    assert all(len(set(_dwm_ks(c[0], c[2]))) == 3 and _dwm_ks(c[0], c[2]) != sorted(_dwm_ks(c[0], c[2])) for c in DWM_FWD_CASES if c[0] >= 3)
+    for nq, br in DWM_BWD_BRANCHES.items():
+        assert br is None or (sum(cs4(c) for c, k in br) == 4 * nq and any(c == 1 for c, k in br) == (nq in (3, 16))), nq
+    assert {c[3] for c in AFFINE_CASES} == {ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_RELU6} and {c[0] for c in AFFINE_CASES} == {0, 1}
+    assert any(c[4] * c[5] * c[6] * c[7] // 4 // (c[4] if c[0] else 1) > 4096 * 256 for c in AFFINE_CASES)
+    assert {c[0] for c in REFLECT_CASES} == {1, 2} and {c[1] for c in REFLECT_CASES} == {0, 1}
+    assert any(c[4] == c[0] + 1 for c in REFLECT_CASES if c[0] == 1) and any(c[4] == c[0] + 1 for c in REFLECT_CASES if c[0] == 2)
+    assert any(c[3] * c[4] * c[5] * c[6] // 4 > 8192 * 256 for c in REFLECT_CASES)
+
+
+# ------------------------------------------------------------------------------------------------ references (host, any dtype)
+def _s1_layout(case):
+    """Z1 = [4 sentinel lanes | k = 1 slice | k = 3 slice | k = 5 slice | 4 sentinel lanes] -> slot widths, first columns, pixel stride,
+    branches (k, channels, first column)"""
+    cin, w5, w3, w1c = case[:4]
+    width = dict(zip((5, 3, 1), _s1_widths(w5, w3, w1c)))
+    col0 = {1: 4, 3: 4 + width[1], 5: 4 + width[1] + width[3]}
+    ycs = col0[5] + width[5] + 4
+    branches, o = [], col0[1]
+    for m in w1c:
+        branches.append((1, m, o))
+        o += cs4(m)
+    branches += [(3, w3, col0[3]), (5, w5, col0[5])]
+    return width, col0, ycs, branches
+
+
+@functools.lru_cache(maxsize=None)
+def _s1_inputs(case):
+    cin, w5, w3, w1c, reflect, bias, n, h, w, xpad = case
+    ycs, branches = _s1_layout(case)[2:]
+    x = detfill.normal((n, cin, h, w), 100)
+    ws = [detfill.normal((m, cin, k, k), 110 + i, 1.0 / np.sqrt(cin * k * k)) for i, (k, m, o) in enumerate(branches)]
+    bs = [detfill.normal((m,), 130 + i, 0.3) if bias else None for i, (k, m, o) in enumerate(branches)]
+    gamma, beta = detfill.normal((ycs,), 150).abs() + 0.5, detfill.normal((ycs,), 151, 0.3)
+    run = [(detfill.normal((m,), 160 + i, 0.1), detfill.normal((m,), 180 + i).abs() + 0.5) for i, (k, m, o) in enumerate(branches)]
+    return x, ws, bs, gamma, beta, run
+
+
+def _s1_ref(case, dtype):
+    cin, w5, w3, w1c, reflect, bias, n, h, w, xpad = case
+    branches = _s1_layout(case)[3]
+    x, ws, bs, gamma, beta, run = _s1_inputs(case)
+    out = {}
+    for i, (k, m, o) in enumerate(branches):
+        p = k // 2
+        z = F.conv2d(_pad(x.to(dtype), p, reflect), ws[i].to(dtype), None if bs[i] is None else bs[i].to(dtype), padding=0)
+        s, m2, _ = _tile_stats(z)
+        out.update({'z%d' % i: z, 'sum%d' % i: s, 'm2%d' % i: m2})
+        for tag, inst in (('b', 0), ('i', 1)):
+            r = _norm_ref(z, inst, gamma[o:o + m], beta[o:o + m], None if inst else run[i][0], None if inst else run[i][1])
+            out.update({'%s%s%d' % (tag, key, i): v for key, v in r.items()})
+    return out
+
+
+def _dg_layout(case):
+    """-> slot widths (5, 3, 1), per slot (buffer index, first column), pixel stride per buffer, branches (slot, k, channels, column in slot)"""
+    cout, m5, m3, m1c, n, h, w, layout = case
+    width = _s1_widths(m5, m3, m1c)
+    if layout == 'sep':
+        place = [(0, 4), (1, 0), (2, 8)]
+        strides = [width[0] + 8, width[1] + 4, width[2] + 12]
+    else:
+        place = [(0, 4), (0, 4 + width[0] + 4), (1, 0)]
+        strides = [4 + width[0] + 4 + width[1] + 4, width[2] + 4]
+    branches, o = [(0, 5, m5, 0), (1, 3, m3, 0)], 0
+    for m in m1c:
+        branches.append((2, 1, m, o))
+        o += cs4(m)
+    return width, place, strides, branches
+
+
+@functools.lru_cache(maxsize=None)
+def _dg_inputs(case):
+    cout, m5, m3, m1c, n, h, w, layout = case
+    branches = _dg_layout(case)[3]
+    dy = detfill.normal((n, cout, h, w), 200)
+    ws = [detfill.normal((cout, m, k, k), 210 + i, 1.0 / np.sqrt(cout * k * k)) for i, (slot, k, m, o) in enumerate(branches)]
+    return dy, ws
+
+
+def _dg_ref(case, dtype):
+    cout, m5, m3, m1c, n, h, w, layout = case
+    branches = _dg_layout(case)[3]
+    dy, ws = _dg_inputs(case)
+    out = {}
+    for i, (slot, k, m, o) in enumerate(branches):
+        a = torch.zeros((n, m, h, w), dtype=dtype, requires_grad=True)
+        out['dx%d' % i], = torch.autograd.grad(F.conv2d(a, ws[i].to(dtype), padding=k // 2), a, dy.to(dtype))
+    return out
+
+
+@functools.lru_cache(maxsize=2)
+def _d_data(n, h, w, ncls, ctot):
+    """x [N, C, ncls, H, W] with per-channel mean and spread, |mean| <= std (float32 values)"""
+    std = detfill.normal((ctot,), 301).abs() + 0.5
+    mean = std * torch.tanh(detfill.normal((ctot,), 302))
+    x = detfill.normal((n, ctot, ncls, h, w), 300) * std.view(1, -1, 1, 1, 1) + mean.view(1, -1, 1, 1, 1)
+    return x
+
+
+def _d_table(x, th, tw):
+    """float64 per-tile sum / M2 of x [N, C, ncls, H, W] in the kernels' entry order [image][lattice tile][class] -> [entries][C] each, pixels
+    per entry [entries per image]"""
+    n, c, ncls, h, w = x.shape
+    s, m2, cnt = _tile_stats(x.double().reshape(n, c * ncls, h, w), th, tw)
+    t = cnt.numel()
+    order = lambda v: v.view(n, t, c, ncls).permute(0, 1, 3, 2).reshape(n * t * ncls, c)
+    return order(s), order(m2), cnt.repeat_interleave(ncls)
+
+
+@functools.lru_cache(maxsize=2)
+def _d_inputs(name):
+    n, h, w, th, tw, ncls, inst, slices, scs, mstride = D_CASES[name]
+    ctot = sum(c for c0, c in slices)
+    x = _d_data(n, h, w, ncls, ctot)
+    s, m2, cnt = _d_table(x, th, tw)
+    table = torch.full((s.shape[0], 2, scs), SENTINEL)
+    o = 0
+    for c0, c in slices:
+        table[:, 0, c0:c0 + c], table[:, 1, c0:c0 + c] = s[:, o:o + c].float(), m2[:, o:o + c].float()
+        o += c
+    gamma, beta = detfill.normal((scs,), 310).abs() + 0.5, detfill.normal((scs,), 311, 0.3)
+    run = [(detfill.normal((c,), 320 + i, 0.1), detfill.normal((c,), 330 + i).abs() + 0.5) for i, (c0, c) in enumerate(slices)]
+    return x, table, cnt, gamma, beta, run
+
+
+def _d_ref(name, dtype):
+    """float64: the statistics of x itself; float32: the exact pairwise merge of the float32 table, the kernel's own formula"""
+    n, h, w, th, tw, ncls, inst, slices, scs, mstride = D_CASES[name]
+    x, table, cnt, gamma, beta, run = _d_inputs(name)
+    out, o = {}, 0
+    for i, (c0, c) in enumerate(slices):
+        g, b = gamma[c0:c0 + c], beta[c0:c0 + c]
+        if dtype == torch.float64:
+            r = _norm_ref(x[:, o:o + c].double(), inst, g, b, None if inst else run[i][0], None if inst else run[i][1])
+        else:
+            G = n if inst else 1
+            s, m2 = table[:, 0, c0:c0 + c].view(G, -1, c), table[:, 1, c0:c0 + c].view(G, -1, c)
+            nt = cnt.float().repeat(n // G).view(1, -1, 1)
+            count = float(h * w * ncls * (n // G))
+            mean = s.sum(1) / count
+            var = (m2 + nt * (s / nt - mean[:, None]) ** 2).sum(1) / count
+            rstd = (var + EPS) ** -0.5
+            r = {'scale': g * rstd, 'shift': b - mean * g * rstd, 'mean': mean, 'rstd': rstd}
+            if not inst:
+                r['rm'] = (1 - MOM) * run[i][0] + MOM * mean[0]
+                r['rv'] = (1 - MOM) * run[i][1] + MOM * var[0] * count / (count - 1)
+        out.update({'%s%d' % (key, i): v for key, v in r.items()})
+        o += c
+    return out
+
+
+SUMS_SLICES, SUMS_SCS = [(0, 5), (8, 3)], 12      # the last channel of the second slice is constant: var = 0, the clamp decides
+
+
+@functools.lru_cache(maxsize=2)
+def _sums_inputs(case):
+    n, h, w, th, tw, ncls, clamp, ranks = case
+    x = _d_data(n, h, w, ncls, 8).clone()
+    x[:, 7] = 0.5
+    s, m2, cnt = _d_table(x, th, tw)
+    table = torch.zeros((s.shape[0], 2, SUMS_SCS))      # cat_tnorm_sums folds every column of the table
+    o = 0
+    for c0, c in SUMS_SLICES:
+        table[:, 0, c0:c0 + c], table[:, 1, c0:c0 + c] = s[:, o:o + c].float(), m2[:, o:o + c].float()
+        o += c
+    gamma, beta = detfill.normal((SUMS_SCS,), 340).abs() + 0.5, detfill.normal((SUMS_SCS,), 341, 0.3)
+    run = [(detfill.normal((c,), 350 + i, 0.1), detfill.normal((c,), 360 + i).abs() + 0.5) for i, (c0, c) in enumerate(SUMS_SLICES)]
+    return x, table, cnt, gamma, beta, run
+
+
+def _sums_ref(case, dtype):
+    """[sum x | sum x^2] and the multi-replica formula of SynchronizedBatchNorm over them (count and sums of `ranks` equal ranks)"""
+    n, h, w, th, tw, ncls, clamp, ranks = case
+    x, table, cnt, gamma, beta, run = _sums_inputs(case)
+    out, o = {}, 0
+    count = float(n * h * w * ncls * ranks)
+    for i, (c0, c) in enumerate(SUMS_SLICES):
+        if dtype == torch.float64:
+            v = x[:, o:o + c].double()
+            sx, sq = v.sum((0, 2, 3, 4)), (v * v).sum((0, 2, 3, 4))
+        else:
+            s, m2 = table[:, 0, c0:c0 + c], table[:, 1, c0:c0 + c]
+            nt = cnt.float().repeat(n).view(-1, 1)
+            sx, sq = s.sum(0), (m2 + s * s / nt).sum(0)
+        g, b = gamma[c0:c0 + c].to(dtype), beta[c0:c0 + c].to(dtype)
+        tx, tq = sx * ranks, sq * ranks
+        mean = tx / count
+        sumvar = torch.clamp(tq - tx * mean, min=0.0)
+        var = sumvar / count
+        rstd = torch.clamp(var, min=EPS) ** -0.5 if clamp else (var + EPS) ** -0.5
+        r = {'sx': sx, 'sq': sq, 'a': rstd, 'b': -mean * rstd, 'scale': g * rstd, 'shift': b - mean * g * rstd,
+             'rm': (1 - MOM) * run[i][0].to(dtype) + MOM * mean, 'rv': (1 - MOM) * run[i][1].to(dtype) + MOM * sumvar / (count - 1)}
+        out.update({'%s%d' % (key, i): t for key, t in r.items()})
+        o += c
+    return out
+
+
+def _dwm_ks(nq, rot):
+    return [KS_CYCLE[(q + rot) % len(KS_CYCLE)] for q in range(nq)]
+
+
+def _frame(w_list, ks_list):
+    """depthwise filters [c][ks][ks] per branch / quad -> the 5 x 5 frame [C][5][5] (zeros around a smaller filter)"""
+    rows = []
+    for wt, ks in zip(w_list, ks_list):
+        o = 2 - ks // 2
+        f = torch.zeros((wt.shape[0], 5, 5), dtype=wt.dtype)
+        f[:, o:o + ks, o:o + ks] = wt
+        rows.append(f)
+    return torch.cat(rows)
+
+
+@functools.lru_cache(maxsize=None)
+def _dwf_inputs(case):
+    nq, plane, rot, reflect, per_image, act, bias, stats, extra = case
+    n, h, w = PLANES[plane]
+    c = 4 * nq
+    ks = _dwm_ks(nq, rot)
+    x = detfill.normal((n, c, h, w), 400)
+    G = n if per_image else 1
+    scale, shift = detfill.normal((G, c), 401).abs() + 0.5, detfill.normal((G, c), 402, 0.3)
+    ws = [detfill.normal((4, k, k), 410 + q, 1.0 / k) for q, k in enumerate(ks)]
+    b = detfill.normal((c,), 403, 0.2) if bias else None
+    return x, scale, shift, ws, b, ks
+
+
+def _dwf_ref(case, dtype):
+    nq, plane, rot, reflect, per_image, act, bias, stats, extra = case
+    x, scale, shift, ws, b, ks = _dwf_inputs(case)
+    n, c, h, w = x.shape
+    a = _act(x.to(dtype) * scale.to(dtype).view(-1, c, 1, 1) + shift.to(dtype).view(-1, c, 1, 1), act)
+    y = torch.zeros((n, c, h, w), dtype=dtype)
+    for k in (1, 3, 5):
+        qs = [q for q in range(nq) if ks[q] == k]
+        if qs:
+            idx = torch.tensor([4 * q + e for q in qs for e in range(4)])
+            wt = torch.cat([ws[q] for q in qs]).to(dtype).unsqueeze(1)
+            y[:, idx] = F.conv2d(_pad(a[:, idx], k // 2, reflect), wt, None if b is None else b[idx].to(dtype), padding=0, groups=len(idx))
+    out = {'y': y}
+    if stats:
+        out['sum'], out['m2'], _ = _tile_stats(y)
+    return out
+
+
+def _dwb_branches(case):
+    nq, plane, reflect = case
+    return DWM_BWD_BRANCHES[nq] or [(3, (5, 3, 1)[plane])]
+
+
+@functools.lru_cache(maxsize=None)
+def _dwb_inputs(case):
+    nq, plane, reflect = case
+    n, h, w = PLANES[plane]
+    br = _dwb_branches(case)
+    c4 = 4 * nq
+    a, dz = torch.zeros((n, c4, h, w)), torch.zeros((n, c4, h, w))      # padding channels of a branch: zeros, as the product leaves them
+    ws, prev, o = [], [], 0
+    for i, (c, k) in enumerate(br):
+        a[:, o:o + c] = F.relu(detfill.normal((n, c, h, w), 500 + i) + 0.3)
+        dz[:, o:o + c] = detfill.normal((n, c, h, w), 520 + i)
+        ws.append(detfill.normal((c, k, k), 540 + i, 1.0 / k))
+        prev.append(detfill.normal((c, k, k), 560 + i, float(np.sqrt(n * h * w))))
+        o += cs4(c)
+    return a, dz, ws, prev
+
+
+def _dwb_ref(case, dtype):
+    nq, plane, reflect = case
+    br = _dwb_branches(case)
+    a32, dz, ws, prev = _dwb_inputs(case)
+    a = a32.to(dtype).requires_grad_(True)
+    wl = [wt.to(dtype).unsqueeze(1).requires_grad_(True) for wt in ws]
+    zs, gz, o = [], [], 0
+    for (c, k), wt in zip(br, wl):
+        zs.append(F.conv2d(_pad(a[:, o:o + c], k // 2, reflect), wt, padding=0, groups=c))
+        gz.append(dz[:, o:o + c].to(dtype))
+        o += cs4(c)
+    grads = torch.autograd.grad(zs, [a] + wl, gz)
+    out = {'da': grads[0]}
+    for i, g in enumerate(grads[1:]):
+        out['dw%d' % i] = g.squeeze(1)
+        out['dwacc%d' % i] = prev[i].to(dtype) + g.squeeze(1)
+    return out
+
+
+@functools.lru_cache(maxsize=2)
+def _tc_inputs(key):
+    cin, cout, k, reflect, n, h, w = TCONV_NT_CASES[key]
+    return (detfill.normal((n, cin, h, w), 600), detfill.normal((cout, cin, k, k), 601, 1.0 / np.sqrt(cin * k * k)), detfill.normal((cout,), 602, 0.2))
+
+
+def _tc_ref(key, dtype):
+    cin, cout, k, reflect, n, h, w = TCONV_NT_CASES[key]
+    x, wt, b = _tc_inputs(key)
+    y = F.conv2d(_pad(x.to(dtype), k // 2, reflect), wt.to(dtype), b.to(dtype), padding=0)
+    if key[2]:
+        s, m2, _ = _tile_stats(y)
+        return {'y': y, 'sum': s, 'm2': m2}
+    return {'y': F.leaky_relu(y, 0.2)}
+
+
+MULTI_MS, MULTI_KS, MULTI_ACTS = [11, 12, 18, 15], [1, 3, 5, 1], [ACT_RELU, ACT_LRELU, ACT_RELU, ACT_NONE]
+MULTI_SHAPE = (2, 24, 40)
+
+
+@functools.lru_cache(maxsize=None)
+def _multi_inputs(nn):
+    n, h, w = MULTI_SHAPE
+    hb = [detfill.normal((n, m, h, w), 620 + i) for i, m in enumerate(MULTI_MS)]
+    sc = [detfill.normal((n, m), 630 + i).abs() + 0.5 for i, m in enumerate(MULTI_MS)]      # per-image rows (sstride != 0)
+    sh = [detfill.normal((n, m), 640 + i, 0.3) for i, m in enumerate(MULTI_MS)]
+    ws = [detfill.normal((nn, m, k, k), 650 + i, 1.0 / np.sqrt(m * k * k * 4)) for i, (m, k) in enumerate(zip(MULTI_MS, MULTI_KS))]
+    return hb, sc, sh, ws, detfill.normal((nn,), 660, 0.1), detfill.normal((n, nn, h, w), 661)
+
+
+def _multi_ref(nn, reflect, dtype):
+    hb, sc, sh, ws, b, res = _multi_inputs(nn)
+    y = res.to(dtype) * 0
+    for i, k in enumerate(MULTI_KS):
+        a = _act(hb[i].to(dtype) * sc[i].to(dtype)[:, :, None, None] + sh[i].to(dtype)[:, :, None, None], MULTI_ACTS[i])
+        y = y + F.conv2d(_pad(a, k // 2, reflect), ws[i].to(dtype), padding=0)
+    return {'y': F.leaky_relu(y + b.to(dtype).view(1, -1, 1, 1), 0.2) + res.to(dtype)}
+
+
+@functools.lru_cache(maxsize=1)
+def _aff_inputs(case):
+    per_image, has_res, extra, act, n, h, w, c4 = case
+    G = n if per_image else 1
+    return (detfill.normal((n, c4, h, w), 700), detfill.normal((G, c4), 701).abs() + 0.5, detfill.normal((G, c4), 702, 0.3),
+            detfill.normal((n, c4, h, w), 703) if has_res else None)
+
+
+def _aff_ref(case, dtype):
+    per_image, has_res, extra, act, n, h, w, c4 = case
+    x, sc, sh, res = _aff_inputs(case)
+    y = _act(x.to(dtype) * sc.to(dtype).view(-1, c4, 1, 1) + sh.to(dtype).view(-1, c4, 1, 1), act)
+    return {'y': y + res.to(dtype) if has_res else y}
+
+
+@functools.lru_cache(maxsize=1)
+def _rp_inputs(case):
+    pad, has_add, extra, n, h, w, c4 = case
+    return detfill.normal((n, c4, h + 2 * pad, w + 2 * pad), 710), detfill.normal((n, c4, h, w), 711) if has_add else None
+
+
+def _rp_ref(case, dtype):
+    pad, has_add, extra, n, h, w, c4 = case
+    dxp, add = _rp_inputs(case)
+    x = torch.zeros((n, c4, h, w), dtype=dtype, requires_grad=True)
+    dx, = torch.autograd.grad(F.pad(x, (pad,) * 4, mode='reflect'), x, dxp.to(dtype))
+    return {'dx': dx + add.to(dtype) if has_add else dx}
+
+
+def test_fp32_twin_of_every_reference_is_within_a_tenth_of_the_bar():
+    """B-F on the host: float32 ATen against float64 ATen, <= TOL / 10 (1e-7 for the reflect fold's 1e-6)"""
+    for case in S1_FWD_CASES:
+        _host('B', case, functools.partial(_s1_ref, case))
+    for case in S1_DGRAD_CASES:
+        _host('C', case, functools.partial(_dg_ref, case))
+    for name in D_CASES:
+        _host('D', name, functools.partial(_d_ref, name))
+    for case in SUMS_CASES:
+        _host('D-sums', case, functools.partial(_sums_ref, case))
+    for case in DWM_FWD_CASES:
+        _host('E-fwd', case, functools.partial(_dwf_ref, case))
+    for case in DWM_BWD_CASES:
+        _host('E-bwd', case, functools.partial(_dwb_ref, case))
+    for key in TCONV_NT_CASES:
+        _host('F-tconv', key, functools.partial(_tc_ref, key))
+    for nt, nn in TCONV_MULTI_NN.items():
+        _host('F-multi', nt, functools.partial(_multi_ref, nn, nt != 6))
+    for case in AFFINE_CASES:
+        _host('F-affine', case, functools.partial(_aff_ref, case))
+    for case in REFLECT_CASES:
+        r64, r32 = _rp_ref(case, torch.float64), _rp_ref(case, torch.float32)
+        d = rel(r32['dx'], r64['dx'])
+        print('host F-reflect', case, 'fp32-vs-fp64 rel %.3g' % d)
+        assert d <= 1e-7, (case, d)
+
+
+# ================================================================================================ GPU plumbing
+@pytest.fixture(scope='module')
+def dev():
+    from cat_amd import _lib
+    _lib.load()
+    return torch.device('cuda:0')
+
+
+def _profiled(fn):
+    from cat_amd import _lib
+    lib = _lib.load()
+    lib.cat_prof_enable(1)
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+        fam = _families()
+    finally:
+        lib.cat_prof_enable(0)
+    return out, fam
+
+
+def _padded_weight(wt, dev):
+    from cat_amd import ops
+    wg = ops.padded_weight_like(wt.shape, dev)
+    wg.copy_(wt)
+    return wg
+
+
+def _nhwc_buffer(x, cs, dev, pad_to=None):
+    """x [N, C, H, W] (host) -> device [N, H, W, cs]: the channels, zeros up to `pad_to` (the lanes a kernel reads as padding), the sentinel in
+    the lanes that belong to a neighbour"""
+    n, c, h, w = x.shape
+    buf = torch.full((n, h, w, cs), SENTINEL)
+    buf[..., :pad_to or cs4(c)] = 0.0
+    buf[..., :c] = x.permute(0, 2, 3, 1)
+    return buf.to(dev)
+
+
+def _sentinel(shape, dev, fill=SENTINEL):
+    """a buffer of `shape` with 64 more sentinels behind it: a write past the end stays inside the allocation and is seen"""
+    numel = int(np.prod(shape))
+    flat = torch.full((numel + 64,), fill, device=dev)
+    flat[numel:] = SENTINEL
+    return flat, flat[:numel].view(*shape)
+
+
+def _columns(buf, owned, valid, what):
+    """buf [..., cs] on the host: the `valid` columns finite, the other `owned` ones exactly 0.0, everything else the sentinel"""
+    cs = buf.shape[-1]
+    own, val = torch.zeros(cs, dtype=torch.bool), torch.zeros(cs, dtype=torch.bool)
+    own[list(owned)] = True
+    val[list(valid)] = True
+    assert bool((val & ~own).sum() == 0)
+    assert bool(torch.isfinite(buf[..., val]).all()), what
+    assert bool((buf[..., own & ~val] == 0.0).all()), (what, 'padding columns')
+    assert bool((buf[..., ~own] == SENTINEL).all()), (what, 'sentinel columns')
+
+
+def _tail(flat, what):
+    assert bool((flat[-64:] == SENTINEL).all()), (what, 'tail')
+
+
+def _nchw(buf, c0, c):
+    return buf[..., c0:c0 + c].permute(0, 3, 1, 2)
+
+
+def _prep_run(jobs, dev, accumulate=0):
+    """one cat_prep_run over a job table (fields as fused_block._Plan._jobs_to_dev fills them)"""
+    from cat_amd import _lib as L, ops
+    arr = (L.PrepJob * len(jobs))()
+    blk = 0
+    for i, j in enumerate(jobs):
+        for f, v in j.items():
+            if f == 'srcs':
+                for k, pv in enumerate(v):
+                    arr[i].srcs[k] = pv
+            elif f != 'threads':
+                setattr(arr[i], f, v)
+        nb = max(1, (j['threads'] + 255) // 256)
+        arr[i].block0, arr[i].nblocks = blk, nb
+        blk += nb
+    t = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    L.call('cat_prep_run', ops._p(t), len(jobs), blk, accumulate, ops._stream())
+    torch.cuda.synchronize()
+
+
+def _pack_job(wg, dst, mode, ks, nt_total, col0):
+    """kind 0: the filter stream of one conv into the columns [col0, col0 + Nn) of a shared stream"""
+    from cat_amd import ops
+    wcs = ops.weight_wcs(wg)
+    o, i = wg.shape[:2]
+    nn, ck = (o, i) if mode == FWD else (i, o)
+    c4, taps = cs4(ck), ks * ks
+    groups = (c4 // 16) * taps + ((taps * ((c4 % 16) // 4) + 3) // 4 if c4 % 16 else 0)
+    ntw = (col0 + nn + 15) // 16 - col0 // 16
+    return dict(kind=0, srcs=[wg.data_ptr()], dst=dst.data_ptr(), mode=mode, Nn=nn, Ck=ck, ks=ks, wcs=wcs, wn=taps * wcs, c4=c4, nt_total=nt_total,
+                col0=col0, threads=groups * ntw * 64)
+
+
+def _concat_pack(items, mode, ks, ck, width, dev):
+    """the N-concatenated filter stream of several convs as the plans build it: a zeroed stream, one kind-0 job per conv at its column"""
+    from cat_amd import tconv
+    dst = torch.zeros(tconv.pack_floats(ks, cs4(ck), width), device=dev)
+    _prep_run([_pack_job(wg, dst, mode, ks, cdiv(width, 16), col0) for wg, col0 in items], dev)
+    return dst
+
+
+def _finalize_gpu(dev, table, scs, inst, n, ho, wo, gamma, beta, pairs, run, mstride, tile=None):
+    """cat_tnorm_finalize (or finalize2 with tile = (th, tw, ncls)) into NaN-filled rows -> per-slice dict like _norm_ref's, after the exact
+    checks: zeros for scale / shift (and mean / rstd below mstride) in channels of no slice, num_batches incremented once per slice"""
+    from cat_amd import _lib as L, ops
+    G = n if inst else 1
+    sl = (L.NSlice * len(pairs))()
+    keep = []
+    for i, (c0, c) in enumerate(pairs):
+        sl[i].c0, sl[i].c = c0, c
+        if not inst:
+            keep.append((run[i][0].to(dev), run[i][1].to(dev), torch.full((1,), 3, dtype=torch.int64, device=dev)))
+            sl[i].running_mean, sl[i].running_var, sl[i].num_batches = (t.data_ptr() for t in keep[-1])
+    scale, shift = torch.full((G, scs), NAN, device=dev), torch.full((G, scs), NAN, device=dev)
+    mean, rstd = torch.full((G, mstride), NAN, device=dev), torch.full((G, mstride), NAN, device=dev)
+    gg, bg = gamma.to(dev), beta.to(dev)
+    tail = (ops._p(gg), ops._p(bg), len(pairs), sl, EPS, MOM, ops._p(scale), ops._p(shift), ops._p(mean), ops._p(rstd), mstride, ops._stream())
+    if tile is None:
+        L.call('cat_tnorm_finalize', ops._p(table), scs, G, n, ho, wo, *tail)
+    else:
+        L.call('cat_tnorm_finalize2', ops._p(table), scs, G, n, ho, wo, tile[0], tile[1], tile[2], *tail)
+    torch.cuda.synchronize()
+    scale, shift, mean, rstd = scale.cpu(), shift.cpu(), mean.cpu(), rstd.cpu()
+    owned = torch.zeros(scs, dtype=torch.bool)
+    for c0, c in pairs:
+        owned[c0:c0 + c] = True
+    assert bool((scale[:, ~owned] == 0.0).all()) and bool((shift[:, ~owned] == 0.0).all())
+    assert bool((mean[:, ~owned[:mstride]] == 0.0).all()) and bool((rstd[:, ~owned[:mstride]] == 0.0).all())
+    out = {}
+    for i, (c0, c) in enumerate(pairs):
+        out.update({'scale%d' % i: scale[:, c0:c0 + c], 'shift%d' % i: shift[:, c0:c0 + c], 'mean%d' % i: mean[:, c0:c0 + c],
+                    'rstd%d' % i: rstd[:, c0:c0 + c]})
+        if not inst:
+            out['rm%d' % i], out['rv%d' % i] = keep[i][0].cpu(), keep[i][1].cpu()
+            assert int(keep[i][2].item()) == 4, 'num_batches is incremented once per slice'
+    return out
+
+
+# ================================================================================================ B: cat_tstage1_fwd
+@pytest.mark.gpu
+def test_stage1_support_predicates_match_their_mirrors(dev):
+    from cat_amd import _lib as L
+    for w5 in (0, 1, 16, 17, 32, 33):
+        for w3 in (0, 4, 16, 20, 32, 36):
+            for w1 in (0, 8, 16, 17, 32, 48, 49, 64, 65):
+                assert bool(L.query('cat_tstage1_supported', w5, w3, w1)) == bool(s1_supported(w5, w3, w1)), (w5, w3, w1)
+                assert bool(L.query('cat_tstage1_dgrad_supported', w5, w3, w1)) == bool(s1_dgrad_supported(w5, w3, w1)), (w5, w3, w1)
+    for c in S1_FWD_CASES:
+        assert L.query('cat_tstage1_supported', *_s1_widths(c[1], c[2], c[3])) == 1, c
+    for c in S1_DGRAD_CASES:
+        assert L.query('cat_tstage1_dgrad_supported', *_s1_widths(c[1], c[2], c[3])) == 1, c
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', S1_FWD_CASES, ids=lambda c: 'x'.join(str(v) for v in _s1_row(c[1], c[2], c[3])) + '-cin%d' % c[0])
+def test_stage1_fwd(dev, case):
+    from cat_amd import _lib as L, ops, tconv
+    cin, w5, w3, w1c, reflect, bias, n, h, w, xpad = case
+    width, col0, ycs, branches = _s1_layout(case)
+    x, ws, bs, gamma, beta, run = _s1_inputs(case)
+    want = _s1_ref(case, torch.float64)
+    scs, tiles = ycs, n * cdiv(h, 8) * cdiv(w, 16)
+    xg = _nhwc_buffer(x, cs4(cin) + xpad, dev, pad_to=cs4(cin))
+    wgs = [_padded_weight(wt, dev) for wt in ws]
+    packs = {}
+    for k in (1, 3, 5):
+        items = [(wgs[i], o - col0[k]) for i, (bk, m, o) in enumerate(branches) if bk == k]
+        packs[k] = tconv.pack(items[0][0], FWD) if k > 1 else _concat_pack(items, FWD, k, cin, width[k], dev)
+    bvec = torch.zeros(ycs)
+    for (k, m, o), b in zip(branches, bs):
+        if b is not None:
+            bvec[o:o + m] = b
+    bg = bvec.to(dev) if bias else None
+    gs = L.Stage1Geom()
+    gs.N, gs.H, gs.W, gs.xcs, gs.cin, gs.reflect, gs.ycs, gs.scs = n, h, w, cs4(cin) + xpad, cin, reflect, ycs, scs
+    pk = (C.c_void_p * 3)()
+    for slot, k in enumerate((5, 3, 1)):
+        gs.col0[slot], gs.width[slot], gs.nvalid[slot] = col0[k], width[k], sum(m for bk, m, o in branches if bk == k)
+        pk[slot] = packs[k].data_ptr()
+    zflat, z = _sentinel((n, h, w, ycs), dev)
+    tflat, tab = _sentinel((tiles, 2, scs), dev)
+    _, fam = _profiled(lambda: L.call('cat_tstage1_fwd', C.byref(gs), ops._p(xg), pk, ops._p(bg), ops._p(z), ops._p(tab), ops._stream()))
+    assert fam.get('conv_tstage1', 0) == 1, fam
+    zc, tc = z.cpu(), tab.cpu()
+    owned = [c for k in (1, 3, 5) for c in range(col0[k], col0[k] + width[k])]
+    valid = [c for k, m, o in branches for c in range(o, o + m)]
+    _columns(zc, owned, valid, (case, 'Z1'))
+    _columns(tc, owned, valid, (case, 'table'))
+    _tail(zflat, (case, 'Z1'))
+    _tail(tflat, (case, 'table'))
+    got = {}
+    for i, (k, m, o) in enumerate(branches):
+        got.update({'z%d' % i: _nchw(zc, o, m), 'sum%d' % i: tc[:, 0, o:o + m], 'm2%d' % i: tc[:, 1, o:o + m]})
+    pairs = [(o, m) for k, m, o in branches]
+    mstride = scs - 4 if case == S1_MSTRIDE_CASE else scs
+    for tag, inst in (('b', 0), ('i', 1)):
+        r = _finalize_gpu(dev, tab, scs, inst, n, h, w, gamma, beta, pairs, run, mstride)
+        got.update({tag + key: v for key, v in r.items()})
+    _cmp('B', case, got, want)
+
+
+# ================================================================================================ C: cat_tstage1_dgrad
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', S1_DGRAD_CASES, ids=lambda c: 'x'.join(str(v) for v in _s1_row(c[1], c[2], c[3])) + '-' + c[7])
+def test_stage1_dgrad(dev, case):
+    from cat_amd import _lib as L, ops, tconv
+    cout, m5, m3, m1c, n, h, w, layout = case
+    width, place, strides, branches = _dg_layout(case)
+    dy, ws = _dg_inputs(case)
+    want = _dg_ref(case, torch.float64)
+    dyg = _nhwc_buffer(dy, cs4(cout), dev)
+    wgs = [_padded_weight(wt, dev) for wt in ws]
+    packs = [tconv.pack(wgs[0], DGRAD), tconv.pack(wgs[1], DGRAD),
+             _concat_pack([(wgs[i], o) for i, (slot, k, m, o) in enumerate(branches) if slot == 2], DGRAD, 1, cout, width[2], dev)]
+    bufs = [_sentinel((n, h, w, cs), dev) for cs in strides]
+    gs = L.Stage1Geom()
+    gs.N, gs.H, gs.W, gs.xcs, gs.cin, gs.reflect, gs.ycs, gs.scs = n, h, w, cs4(cout), cout, 0, 0, 0
+    pk, dxs, dxcs = (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_int * 3)()
+    for slot in range(3):
+        bi, c0 = place[slot]
+        gs.col0[slot], gs.width[slot], gs.nvalid[slot] = c0, width[slot], sum(m for s, k, m, o in branches if s == slot)
+        pk[slot], dxs[slot], dxcs[slot] = packs[slot].data_ptr(), bufs[bi][1].data_ptr(), strides[bi]
+    _, fam = _profiled(lambda: L.call('cat_tstage1_dgrad', C.byref(gs), ops._p(dyg), pk, dxs, dxcs, ops._stream()))
+    assert fam.get('conv_tstage1_dgrad', 0) == 1, fam
+    host = [b[1].cpu() for b in bufs]
+    for bi, (flat, _) in enumerate(bufs):
+        owned = [c for slot in range(3) if place[slot][0] == bi for c in range(place[slot][1], place[slot][1] + width[slot])]
+        valid = [c for slot, k, m, o in branches if place[slot][0] == bi for c in range(place[slot][1] + o, place[slot][1] + o + m)]
+        _columns(host[bi], owned, valid, (case, 'buffer', bi))
+        _tail(flat, (case, 'buffer', bi))
+    got = {'dx%d' % i: _nchw(host[place[slot][0]], place[slot][1] + o, m) for i, (slot, k, m, o) in enumerate(branches)}
+    _cmp('C', case, got, want)
+
+
+# ================================================================================================ D: tile-norm kernels on synthetic tables
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', sorted(D_CASES))
+def test_tnorm_finalize_on_synthetic_tables(dev, name):
+    n, h, w, th, tw, ncls, inst, slices, scs, mstride = D_CASES[name]
+    x, table, cnt, gamma, beta, run = _d_inputs(name)
+    want = _d_ref(name, torch.float64)
+    tg = table.to(dev)
+    tile = None if (th, tw, ncls) == (8, 16, 1) else (th, tw, ncls)
+    got = _finalize_gpu(dev, tg, scs, inst, n, h, w, gamma, beta, slices, run, mstride, tile)
+    assert torch.equal(tg.cpu(), table), 'the table is read-only'
+    _cmp('D', name, got, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', SUMS_CASES, ids=lambda c: '-'.join(str(v) for v in c))
+def test_tnorm_sums_and_finalize_sums(dev, case):
+    from cat_amd import _lib as L, ops
+    n, h, w, th, tw, ncls, clamp, ranks = case
+    x, table, cnt, gamma, beta, run = _sums_inputs(case)
+    want = _sums_ref(case, torch.float64)
+    scs = SUMS_SCS
+    tg = table.to(dev)
+    sflat, sums = _sentinel((2, scs), dev, NAN)
+    L.call('cat_tnorm_sums', ops._p(tg), scs, n, h, w, th, tw, ncls, ops._p(sums), ops._stream())
+    torch.cuda.synchronize()
+    _tail(sflat, (case, 'sums'))
+    sc = sums.cpu()
+    owned = torch.zeros(scs, dtype=torch.bool)
+    for c0, c in SUMS_SLICES:
+        owned[c0:c0 + c] = True
+    assert bool((sc[:, ~owned] == 0.0).all())      # all-zero table columns fold to exact zeros
+    total = sums * float(ranks)      # the all-reduce over `ranks` equal ranks
+    sl = (L.NSlice * len(SUMS_SLICES))()
+    keep = []
+    for i, (c0, c) in enumerate(SUMS_SLICES):
+        keep.append((run[i][0].to(dev), run[i][1].to(dev), torch.full((1,), 3, dtype=torch.int64, device=dev)))
+        sl[i].c0, sl[i].c = c0, c
+        sl[i].running_mean, sl[i].running_var, sl[i].num_batches = (t.data_ptr() for t in keep[-1])
+    rows = {k: _sentinel((scs,), dev, NAN) for k in ('scale', 'shift', 'a', 'b')}
+    gg, bg = gamma.to(dev), beta.to(dev)
+    L.call('cat_tnorm_finalize_sums', ops._p(total), float(n * h * w * ncls * ranks), scs, ops._p(gg), ops._p(bg), len(SUMS_SLICES), sl,
+           EPS, MOM, clamp, ops._p(rows['scale'][1]), ops._p(rows['shift'][1]), ops._p(rows['a'][1]), ops._p(rows['b'][1]), ops._stream())
+    torch.cuda.synchronize()
+    got = {}
+    for key, (flat, row) in rows.items():
+        _tail(flat, (case, key))
+        assert bool((row.cpu()[~owned] == 0.0).all()), key
+    for i, (c0, c) in enumerate(SUMS_SLICES):
+        got.update({'sx%d' % i: sc[0, c0:c0 + c], 'sq%d' % i: sc[1, c0:c0 + c], 'rm%d' % i: keep[i][0].cpu(), 'rv%d' % i: keep[i][1].cpu()})
+        got.update({'%s%d' % (key, i): row.cpu()[c0:c0 + c] for key, (flat, row) in rows.items()})
+        assert int(keep[i][2].item()) == 4
+    _cmp('D', case, got, want)
+    # the constant channel: sum x^2 - sum x * mean is exactly 0 in float32 (0.5 and the counts are exact), so rstd is eps^-1/2 in both forms
+    assert abs(float(got['a1'][2]) - EPS ** -0.5) <= 1e-4 * EPS ** -0.5
+
+
+# ================================================================================================ E: depthwise stage
+def _dwm_geom(n, h, w, nq, xcs, ycs, scs, sstride, reflect, act, ks):
+    from cat_amd import _lib as L
+    g = L.DwmGeom()
+    g.N, g.H, g.W, g.nq, g.xcs, g.ycs, g.scs, g.sstride, g.reflect, g.act, g.slope = n, h, w, nq, xcs, ycs, scs, sstride, reflect, act, 0.2
+    for q, k in enumerate(ks):
+        g.ks[q] = k
+    return g
+
+
+def _w25(frame, dev):
+    """[C][5][5] -> the kernels' [25][C]"""
+    return frame.permute(1, 2, 0).reshape(25, -1).contiguous().to(dev)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', DWM_FWD_CASES, ids=lambda c: 'nq%d-plane%d-refl%d' % (c[0], c[1], c[3]))
+def test_dwm_fwd(dev, case):
+    from cat_amd import _lib as L, ops
+    nq, plane, rot, reflect, per_image, act, bias, stats, (xe, ye, se) = case
+    x, scale, shift, ws, b, ks = _dwf_inputs(case)
+    want = _dwf_ref(case, torch.float64)
+    n, c, h, w = x.shape
+    xcs, ycs, scs, sstride = c + xe, c + ye, c + se, (c + 4 if per_image else 0)
+    xg = _nhwc_buffer(x, xcs, dev)
+    rows = lambda v: F.pad(v, (0, 4), value=SENTINEL).to(dev) if per_image else v.reshape(-1).to(dev)
+    scg, shg = rows(scale), rows(shift)
+    g = _dwm_geom(n, h, w, nq, xcs, ycs, scs, sstride, reflect, act, ks)
+    tiles = n * cdiv(h, 8) * cdiv(w, 16)
+    yflat, y = _sentinel((n, h, w, ycs), dev)
+    tflat, tab = _sentinel((tiles, 2, scs), dev)
+    w25, bg = _w25(_frame(ws, ks), dev), (b.to(dev) if bias else None)
+    _, fam = _profiled(lambda: L.call('cat_dwm_fwd', C.byref(g), ops._p(xg), ops._p(scg), ops._p(shg), ops._p(w25), ops._p(bg), ops._p(y),
+                                      ops._p(tab) if stats else None, ops._stream()))
+    assert fam.get('dwconv_fwd', 0) == 1, fam
+    yc, tc = y.cpu(), tab.cpu()
+    _columns(yc, range(c), range(c), (case, 'y'))
+    _tail(yflat, (case, 'y'))
+    _tail(tflat, (case, 'table'))
+    got = {'y': _nchw(yc, 0, c)}
+    if stats:
+        _columns(tc, range(c), range(c), (case, 'table'))
+        got['sum'], got['m2'] = tc[:, 0, :c], tc[:, 1, :c]
+    else:
+        assert bool((tc == SENTINEL).all())
+    _cmp('E', case, got, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', DWM_BWD_CASES, ids=lambda c: 'nq%d-plane%d-refl%d' % c)
+def test_dwm_bwd(dev, case):
+    from cat_amd import _lib as L, ops
+    nq, plane, reflect = case
+    br = _dwb_branches(case)
+    a, dz, ws, prev = _dwb_inputs(case)
+    want = _dwb_ref(case, torch.float64)
+    n, c4, h, w = a.shape
+    acs, zcs, dacs = c4 + 4, c4 + 8, c4 + 12
+    ks = [k for c, k in br for _ in range(cs4(c) // 4)]
+    wpad = [F.pad(wt, (0, 0, 0, 0, 0, cs4(wt.shape[0]) - wt.shape[0])) for wt in ws]      # zero filters in a branch's padding channels
+    w25 = _w25(_frame(wpad, [k for c, k in br]), dev)
+    ag, zg = _nhwc_buffer(a, acs, dev), _nhwc_buffer(dz, zcs, dev)
+    g = _dwm_geom(n, h, w, nq, acs, zcs, 0, 0, reflect, 0, ks)
+    nb = len(br)
+    IA = C.c_int * nb
+    c0s, o = [], 0
+    for c, k in br:
+        c0s.append(o)
+        o += cs4(c)
+    nbytes = int(L.query('cat_dwm_bwd_ws_bytes', C.byref(g)))
+    assert nbytes == n * cdiv(h, 8) * cdiv(w, 16) * 25 * c4 * 4
+    got = {}
+    for accumulate in (0, 1):
+        dflat, da = _sentinel((n, h, w, dacs), dev)
+        wsflat, wsbuf = _sentinel((nbytes // 4,), dev, NAN)
+        dsts = [_sentinel((c * k * k,), dev, NAN) for c, k in br]
+        if accumulate:
+            for (flat, d), p in zip(dsts, prev):
+                d.copy_(p.reshape(-1))
+        _, fam = _profiled(lambda: L.call('cat_dwm_bwd', C.byref(g), ops._p(ag), ops._p(zg), ops._p(w25), ops._p(da), dacs, nb, IA(*c0s), IA(*[c for c, k in br]),
+                                          IA(*[k for c, k in br]), (C.c_void_p * nb)(*[d.data_ptr() for flat, d in dsts]), accumulate, ops._p(wsbuf),
+                                          ops._stream()))
+        assert fam.get('dwconv_bwd', 0) == 1, fam
+        dc = da.cpu()
+        _columns(dc, range(c4), range(c4), (case, 'da'))
+        _tail(dflat, (case, 'da'))
+        _tail(wsflat, (case, 'workspace'))
+        assert bool(torch.isfinite(wsbuf).all()), 'every partial of the workspace is written'
+        if not accumulate:
+            got['da'] = _nchw(dc, 0, c4)
+        else:
+            assert torch.equal(_nchw(dc, 0, c4), got['da']), 'accumulate only concerns the filter gradient'
+        for i, ((c, k), (flat, d)) in enumerate(zip(br, dsts)):
+            _tail(flat, (case, 'dw', i))
+            got[('dwacc%d' if accumulate else 'dw%d') % i] = d.cpu().view(c, k, k)
+    _cmp('E', case, got, want)
+
+
+# ================================================================================================ F: tconv instantiations
+@pytest.mark.gpu
+@pytest.mark.parametrize('key', sorted(TCONV_NT_CASES), ids=lambda k: 'nt%d-tw%d-stats%d' % k)
+def test_tconv_instantiation(dev, key):
+    from cat_amd import ops, tconv
+    cin, cout, k, reflect, n, h, w = TCONV_NT_CASES[key]
+    nt, tw, stats = key
+    assert tconv_launch(cout, n, h, w, stats)[::2] == (nt, tw)
+    x, wt, b = _tc_inputs(key)
+    want = _tc_ref(key, torch.float64)
+    xg = ops.to_nhwc(x.to(dev))
+    pack = tconv.pack(_padded_weight(wt, dev), FWD)
+    ycw, ycs = cs4(cout), cs4(cout) + 8
+    scs = ycw + 4
+    yflat, y = _sentinel((n, h, w, ycs), dev)
+    tiles = n * cdiv(h, 8) * cdiv(w, 16)
+    tflat, tab = _sentinel((tiles, 2, scs), dev)
+    seg = tconv.Segment(xg, k, k // 2, reflect and k > 1, 0)
+    bg = b.to(dev)
+
+    def call():
+        tconv.run([seg], pack, bg, None, cout, n, h, w, h, w, act=ACT_NONE if stats else ACT_LRELU, slope=0.2, ycs=ycs, ycw=ycw, yptr=y.data_ptr(),
+                  stats=tab if stats else None, scs=scs if stats else 0)
+    _, fam = _profiled(call)
+    assert fam.get('conv_tconv', 0) == 1, fam
+    yc, tc = y.cpu(), tab.cpu()
+    _columns(yc, range(ycw), range(cout), (key, 'y'))
+    _tail(yflat, (key, 'y'))
+    _tail(tflat, (key, 'table'))
+    got = {'y': _nchw(yc, 0, cout)}
+    if stats:
+        _columns(tc, range(ycw), range(cout), (key, 'table'))
+        got['sum'], got['m2'] = tc[:, 0, :cout], tc[:, 1, :cout]
+    else:
+        assert bool((tc == SENTINEL).all())
+    _cmp('F', key, got, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('nt', sorted(TCONV_MULTI_NN))
+def test_tconv_multi_segment_instantiation(dev, nt):
+    """K-concatenated segments (k = 1, 3, 5, 1) over channel slices of one hidden buffer, per-image staging affine + activation, bias,
+    LeakyReLU epilogue and a residual, at the N-tile counts the single-conv table of test_kernels_gpu.py does not reach"""
+    from cat_amd import ops, tconv
+    nn, reflect = TCONV_MULTI_NN[nt], nt != 6
+    n, h, w = MULTI_SHAPE
+    assert tconv_launch(nn, n, h, w, 0) == (nt, 1, 16)
+    hb, sc, sh, ws, b, res = _multi_inputs(nn)
+    want = _multi_ref(nn, reflect, torch.float64)
+    offs = np.cumsum([0] + [cs4(m) for m in MULTI_MS])
+    hc = int(offs[-1])
+    hbuf, scb, shb = torch.zeros(n, h, w, hc), torch.zeros(n, hc), torch.zeros(n, hc)
+    for i, m in enumerate(MULTI_MS):
+        o = int(offs[i])
+        hbuf[..., o:o + m], scb[:, o:o + m], shb[:, o:o + m] = hb[i].permute(0, 2, 3, 1), sc[i], sh[i]
+    hg, scg, shg = hbuf.to(dev), scb.to(dev), shb.to(dev)
+    packs = [tconv.pack(_padded_weight(wt, dev), FWD) for wt in ws]
+    segs, poff = [], 0
+    for i, (m, k) in enumerate(zip(MULTI_MS, MULTI_KS)):
+        o = int(offs[i])
+        segs.append(tconv.Segment(None, k, k // 2, reflect and k > 1, poff, c4=cs4(m), cin=m, xcs=hc, ptr=hg.data_ptr() + 4 * o,
+                                  scale=scg.data_ptr() + 4 * o, shift=shg.data_ptr() + 4 * o, act=MULTI_ACTS[i], slope=0.2, sstride=hc))
+        poff += packs[i].numel()
+    rg, bg, allpacks = ops.to_nhwc(res.to(dev)), b.to(dev), torch.cat(packs)
+    ycs = cs4(nn) + 4
+    yflat, y = _sentinel((n, h, w, ycs), dev)
+    _, fam = _profiled(lambda: tconv.run(segs, allpacks, bg, None, nn, n, h, w, h, w, act=ACT_LRELU, slope=0.2, ycs=ycs, ycw=cs4(nn),
+                                         yptr=y.data_ptr(), res=rg))
+    assert fam.get('conv_tconv_multi', 0) == 1, fam
+    yc = y.cpu()
+    _columns(yc, range(cs4(nn)), range(nn), (nt, 'y'))
+    _tail(yflat, (nt, 'y'))
+    _cmp('F', ('multi', nt), {'y': _nchw(yc, 0, nn)}, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', AFFINE_CASES, ids=lambda c: 'g%d-res%d-act%d-%dx%dx%dx%d' % (c[0], c[1], c[3], c[4], c[5], c[6], c[7]))
+def test_affine_res_fwd(dev, case):
+    from cat_amd import _lib as L, ops
+    per_image, has_res, (xe, re_, ye), act, n, h, w, c4 = case
+    x, sc, sh, res = _aff_inputs(case)
+    want = _aff_ref(case, torch.float64)
+    G = n if per_image else 1
+    xcs, rcs, ycs, sstride = c4 + xe, c4 + re_, c4 + ye, (c4 + 4 if per_image else 0)
+    xg = _nhwc_buffer(x, xcs, dev)
+    rg = _nhwc_buffer(res, rcs, dev) if has_res else None
+    rows = lambda v: F.pad(v, (0, 4), value=SENTINEL).to(dev) if per_image else v.reshape(-1).to(dev)
+    scg, shg = rows(sc), rows(sh)
+    yflat, y = _sentinel((n, h, w, ycs), dev)
+    _, fam = _profiled(lambda: L.call('cat_affine_res_fwd', ops._p(xg), xcs, ops._p(scg), ops._p(shg), sstride, ops._p(rg), rcs if has_res else 0, ops._p(y), ycs, G,
+                                      (n // G) * h * w, c4, act, 0.2, ops._stream()))
+    assert fam.get('affine_res', 0) == 1, fam
+    yc = y.cpu()
+    _columns(yc, range(c4), range(c4), (case, 'y'))
+    _tail(yflat, (case, 'y'))
+    _cmp('F', case, {'y': _nchw(yc, 0, c4)}, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', REFLECT_CASES, ids=lambda c: 'pad%d-add%d-%dx%dx%dx%d' % (c[0], c[1], c[3], c[4], c[5], c[6]))
+def test_reflect_pad_bwd2(dev, case):
+    from cat_amd import _lib as L, ops
+    pad, has_add, (pe, de, ae), n, h, w, c4 = case
+    dxp, add = _rp_inputs(case)
+    want = _rp_ref(case, torch.float64)
+    pcs, dcs, acs = c4 + pe, c4 + de, c4 + ae
+    pg = _nhwc_buffer(dxp, pcs, dev)
+    ag = _nhwc_buffer(add, acs, dev) if has_add else None
+    dflat, dx = _sentinel((n, h, w, dcs), dev)
+    L.call('cat_reflect_pad_bwd2', ops._p(pg), pcs, ops._p(dx), dcs, ops._p(ag), acs if has_add else 0, n, h, w, c4, pad, ops._stream())
+    torch.cuda.synchronize()
+    dc = dx.cpu()
+    _columns(dc, range(c4), range(c4), (case, 'dx'))
+    _tail(dflat, (case, 'dx'))
+    _cmp('F-reflect', case, {'dx': _nchw(dc, 0, c4)}, want, bar=1e-6)      # additions of at most ten terms
+
+
+# ------------------------------------------------------------------------------------------------ F: cat_prep_run
+def _stream_columns(stream, nt_total):
+    """a packed filter stream [group][N tile][lane quarter][16 columns][4] -> [column][everything else]"""
+    v = stream.view(-1, nt_total, 4, 16, 4)
+    return v.permute(1, 3, 0, 2, 4).reshape(nt_total * 16, -1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('mode', [FWD, DGRAD])
+def test_prep_kind0_is_the_tconv_pack_of_its_columns(dev, mode):
+    """two convs sharing an N tile of one stream: a kind-0 job writes exactly its own columns, bit-identical to cat_tconv_pack of the
+    N-concatenated weight (zero rows in the padding columns between the convs); the other conv's columns stay untouched"""
+    from cat_amd import tconv
+    ck, ks, ms, col0s, width = 23, 3, (7, 13), (0, 8), 24      # c4 = 24: c4 % 16 != 0
+    if mode == FWD:
+        ws = [detfill.normal((m, ck, ks, ks), 800 + i) for i, m in enumerate(ms)]
+        cat = torch.zeros((width, ck, ks, ks))
+        for wt, c0, m in zip(ws, col0s, ms):
+            cat[c0:c0 + m] = wt
+    else:
+        ws = [detfill.normal((ck, m, ks, ks), 810 + i) for i, m in enumerate(ms)]
+        cat = torch.zeros((ck, width, ks, ks))
+        for wt, c0, m in zip(ws, col0s, ms):
+            cat[:, c0:c0 + m] = wt
+    want = tconv.pack(_padded_weight(cat, dev), mode).cpu()
+    nt_total = cdiv(width, 16)
+    assert want.numel() == tconv.pack_floats(ks, cs4(ck), width)
+    wgs = [_padded_weight(wt, dev) for wt in ws]
+    flat, dst = _sentinel((want.numel(),), dev)
+    _prep_run([_pack_job(wgs[1], dst, mode, ks, nt_total, col0s[1])], dev)
+    got, ref = _stream_columns(dst.cpu(), nt_total), _stream_columns(want, nt_total)
+    mine = torch.zeros(width + 8, dtype=torch.bool)[:nt_total * 16]
+    mine[col0s[1]:col0s[1] + ms[1]] = True
+    assert torch.equal(got[mine], ref[mine])
+    assert bool((got[~mine] == SENTINEL).all()), 'columns of the other conv and the padding columns are not written'
+    _tail(flat, 'stream')
+    both = _concat_pack(list(zip(wgs, col0s)), mode, ks, ck, width, dev)
+    assert torch.equal(both.cpu(), want)
+
+
+@pytest.mark.gpu
+def test_prep_run_all_job_kinds(dev):
+    """one table with jobs of all five kinds, run with accumulate 0 and then 1 (kinds 0 - 2 overwrite in both)"""
+    from cat_amd import tconv
+    wt = detfill.normal((13, 9, 3, 3), 820)
+    wg = _padded_weight(wt, dev)
+    want0 = tconv.pack(wg, FWD).cpu()
+    v = [detfill.normal((37,), 821 + i) for i in range(3)]
+    vg = [t.to(dev) for t in v]
+    dwt = detfill.normal((6, 3, 3), 825)      # a 3 x 3 depthwise filter into columns [4, 10) of a 12-wide frame
+    src3, src4 = detfill.normal((300,), 826), detfill.normal((5, 12), 827)
+    dwg, s3g, s4g = dwt.to(dev), src3.to(dev), src4.to(dev)
+    # kind 0 goes into a zeroed stream, as the plans allocate it: the padding columns of the last N tile are never written
+    bufs = {0: _sentinel((want0.numel(),), dev, 0.0), 1: _sentinel((37,), dev, NAN), 2: _sentinel((25, 12), dev), 3: _sentinel((300,), dev, NAN),
+            4: _sentinel((5, 16), dev)}
+    bufs[4][1][:, :7] = NAN
+    jobs = [
+        _pack_job(wg, bufs[0][1], FWD, 3, 1, 0),
+        dict(kind=1, srcs=[t.data_ptr() for t in vg], nsrc=3, dst=bufs[1][1].data_ptr(), n=37, threads=37),
+        dict(kind=2, srcs=[dwg.data_ptr()], dst=bufs[2][1].data_ptr(), Nn=6, ks=3, col0=4, cs=12, threads=6 * 9),
+        dict(kind=3, srcs=[s3g.data_ptr(), bufs[3][1].data_ptr()], nsrc=2, n=300, threads=300),
+        dict(kind=4, srcs=[s4g.data_ptr(), bufs[4][1].data_ptr()], nsrc=2, n=5 * 7, cs=7, wn=12, wcs=16, threads=5 * 7),
+    ]
+    frame = np.full((5, 5, 12), SENTINEL, dtype=np.float32)
+    frame[1:4, 1:4, 4:10] = dwt.numpy().transpose(1, 2, 0)
+    scat = np.full((5, 16), SENTINEL, dtype=np.float32)
+    for accumulate in (0, 1):
+        _prep_run(jobs, dev, accumulate)
+        for flat, _ in bufs.values():
+            _tail(flat, accumulate)
+        mul = np.float32(accumulate + 1)
+        assert torch.equal(bufs[0][1].cpu(), want0)
+        assert np.array_equal(bufs[1][1].cpu().numpy(), (v[0].numpy() + v[1].numpy()) + v[2].numpy())
+        assert np.array_equal(bufs[2][1].cpu().numpy().reshape(5, 5, 12), frame)
+        assert np.array_equal(bufs[3][1].cpu().numpy(), src3.numpy() * mul)
+        scat[:, :7] = src4.numpy()[:, :7] * mul
+        assert np.array_equal(bufs[4][1].cpu().numpy(), scat), 'the 2-D scatter stays inside its rows'
+
+
+@pytest.mark.gpu
+def test_plan_packs_are_the_tconv_pack_of_the_concatenated_weights(dev):
+    """a real fused_block._Plan after prepare(): every stage-1 group's filter stream is bit-identical to cat_tconv_pack of the N-concatenated
+    first-conv weights with zero rows in the padding columns between the branches"""
+    from cat_amd import fused_block, tconv
+    from test_fused_block_gpu import _block
+    blk = _block('batch', dev)
+    plan = fused_block._Plan(blk, dev)
+    plan.prepare()
+    torch.cuda.synchronize()
+    assert sorted(g['k'] for g in plan.groups) == [1, 3, 5]
+    for g in plan.groups:
+        cat = torch.zeros((g['width'], plan.C, g['k'], g['k']))
+        for b in g['branches']:
+            cat[b['o1'] - g['off']:b['o1'] - g['off'] + b['m']] = b['conv1'].weight.detach().cpu()
+        want = tconv.pack(_padded_weight(cat, dev), FWD)
+        assert torch.equal(g['pack'].cpu(), want.cpu()), g['k']
+
+
+# ------------------------------------------------------------------------------------------------ F: refusals before any launch
+@pytest.mark.gpu
+@pytest.mark.parametrize('w5,w3,w1', [(40, 12, 32), (16, 16, 80), (16, 36, 32)])
+def test_stage1_fwd_refuses_widths_without_a_kernel(dev, w5, w3, w1):
+    from cat_amd import _lib as L, ops, tconv
+    assert not s1_supported(w5, w3, w1) and L.query('cat_tstage1_supported', w5, w3, w1) == 0
+    n, h, w, cin = 1, 8, 16, 8
+    ycs = w5 + w3 + w1
+    xg = torch.zeros((n, h, w, cin), device=dev)
+    pk = (C.c_void_p * 3)()
+    packs = [torch.zeros(tconv.pack_floats(k, cin, wd), device=dev) for k, wd in ((5, w5), (3, w3), (1, w1))]
+    gs = L.Stage1Geom()
+    gs.N, gs.H, gs.W, gs.xcs, gs.cin, gs.reflect, gs.ycs, gs.scs = n, h, w, cin, cin, 0, ycs, ycs
+    for slot, (c0, wd) in enumerate(((w1 + w3, w5), (w1, w3), (0, w1))):
+        gs.col0[slot], gs.width[slot], gs.nvalid[slot] = c0, wd, wd
+        pk[slot] = packs[slot].data_ptr()
+    zflat, z = _sentinel((n, h, w, ycs), dev)
+    tflat, tab = _sentinel((n, 2, ycs), dev)
+    with pytest.raises(RuntimeError, match='tstage1'):
+        L.call('cat_tstage1_fwd', C.byref(gs), ops._p(xg), pk, None, ops._p(z), ops._p(tab), ops._stream())
+    torch.cuda.synchronize()
+    assert bool((zflat == SENTINEL).all()) and bool((tflat == SENTINEL).all())
+
+
+@pytest.mark.gpu
+def test_dwm_refuses_more_quads_than_its_kernels_hold(dev):
+    from cat_amd import _lib as L, ops
+    assert (L.DWM_MAXQ, L.DWM_MAXQ_BWD) == (24, 18)
+    n, h, w = 1, 8, 16
+    for entry, nq in (('fwd', 25), ('bwd', 19)):
+        c = 4 * nq
+        ks = [3] * min(nq, L.DWM_MAXQ)
+        g = _dwm_geom(n, h, w, nq, c, c, c, 0, 0, 0, ks)
+        xg, zg, w25 = torch.zeros((n, h, w, c), device=dev), torch.zeros((n, h, w, c), device=dev), torch.zeros((25, c), device=dev)
+        one = torch.ones(c, device=dev)
+        yflat, y = _sentinel((n, h, w, c), dev)
+        tflat, tab = _sentinel((c * 9,), dev)
+        wsb = torch.zeros(25 * c, device=dev)
+        with pytest.raises(RuntimeError, match='dwm'):
+            if entry == 'fwd':
+                L.call('cat_dwm_fwd', C.byref(g), ops._p(xg), ops._p(one), ops._p(one), ops._p(w25), None, ops._p(y), ops._p(tab), ops._stream())
+            else:
+                L.call('cat_dwm_bwd', C.byref(g), ops._p(xg), ops._p(zg), ops._p(w25), ops._p(y), c, 1, (C.c_int * 1)(0), (C.c_int * 1)(c), (C.c_int * 1)(3),
+                       (C.c_void_p * 1)(tab.data_ptr()), 0, ops._p(wsb), ops._stream())
+        torch.cuda.synchronize()
+        assert bool((yflat == SENTINEL).all()) and bool((tflat == SENTINEL).all())
