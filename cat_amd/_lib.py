@@ -138,6 +138,9 @@ SIGNATURES = {
     'cat_pool2d_fwd': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p]),
     'cat_global_avgpool_fwd': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p]),
     'cat_resize_bilinear_fwd': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_f, c_f, c_p]),
+    'cat_conv2d_fwd_ex': (c_i, [_G, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    'cat_seg_up_logsoftmax': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_p]),
+    'cat_seg_confusion': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     'cat_conv2d_fwd_ws': (c_i, [_G, c_p, c_p, c_p, c_p, c_p, c_p]),
     'cat_conv2d_dgrad_ws_bytes': (C.c_size_t, [_G, c_i]),
     'cat_conv2d_dgrad_ws': (c_i, [_G, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),

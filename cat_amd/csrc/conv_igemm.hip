@@ -50,6 +50,10 @@ struct IgemmArgs {
   float* part;
   const float* bt;  // dgrad: filters transposed to [Cin][taps][Cout] (cat_conv2d_dgrad_t), or null
   long long* dbg;  // diagnostic build only (cat::kDiag, CAT_DBG): per-phase shader-clock totals of one wave
+  // cat_conv2d_fwd_ex only (the EX instantiations of the forward kernels; the others never read these)
+  int dil;           // filter dilation: tap (ky, kx) reads input pixel (oy * stride - pad + ky * dil, ...)
+  const float* res;  // optional residual, added BEFORE the activation: res[m * rcs + col]
+  int rcs;
 };
 
 __device__ __forceinline__ int swz(int r, int q) { return (r * 4 + (q ^ ((r >> 1) & 3))) * 4; }
@@ -184,7 +188,7 @@ __device__ __forceinline__ void dma_chunk(__amdgpu_buffer_rsrc_t rA, __amdgpu_bu
 
 // Row-major accumulators (lane (lr, lq) holds rows i * 16 + lq * 4 + 0..3 of column j * 16 + lr) of the forward kernels:
 // out[m][col] = act(acc + bias[col]) for col < Cout, zeros for Cout <= col < cw.  m0 / n0 = first row / column of the WAVE tile.
-template <int MT, int NT>
+template <int MT, int NT, bool EX = false>
 __device__ __forceinline__ void store_rows(const IgemmArgs& p, const f4 (&acc)[MT][NT], int m0, int n0, int lane) {
   const int lr = lane & 15, lq = lane >> 4;
 #pragma unroll
@@ -198,7 +202,11 @@ __device__ __forceinline__ void store_rows(const IgemmArgs& p, const f4 (&acc)[M
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) {
         const int m = m0 + i * 16 + lq * 4 + rg;
-        if (m < p.M) p.out[(int64_t)m * p.ycs + col] = cvalid ? cat::apply_act(acc[i][j][rg] + bias, p.act, p.slope) : 0.f;
+        if (m < p.M) {
+          float v = acc[i][j][rg] + bias;
+          if (EX && cvalid && p.res) v += p.res[(int64_t)m * p.rcs + col];
+          p.out[(int64_t)m * p.ycs + col] = cvalid ? cat::apply_act(v, p.act, p.slope) : 0.f;
+        }
       }
     }
   }
@@ -207,8 +215,10 @@ __device__ __forceinline__ void store_rows(const IgemmArgs& p, const f4 (&acc)[M
 // Transposed accumulators (mfma_block<true>): lane (lr, lq) holds channels j * 16 + lq * 4 + 0..3 of tile row (pixel) i * 16 + lr -- one
 // pixel address and one float4 store per tile instead of four of each (round 6: -3.7 % on a 256 -> 256 3x3 forward).
 // orow = the pixel of tile row i, c0 = first channel of the wave tile + lq * 4, C = valid channels; zeros for C <= c < cw.
-template <int MT, int NT>
-__device__ __forceinline__ void store_pixel_t(const IgemmArgs& p, float* orow, const f4 (&acc)[MT][NT], int i, int c0, int C, bool vec) {
+// rrow (EX only) = the same pixel of the residual, or null.
+template <int MT, int NT, bool EX = false>
+__device__ __forceinline__ void store_pixel_t(const IgemmArgs& p, float* orow, const f4 (&acc)[MT][NT], int i, int c0, int C, bool vec,
+                                              const float* rrow = nullptr) {
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     const int cj = c0 + j * 16;
@@ -216,14 +226,23 @@ __device__ __forceinline__ void store_pixel_t(const IgemmArgs& p, float* orow, c
     if (vec && cj + 3 < C) {
       f4 v = acc[i][j];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = cat::apply_act(v[e] + (p.bias ? p.bias[cj + e] : 0.f), p.act, p.slope);
+      for (int e = 0; e < 4; ++e) {
+        float t = v[e] + (p.bias ? p.bias[cj + e] : 0.f);
+        if (EX && rrow) t += rrow[cj + e];
+        v[e] = cat::apply_act(t, p.act, p.slope);
+      }
       *reinterpret_cast<f4*>(orow + cj) = v;
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int c = cj + e;
-        if (c < C) orow[c] = cat::apply_act(acc[i][j][e] + (p.bias ? p.bias[c] : 0.f), p.act, p.slope);
-        else if (c < p.cw) orow[c] = 0.f;
+        if (c < C) {
+          float t = acc[i][j][e] + (p.bias ? p.bias[c] : 0.f);
+          if (EX && rrow) t += rrow[c];
+          orow[c] = cat::apply_act(t, p.act, p.slope);
+        } else if (c < p.cw) {
+          orow[c] = 0.f;
+        }
       }
     }
   }
@@ -269,7 +288,8 @@ __device__ __forceinline__ void store_dw(const IgemmArgs& p, int co, int k, int 
 }
 
 // ------------------------------------------------------------------------------------------------ forward
-template <int MT, int NT, int WM, int WN, bool WVEC = false, int SCHED = 0>
+// EX (cat_conv2d_fwd_ex): taps `dil` pixels apart and a residual in the epilogue; EX = false compiles to the code it was before
+template <int MT, int NT, int WM, int WN, bool WVEC = false, int SCHED = 0, bool EX = false>
 __global__ __launch_bounds__(256) void conv_fwd_kernel(IgemmArgs p) {
   constexpr int BM = WM * MT * 16, BN = WN * NT * 16;
   constexpr int AI = BM / 64, BI = (BN + 63) / 64;
@@ -284,6 +304,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(IgemmArgs p) {
   const int q = tid & 3, r0 = tid >> 2;
   const int HoWo = p.Ho * p.Wo;
   const int taps = p.kh * p.kw;
+  const int dil = EX ? p.dil : 1;
 
   int iy0[AI], ix0[AI];
   int64_t xoff[AI];
@@ -324,7 +345,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(IgemmArgs p) {
   auto locate = [&]() {
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
-      int iy = iy0[i] + ky, ix = ix0[i] + kx;
+      int iy = iy0[i] + ky * dil, ix = ix0[i] + kx * dil;
       const bool inr = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
       const int ry = cat::reflect_idx(iy, p.H), rx = cat::reflect_idx(ix, p.W);
       iy = p.reflect ? ry : (inr ? iy : 0);
@@ -423,7 +444,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(IgemmArgs p) {
   if (dbg) { p.dbg[0] = t_load; p.dbg[1] = t_mma; p.dbg[2] = t_store; p.dbg[3] = t_bar; p.dbg[4] = nk - 1; }
   mma_kcontig_a_kcontig_b<MT, NT>(sA + ((nk - 1) & 1) * BM * 16, sB + ((nk - 1) & 1) * BN * 16, wm * MT * 16, wn * NT * 16, lane, acc);
 
-  store_rows(p, acc, m0 + wm * MT * 16, n0 + wn * NT * 16, lane);
+  store_rows<MT, NT, EX>(p, acc, m0 + wm * MT * 16, n0 + wn * NT * 16, lane);
 }
 
 // ------------------------------------------------------------------------------------------------ forward, BK = 32
@@ -432,7 +453,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(IgemmArgs p) {
 // multiple of 32 (so a chunk never straddles taps and the walk is wave-uniform) and the filter rows are float4-readable.
 // Invalid rows / padding taps keep their pointer parked on the zero page (increment 0), so the steady state is one 64-bit add per
 // load and nothing else on the vector ALU.
-template <int MT, int NT, int WM, int WN>
+template <int MT, int NT, int WM, int WN, bool EX = false>
 __global__ __launch_bounds__(256) void conv_fwd32_kernel(IgemmArgs p) {
   constexpr int BM = WM * MT * 16, BN = WN * NT * 16;
   constexpr int AI = BM / 32, BI = (BN + 31) / 32;
@@ -450,6 +471,7 @@ __global__ __launch_bounds__(256) void conv_fwd32_kernel(IgemmArgs p) {
   const int q4 = tid & 3, q = half * 4 + q4, r0 = (tid & 127) >> 2;
   const int HoWo = p.Ho * p.Wo;
   const int taps = p.kh * p.kw;
+  const int dil = EX ? p.dil : 1;
 
   int iy0[AI], ix0[AI];
   int64_t xoff[AI];
@@ -481,7 +503,7 @@ __global__ __launch_bounds__(256) void conv_fwd32_kernel(IgemmArgs p) {
     const bool cv = ci < p.cval && tap < taps;
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
-      int iy = iy0[i] + ky, ix = ix0[i] + kx;
+      int iy = iy0[i] + ky * dil, ix = ix0[i] + kx * dil;
       const bool inr = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
       const int ry = cat::reflect_idx(iy, p.H), rx = cat::reflect_idx(ix, p.W);
       iy = p.reflect ? ry : (inr ? iy : 0);
@@ -582,7 +604,7 @@ __global__ __launch_bounds__(256) void conv_fwd32_kernel(IgemmArgs p) {
     }
     return;
   }
-  store_rows(p, acc, m0 + wm * MT * 16, n0 + wn * NT * 16, lane);
+  store_rows<MT, NT, EX>(p, acc, m0 + wm * MT * 16, n0 + wn * NT * 16, lane);
 }
 
 // ------------------------------------------------------------------------------------------------ forward, BK = 32, direct-to-LDS staging
@@ -595,8 +617,10 @@ __global__ __launch_bounds__(256) void conv_fwd32_kernel(IgemmArgs p) {
 // Out-of-image / padding / tail lanes carry voffset 0x80000000: beyond num_records, the buffer unit returns zeros.
 // Preconditions (host): Cin % 32 == 0 (a 32-chunk never straddles taps), float4-readable filters, tensors < 2 GB.
 // 2 x 2 waves of 4 x 4 MFMA tiles.
+template <bool EX = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_fwd32d_kernel(IgemmArgs p) {
   constexpr int MT = 4, NT = 4, WN = 2, BM = 128, BN = 128;
+  const int dil = EX ? p.dil : 1;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* sA = smem;
   float* sB = smem + 2 * BM * 32;
@@ -630,7 +654,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   auto locate = [&](int ky, int kx) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      int iy = iy0[i] + ky, ix = ix0[i] + kx;
+      int iy = iy0[i] + ky * dil, ix = ix0[i] + kx * dil;
       const bool inr = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
       const int ry = cat::reflect_idx(iy, p.H), rx = cat::reflect_idx(ix, p.W);
       iy = p.reflect ? ry : (inr ? iy : 0);
@@ -677,7 +701,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   for (int i = 0; i < MT; ++i) {
     const int m = m0 + wm * MT * 16 + i * 16 + lr;
     if (m >= p.M) continue;
-    store_pixel_t(p, p.out + (int64_t)m * p.ycs, acc, i, n0 + wn * NT * 16 + lq * 4, p.Cout, vec);
+    store_pixel_t<MT, NT, EX>(p, p.out + (int64_t)m * p.ycs, acc, i, n0 + wn * NT * 16 + lq * 4, p.Cout, vec,
+                              (EX && p.res) ? p.res + (int64_t)m * p.rcs : nullptr);
   }
 }
 
@@ -1667,13 +1692,14 @@ static void zero_lanes_past_c4(float* out, int64_t P, int C, int cw, int cs, hip
 // the direct-to-LDS kernels address a tensor with 32-bit byte offsets
 static bool fits_2gb(int64_t floats) { return floats * 4 < (int64_t)2147483647; }
 
-int fill_common(IgemmArgs& a, const cat_conv_t* g, int pad_w = -1) {
+int fill_common(IgemmArgs& a, const cat_conv_t* g, int pad_w = -1, int dil = 1) {
   const int padw = pad_w >= 0 ? pad_w : g->pad;
   CAT_REQUIRE(g->N > 0 && g->H > 0 && g->W > 0 && g->Cin > 0 && g->Cout > 0, "conv: empty geometry");
   CAT_REQUIRE(g->stride == 1 || g->stride == 2, "conv: stride %d unsupported", g->stride);
   CAT_REQUIRE(g->xcs % 4 == 0 && g->ycs % 4 == 0, "conv: pixel strides must be multiples of 4 (xcs=%d ycs=%d)", g->xcs, g->ycs);
   CAT_REQUIRE(g->xcs >= ((g->Cin + 3) & ~3) && g->ycs >= ((g->Cout + 3) & ~3), "conv: pixel stride smaller than padded channel count");
-  CAT_REQUIRE(g->Ho == (g->H + 2 * g->pad - g->kh) / g->stride + 1 && g->Wo == (g->W + 2 * padw - g->kw) / g->stride + 1,
+  const int eh = dil * (g->kh - 1) + 1, ew = dil * (g->kw - 1) + 1;   // filter extent (== kh, kw without dilation)
+  CAT_REQUIRE(g->Ho == (g->H + 2 * g->pad - eh) / g->stride + 1 && g->Wo == (g->W + 2 * padw - ew) / g->stride + 1,
               "conv: output size (%d,%d) inconsistent with geometry", g->Ho, g->Wo);
   CAT_REQUIRE(g->pad_mode == CAT_PAD_ZERO || (g->pad < g->H && padw < g->W), "conv: reflect pad must be < input size");
   a.N = g->N; a.H = g->H; a.W = g->W; a.Cin = g->Cin; a.xcs = g->xcs;
@@ -1684,6 +1710,7 @@ int fill_common(IgemmArgs& a, const cat_conv_t* g, int pad_w = -1) {
   CAT_REQUIRE(a.wcs >= g->Cin, "conv: wcs < Cin");
   a.wvec = (a.wcs % 4) == 0;
   a.M = g->N * g->Ho * g->Wo;
+  a.dil = dil;
   return 0;
 }
 
@@ -1735,8 +1762,8 @@ static bool fwd_bk32_ok(const IgemmArgs& a) {
   return a.wvec && (a.c4 & 15) == 0 && !dbg_on;
 }
 
-static int fwd_setup(IgemmArgs& a, const cat_conv_t* g, int pad_w = -1) {
-  if (int e = fill_common(a, g, pad_w)) return e;
+static int fwd_setup(IgemmArgs& a, const cat_conv_t* g, int pad_w = -1, int dil = 1) {
+  if (int e = fill_common(a, g, pad_w, dil)) return e;
   a.cval = (g->Cin + 3) & ~3;
   a.c4 = walk_extent(a.cval);
   a.K = g->kh * g->kw * a.c4;
@@ -1755,8 +1782,9 @@ size_t cat_conv2d_fwd_ws_bytes(const cat_conv_t* g) {
   return sp.ksplit > 1 ? (size_t)sp.ksplit * a.M * g->ycs * sizeof(float) : 0;
 }
 
+struct FwdEx { int dil; const float* res; int rcs; };   // cat_conv2d_fwd_ex: dilation + residual epilogue (the EX kernel instantiations)
 static int conv_fwd_impl(const cat_conv_t* g, const float* x, const float* w, const float* bias, float* y, void* ws, cat_stream_t stream,
-                         int pad_w = -1);
+                         int pad_w = -1, const FwdEx* ex = nullptr);
 
 int cat_conv2d_fwd(const cat_conv_t* g, const float* x, const float* w, const float* bias, float* y, cat_stream_t stream) {
   return conv_fwd_impl(g, x, w, bias, y, nullptr, stream);
@@ -1774,17 +1802,33 @@ int cat_conv2d_fwd_rect(const cat_conv_t* g, int pad_w, const float* x, const fl
   return conv_fwd_impl(g, x, w, bias, y, nullptr, stream, pad_w);
 }
 
+// y = act(conv_dilated(x, w) + bias + res): the layers of the dilated residual network behind the cityscapes mIoU (metric/drn.py:78-125,
+// 163-202) -- 3 x 3 filters with taps 2 / 4 pixels apart, and the last 1 x 1 of a bottleneck, whose shortcut is added BEFORE the ReLU
+// (:116-123).  The tap geometry is computed once per tap in the kernels' locate(), so dilation costs nothing per MFMA.  Zero padding,
+// forward / inference only.  dilation == 1 && res == NULL is cat_conv2d_fwd itself (same dispatch, same bits).
+int cat_conv2d_fwd_ex(const cat_conv_t* g, int dilation, const float* x, const float* w, const float* bias, const float* res, int rcs,
+                      float* y, cat_stream_t stream) {
+  CAT_REQUIRE(dilation >= 1 && dilation <= 64, "conv fwd ex: dilation %d", dilation);
+  CAT_REQUIRE(g->pad_mode == CAT_PAD_ZERO, "conv fwd ex: zero padding only");
+  CAT_REQUIRE(dilation == 1 || g->stride == 1, "conv fwd ex: dilation > 1 needs stride 1");
+  CAT_REQUIRE(!res || rcs >= g->Cout, "conv fwd ex: residual pixel stride %d < Cout", rcs);
+  if (dilation == 1 && !res) return conv_fwd_impl(g, x, w, bias, y, nullptr, stream);
+  const FwdEx ex{dilation, res, rcs};
+  return conv_fwd_impl(g, x, w, bias, y, nullptr, stream, -1, &ex);
+}
+
 static int conv_fwd_impl(const cat_conv_t* g, const float* x, const float* w, const float* bias, float* y, void* ws, cat_stream_t stream,
-                         int pad_w) {
+                         int pad_w, const FwdEx* ex) {
   IgemmArgs a{};
-  if (int e = fwd_setup(a, g, pad_w)) return e;
+  if (int e = fwd_setup(a, g, pad_w, ex ? ex->dil : 1)) return e;
+  if (ex) { a.res = ex->res; a.rcs = ex->rcs; }
   const bool rect = pad_w >= 0 && pad_w != g->pad;
   a.a = x; a.b = w; a.bias = bias; a.out = y;
   a.cw = g->ycw > g->Cout ? g->ycw : g->Cout;
   CAT_REQUIRE(a.cw <= g->ycs, "conv fwd: ycw > ycs");
   hipStream_t s = (hipStream_t)stream;
   zero_lanes_past_c4(y, a.M, a.Cout, a.cw, a.ycs, s);
-  if (!rect && cat::smallco_applicable(g)) {
+  if (!rect && !ex && cat::smallco_applicable(g)) {
     cat::ProfScope prof("conv_fwd_smallco", 2.0 * (double)g->N * g->Ho * g->Wo * g->Cout * g->kh * g->kw * g->Cin, 0.0, stream);
     const int ks = ws ? cat::smallco_fwd_ksplit(g) : 1;
     if (int e = cat::smallco_fwd(g, x, w, bias, y, (float*)ws, ks, s)) return e;
@@ -1809,7 +1853,10 @@ static int conv_fwd_impl(const cat_conv_t* g, const float* x, const float* w, co
   {                                                                                        \
     cat::ProfScope prof("conv_fwd_" #MT "x" #NT "x" #WM "x" #WN, prof_flops, 0.0, stream); \
     const int grid = cdiv(a.M, WM * MT * 16) * cdiv(a.Cout, WN * NT * 16);                 \
-    if (!a.wvec) conv_fwd_kernel<MT, NT, WM, WN, false, 0><<<grid, 256, 0, s>>>(a);         \
+    /* the EX launches take neither the CAT_SCHED variants nor the CAT_LDS_PAD occupancy cap: those diagnostics cover the plain kernels only */ \
+    if (ex && !a.wvec) conv_fwd_kernel<MT, NT, WM, WN, false, 0, true><<<grid, 256, 0, s>>>(a); \
+    else if (ex) conv_fwd_kernel<MT, NT, WM, WN, true, 0, true><<<grid, 256, 0, s>>>(a);    \
+    else if (!a.wvec) conv_fwd_kernel<MT, NT, WM, WN, false, 0><<<grid, 256, 0, s>>>(a);    \
     else if (WN == 2 && sched) launch_fwd_sched<cat::kDiag>(sched, grid, a, s);             \
     else conv_fwd_kernel<MT, NT, WM, WN, true, 0><<<grid, 256, lds_pad, s>>>(a);            \
   }
@@ -1828,9 +1875,14 @@ static int conv_fwd_impl(const cat_conv_t* g, const float* x, const float* w, co
                         stream);                                                                      \
     const dim3 grid(cdiv(a.M, WM * MT * 16) * cdiv(a.Cout, WN * NT * 16), a.ksplit);                   \
     const size_t lds = (size_t)2 * (WM * MT * 16 + WN * NT * 16) * 32 * sizeof(float);                \
-    static cat::LdsOptIn optin;                                                                       \
-    cat::lds_optin(optin, (const void*)conv_fwd32_kernel<MT, NT, WM, WN>, (int)lds);                  \
-    conv_fwd32_kernel<MT, NT, WM, WN><<<grid, 256, lds, s>>>(a);                                       \
+    static cat::LdsOptIn optin, optin_ex;                                                             \
+    if (ex) {                                                                                         \
+      cat::lds_optin(optin_ex, (const void*)conv_fwd32_kernel<MT, NT, WM, WN, true>, (int)lds);       \
+      conv_fwd32_kernel<MT, NT, WM, WN, true><<<grid, 256, lds, s>>>(a);                               \
+    } else {                                                                                          \
+      cat::lds_optin(optin, (const void*)conv_fwd32_kernel<MT, NT, WM, WN>, (int)lds);                \
+      conv_fwd32_kernel<MT, NT, WM, WN><<<grid, 256, lds, s>>>(a);                                     \
+    }                                                                                                 \
     if (a.ksplit > 1) launch_splitk_reduce(a.part, a.bias, a.out, a.M, a.Cout, a.cw, a.ycs, a.ksplit, a.act, a.slope, s);   \
   }
   // direct-to-LDS variant of the 128 x 128 tile: Cin % 32 == 0 (a chunk never straddles taps), no K split, 32-bit byte offsets
@@ -1840,9 +1892,14 @@ static int conv_fwd_impl(const cat_conv_t* g, const float* x, const float* w, co
     cat::ProfScope prof("conv_fwd32d_4x4x2x2", prof_flops, 0.0, stream);
     const int grid = cdiv(a.M, 128) * cdiv(a.Cout, 128);
     const size_t lds = (size_t)2 * (128 + 128) * 32 * sizeof(float);
-    static cat::LdsOptIn optin;
-    cat::lds_optin(optin, (const void*)conv_fwd32d_kernel, (int)lds);
-    conv_fwd32d_kernel<<<grid, 256, lds, s>>>(a);
+    static cat::LdsOptIn optin, optin_ex;
+    if (ex) {
+      cat::lds_optin(optin_ex, (const void*)conv_fwd32d_kernel<true>, (int)lds);
+      conv_fwd32d_kernel<true><<<grid, 256, lds, s>>>(a);
+    } else {
+      cat::lds_optin(optin, (const void*)conv_fwd32d_kernel<false>, (int)lds);
+      conv_fwd32d_kernel<false><<<grid, 256, lds, s>>>(a);
+    }
     return cat::check_launch("conv2d_fwd");
   }
   const bool smallm = use_small_m(a.M, a.Cout);

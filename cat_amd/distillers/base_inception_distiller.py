@@ -1,7 +1,7 @@
 """BaseInceptionDistiller: the attribute / method surface Trainer and shrink() rely on, following
-distillers/base_inception_distiller.py:103-312 for everything on the hot path.  Dataset loaders, FID / mIoU models
-and checkpoint directories of the reference constructor are host-side I/O that stays with CAT:
-they are only touched when `opt` carries the corresponding paths."""
+distillers/base_inception_distiller.py:103-312 for everything on the hot path.  Dataset loaders and checkpoint directories of the
+reference constructor are host-side I/O that stays with CAT: they are only touched when `opt` carries the corresponding
+paths.  The FID / mIoU networks run on the HIP kernels and are attached with evaluation.attach_fid / attach_miou."""
 import itertools
 import os
 from collections import OrderedDict
@@ -377,8 +377,8 @@ class BaseInceptionDistiller:
 
     def evaluate_model(self, step, save_image=False):
         """reference inception_distiller.py:204-281: student (and teacher) inference over `self.eval_dataloader` on the HIP kernels, image
-        dumps, `is_best` / running-mean bookkeeping; the FID / mIoU networks themselves are the integrator's callables
-        `self.fid_fn(fakes)`, `self.miou_fn(fakes, names)` (cat_amd/distillers/evaluation.py, INTEGRATION.md)."""
+        dumps, `is_best` / running-mean bookkeeping; the FID / mIoU networks are cat_amd.metric's (evaluation.attach_fid / attach_miou),
+        or the integrator's callables `self.fid_fn(fakes)`, `self.miou_fn(fakes, names)` (cat_amd/distillers/evaluation.py)."""
         from . import evaluation as E
         self.finish_pending()
         aligned = self.opt.dataset_mode == 'aligned'

@@ -208,8 +208,8 @@ class BaseSPADEDistiller:
             torch.save(optimizer.state_dict(), os.path.join(self.save_dir, '%s_optim-%d.pth' % (epoch, i)))
 
     def evaluate_model(self, step, save_image=False):
-        """reference spade_distiller.py:96-180: see cat_amd/distillers/evaluation.py (generator passes here, metric networks attached by
-        the integrator as `self.fid_fn`, `self.miou_fn`)."""
+        """reference spade_distiller.py:96-180: see cat_amd/distillers/evaluation.py (generator passes here, metric networks attached with
+        evaluation.attach_fid / attach_miou, or by the integrator as `self.fid_fn`, `self.miou_fn`)."""
         from . import evaluation as E
 
         def images(j):

@@ -8,12 +8,16 @@ FID (round 5): the InceptionV3 pool3 feature extractor runs on the HIP kernels t
 reference metric/inception.py, metric/fid_score.py:152-216, metric/__init__.py:11-21).  `attach_fid(model, checkpoint, real_stat_path)`
 builds it exactly as the reference's __init__ does (base_inception_distiller.py:218-234: `InceptionV3([block_idx])`, `np.load(real_stat_path)`)
 from the torchvision-keyed FID checkpoint the reference downloads; a model that carries `inception_model` + `npz` needs no `fid_fn`.
-The mIoU network (DRN + cityscapes data) stays with the reference: the integrator attaches
+mIoU: the cityscapes segmentation network (DRN-D-105 + head) and the resize / argmax / confusion-matrix tail run on the HIP kernels as well
+(cat_amd.metric.DRNSeg, cat_amd.metric.get_mIoU -- reference metric/drn.py, metric/mIoU_score.py, metric/__init__.py:24-46).
+`attach_miou(model, checkpoint, table_path, data_dir)` does what the reference's __init__ does (base_inception_distiller.py:226-232,
+base_spade_distiller.py:166-170: `DRNSeg('drn_d_105', 19, pretrained=False)` + `load_network(..., opt.drn_path)`); a model that carries
+`drn_model` needs no `miou_fn`.  An attached
 
-    model.miou_fn = lambda fakes, names: get_mIoU(fakes, names, drn_model, model.device, table_path=..., data_dir=..., ...)
+    model.miou_fn = lambda fakes, names: ...
 
-(`fakes` is the reference's list of NCHW CPU tensors, one per eval batch) and gets the reference's bookkeeping back: `is_best`,
-`best_fid / best_mIoU`, the 3-evaluation running means and the `metric/*` dict that `Trainer` logs."""
+(`fakes` is the reference's list of NCHW CPU tensors, one per eval batch) still wins.  Either way the reference's bookkeeping comes back:
+`is_best`, `best_fid / best_mIoU`, the 3-evaluation running means and the `metric/*` dict that `Trainer` logs."""
 import ntpath
 import os
 
@@ -94,6 +98,20 @@ def attach_fid(model, state_dict, real_stat_path=None, npz=None, dims=2048):
     return net
 
 
+def attach_miou(model, state_dict, table_path=None, data_dir=None):
+    """What the reference's distiller __init__ does for the cityscapes mIoU (base_inception_distiller.py:226-232, base_spade_distiller.py:166-170),
+    with the network on the HIP kernels: `state_dict` = the reference's `--drn_path` checkpoint (DRNSeg('drn_d_105', 19) keys), or a path to
+    it; table_path / data_dir default to `opt.table_path` / `opt.cityscapes_path` at evaluation time."""
+    from ..metric import DRNSeg
+    if isinstance(state_dict, (str, bytes, os.PathLike)):
+        state_dict = torch.load(state_dict, map_location='cpu')
+    net = DRNSeg('drn_d_105', 19, pretrained=False)
+    net.load_state_dict(state_dict)
+    model.drn_model = net.to(model.device).eval()
+    model.miou_table_path, model.miou_data_dir = table_path, data_dir
+    return net
+
+
 def evaluate(model, step, student, feed, images, want_fid, want_miou, save_all=False):
     """feed(batch): set_input / set_single_input; images(j): {'input'|'real'|'Tfake'|'Sfake': HWC uint8} of sample j of the batch."""
     if getattr(model, 'eval_dataloader', None) is None:
@@ -108,7 +126,16 @@ def evaluate(model, step, student, feed, images, want_fid, want_miou, save_all=F
             raise RuntimeError('evaluate_model: call evaluation.attach_fid(model, fid_checkpoint, real_stat_path) or attach model.fid_fn '
                                '(cat_amd/distillers/evaluation.py)')
     if want_miou and getattr(model, 'miou_fn', None) is None:
-        raise RuntimeError('evaluate_model: attach model.miou_fn = lambda fakes, names: get_mIoU(...) (cat_amd/distillers/evaluation.py)')
+        if getattr(model, 'drn_model', None) is not None:
+            from .. import metric      # the reference's own call: get_mIoU(fakes, names, self.drn_model, ...) (inception_distiller.py:263-270)
+            table_path = getattr(model, 'miou_table_path', None) or model.opt.table_path
+            data_dir = getattr(model, 'miou_data_dir', None) or model.opt.cityscapes_path
+            model.miou_fn = lambda fakes, names: metric.get_mIoU(fakes, names, model.drn_model, model.device, table_path=table_path,
+                                                                 data_dir=data_dir, batch_size=getattr(model.opt, 'eval_batch_size', 1),
+                                                                 num_workers=getattr(model.opt, 'num_threads', 8), use_tqdm=False)
+        else:
+            raise RuntimeError('evaluate_model: call evaluation.attach_miou(model, drn_checkpoint, table_path, data_dir) or attach model.miou_fn = '
+                               'lambda fakes, names: ... (cat_amd/distillers/evaluation.py)')
     model.is_best = False
     save_dir = os.path.join(model.opt.log_dir, 'eval', str(step))
     os.makedirs(save_dir, exist_ok=True)

@@ -1,9 +1,12 @@
-"""Evaluation metrics of the distillers (reference metric/__init__.py): FID with its InceptionV3 feature extractor on the HIP kernels."""
+"""Evaluation metrics of the distillers (reference metric/__init__.py): FID with its InceptionV3 feature extractor and the cityscapes mIoU
+with its DRN-D-105 segmentation network, both on the HIP kernels."""
 import numpy as np
 import torch
 
 from .fid_score import _compute_statistics_of_ims, calculate_frechet_distance, get_activations_from_ims  # noqa: F401
+from .drn import DRNSeg  # noqa: F401
 from .inception import InceptionV3  # noqa: F401
+from .miou import miou_from_hist, per_class_iu  # noqa: F401
 
 
 def tensor2im_batch(t):
@@ -18,3 +21,22 @@ def get_fid(fakes, model, npz, device=None, batch_size=1, use_tqdm=True):
     ims = tensor2im_batch(torch.cat(fakes, dim=0)).astype(float)
     m2, s2 = _compute_statistics_of_ims(ims, model, batch_size, 2048, device, use_tqdm=use_tqdm)
     return float(calculate_frechet_distance(m1, s1, m2, s2))
+
+
+def get_mIoU(fakes, names, model, device, table_path='datasets/table.txt', data_dir='database/cityscapes', batch_size=1, num_workers=8,
+             num_classes=19, use_tqdm=True):
+    """metric/__init__.py:24-46: `fakes` = list of [B, 3, H, W] tensors in [-1, 1], `names` = their image names (looked up in the table);
+    model = cat_amd.metric.DRNSeg on `device`."""
+    from . import miou
+    ims = tensor2im_batch(torch.cat(fakes, dim=0))
+    return float(miou.test(ims, names, model, device, table_path=table_path, data_dir=data_dir, batch_size=batch_size, num_workers=num_workers,
+                           num_classes=num_classes, use_tqdm=use_tqdm))
+
+
+def get_cityscapes_mIoU(fakes, names, model, device, table_path='datasets/table.txt', data_dir='database/cityscapes', batch_size=1, num_workers=8,
+                        num_classes=19, tqdm_position=None):
+    """metric/__init__.py:49-71: the same arithmetic through metric/cityscapes_mIoU.py's `test`."""
+    from . import miou
+    ims = tensor2im_batch(torch.cat(fakes, dim=0))
+    return float(miou.test_cityscapes(ims, names, model, device, table_path=table_path, data_dir=data_dir, batch_size=batch_size,
+                                      num_workers=num_workers, num_classes=num_classes, tqdm_position=tqdm_position))

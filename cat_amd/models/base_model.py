@@ -1,6 +1,7 @@
 """BaseModel: the host-side glue of models/base_model.py:12-232 that `train.py` / `Trainer` touch (device, save_dir, setup,
 schedulers, loss dictionary, requires_grad toggling, checkpoints with the reference's file names and state_dict keys).  Dataset
-loaders and FID / mIoU evaluation stay with the reference."""
+loaders stay with the reference; FID / mIoU evaluation is the distillers' path (cat_amd/distillers/evaluation.py,
+cat_amd/metric: InceptionV3 and DRN-D-105 on the HIP kernels)."""
 import os
 from abc import ABC, abstractmethod
 from collections import OrderedDict
@@ -144,5 +145,5 @@ class BaseModel(ABC):
 
     def evaluate_model(self, step):
         raise NotImplementedError('teacher-training models: evaluate with the distillers\' path -- cat_amd.distillers.evaluation.evaluate + '
-                                  'attach_fid (InceptionV3 pool3 features on the HIP kernels, cat_amd.metric); mIoU needs the reference\'s DRN '
-                                  'weights and the cityscapes data (SURVEY §2 rows 18-19)')
+                                  'attach_fid / attach_miou (InceptionV3 pool3 features and the DRN-D-105 cityscapes mIoU on the HIP kernels, '
+                                  'cat_amd.metric); mIoU needs the reference\'s DRN checkpoint and the cityscapes data (SURVEY §2 rows 18-19)')

@@ -286,6 +286,23 @@ int cat_global_avgpool_fwd(const float* x, int xcs, int N, int HW, int C4, float
  * 2 * x - 1 input normalisation in one pass); padding channels [C, round_up(C, 4)) are written as 0. */
 int cat_resize_bilinear_fwd(const float* x, int xcs, int N, int H, int W, int C, float* y, int ycs, int Ho, int Wo, float a, float b,
                             cat_stream_t stream);
+/* ---- evaluation path: the cityscapes mIoU (metric/mIoU_score.py:127-247: DRN-D-105 + up-sampling head + confusion matrix).  Inference only. ---- */
+/* y = act(conv_dilated(x, w) + bias + res): nn.Conv2d(dilation=) of metric/drn.py:78-125, 163-202 with eval-mode BatchNorm folded into
+ * w / bias by the host, and the bottleneck's shortcut added BEFORE the ReLU (:116-123).  res may be NULL, or point at a channel slice with
+ * pixel stride rcs.  Zero padding g->pad; Ho = (H + 2 * pad - dilation * (kh - 1) - 1) / stride + 1.  dilation > 1 needs stride 1.
+ * dilation == 1 with res == NULL is cat_conv2d_fwd itself, bit for bit. */
+int cat_conv2d_fwd_ex(const cat_conv_t* g, int dilation, const float* x, const float* w, const float* bias, const float* res, int rcs,
+                      float* y, cat_stream_t stream);
+/* nn.ConvTranspose2d(C, C, 2 * s, stride=s, padding=s / 2, groups=C, bias=False) + nn.LogSoftmax(dim=1) (metric/mIoU_score.py:152-168; s = 8).
+ * x: [N][h][w][xcs]; up_w: [C][1][2s][2s] dense, as in the checkpoint; y: [N][h * s][w * s][ycs], padding channels written as 0. */
+int cat_seg_up_logsoftmax(const float* x, int xcs, int N, int h, int w, int C, const float* up_w, int s, float* y, int ycs,
+                          cat_stream_t stream);
+/* resize_4d_tensor + argmax + fast_hist (metric/mIoU_score.py:174-206, 238-241) without the resized map: for every pixel of the Hl x Wl
+ * label map, interpolate the C log-probabilities bilinearly (half-pixel centres, clamped edges; none when (h, w) == (Hl, Wl)), take the argmax
+ * (lowest index wins) and, if label < n_classes, add 1 to hist[n_classes * label + pred].  hist: n_classes^2 64-bit counters that ACCUMULATE
+ * across calls; label: uint8 [N][Hl][Wl] (255 = ignore); pred: uint8 [N][Hl][Wl] or NULL. */
+int cat_seg_confusion(const float* logp, int lcs, int N, int h, int w, int C, const unsigned char* label, int Hl, int Wl, int n_classes,
+                      long long* hist, unsigned char* pred, cat_stream_t stream);
 /* SPADEModel.preprocess_input + get_edges (models/spade_model.py:142-179): label -> one-hot over nc channels,
  * instance ids -> 4-neighbour edge map in channel nc (inst may be NULL = --no_instance).  y: [N][H][W][cs]. */
 int cat_onehot_edges(const int* label, const int* inst, float* y, int N, int H, int W, int nc, int cs,
