@@ -5,8 +5,8 @@
 
 with train-mode (Synchronized)BatchNorm2d in every position, zero ("same") padding, C_in != C_out in general and an optional addend r (the
 block's shortcut).  The per-layer path launches ~45 kernels per unit (12 convs, 9 norms x 3, add_n); most of them HBM-bound passes over
-hidden tensors of 1..13 channels on planes of up to 256 x 512 pixels.  Here a unit is the protocol of cat_amd/fused_block.py without the
-closing pw_bn:
+hidden tensors of 1..13 channels on planes of up to 256 x 512 pixels.  Here a unit is the protocol of cat_amd/fused_unit.py (layout, operand
+preparation and the stages, shared with the fused inception block) without that block's closing pw_bn:
 
     stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tconv_fwd)
     finalize  scale / shift of all stage-1 norms + their running statistics                               (cat_tnorm_finalize)
@@ -14,8 +14,8 @@ closing pw_bn:
     finalize
     stage 2   the branch sum: six second convs K-concatenated, norm + ReLU applied while staging, bias and the addend r in the epilogue
 
-5 launches, no normalised tensor is ever written.  The backward pass re-materialises the two hidden activations and reuses the kernels of
-the fused inception block (branch-wise weight gradients on side streams, norm backward once per stage over the concatenation, the first-conv
+5 launches, no normalised tensor is ever written.  The backward pass re-materialises the two hidden activations and runs the shared backward
+stages (branch-wise weight gradients on side streams, norm backward once per stage over the concatenation, the first-conv
 input gradients as one K-concatenated launch).  Taken when the unit runs in training mode on one rank (with several ranks the
 SynchronizedBatchNorm statistics are exchanged per layer: general path), on planes of at least `ops._TCONV_MIN_TILES` 8 x 16 tiles (the
 64 x 128 .. 256 x 512 stages at batch 4); tests/test_spade_gpu.py::test_fused_spade_units_match_general_path pins it to the general path."""
@@ -29,6 +29,7 @@ from . import nn as cnn
 from . import ops
 from . import optim
 from . import tconv
+from . import fused_unit as U
 
 _ENABLED = os.environ.get('CAT_FUSED_SPADE', '1') != '0'      # A/B switch; 'train' / 'frozen' select one of the two forms
 _ONLY = os.environ.get('CAT_FUSED_SPADE', '1') if os.environ.get('CAT_FUSED_SPADE', '1') in ('train', 'frozen') else None
@@ -45,10 +46,6 @@ def set_enabled(on):
     _ENABLED = bool(on)
 
 
-def _cs4(c):
-    return (c + 3) // 4 * 4
-
-
 def _conv_of(m):
     """nn.Conv2d behind a `Conv` wrapper (main branches) or the plain conv (gamma|beta nets)."""
     return m.conv if hasattr(m, 'conv') and not isinstance(m, cnn.Conv2d) else m
@@ -60,14 +57,6 @@ def _branches(res_ops, dw_ops):
     dws = [dict(kind='dw', k=1, kd=op[1].conv.kernel_size[0], m=op[0].conv.out_channels, conv1=op[0].conv, bn1=op[0].norm, act=op[0].active,
                 dconv=op[1].conv, bn2=op[1].norm, conv2=_conv_of(op[2])) for op in dw_ops]
     return res, dws
-
-
-def _has_hooks(mods):
-    for m in mods:
-        for s in m.modules():
-            if s._forward_hooks or s._forward_pre_hooks or s._backward_hooks:
-                return True
-    return False
 
 
 def applicable(res_ops, dw_ops, x, training):
@@ -123,222 +112,48 @@ def applicable(res_ops, dw_ops, x, training):
             return False
         if dw and b['dconv'].padding[0] != (b.get('kd', 1) - 1) // 2:
             return False
-    if sum(_cs4(b['m']) for b in dws) > 4 * (L.DWM_MAXQ_BWD if training else L.DWM_MAXQ):
+    if sum(U.cs4(b['m']) for b in dws) > 4 * (L.DWM_MAXQ_BWD if training else L.DWM_MAXQ):
         return False
-    return not _has_hooks(list(res_ops) + list(dw_ops))
+    return not U.has_hooks(list(res_ops) + list(dw_ops))
 
 
-class _Plan:
-    """Static layout of one unit: channel slices, persistent operand buffers and the preparation job table (cf. fused_block._Plan)."""
+class _Plan(U.Plan):
+    """The layout of one unit (C_in != C_out in general, 'same' zero padding, one (eps, momentum, activation) for all its norms)."""
+    what = 'fused SPADE unit'
+    GAMMA0 = 1.0      # non-affine norms (the depthwise branches' second norm of a SPADE block) read gamma = 1 / beta = 0 from the concatenated vectors
 
     def __init__(self, res_ops, dw_ops, cin, cout, dev):
-        self.dev = dev
         res, dws = _branches(res_ops, dw_ops)
-        self.mods = list(res_ops) + list(dw_ops)
         for b in res + dws:
             cnn._to_channels_last_(b['conv1'])
             cnn._to_channels_last_(b['conv2'])
-        self.Cin, self.csi = cin, _cs4(cin)
-        self.Cout, self.cso = cout, _cs4(cout)
         first = (res + dws)[0]
         self.act, self.slope = cnn._act_code(first['act'])
         self.eps, self.momentum = float(first['bn1'].eps), float(first['bn1'].momentum)
-        order = [b for b in res if b['k'] == 1] + dws + [b for b in res if b['k'] == 3] + [b for b in res if b['k'] == 5]
-        off = 0
-        for b in order:
-            b['o1'], b['w1'] = off, _cs4(b['m'])
-            off += b['w1']
-        self.hc1 = off
-        off = 0
-        for b in dws:
-            b['od'] = off
-            off += _cs4(b['m'])
-        self.hcd = off
-        self.dw_in0 = dws[0]['o1'] if dws else 0
-        self.branches, self.res, self.dws = order, res, dws
-        self.groups = []
-        for k in (1, 3, 5):
-            bs = [b for b in order if b['k'] == k]
-            if bs:
-                g0, g1 = bs[0]['o1'], bs[-1]['o1'] + bs[-1]['w1']
-                self.groups.append(dict(k=k, off=g0, width=g1 - g0, branches=bs))
-        z = lambda n: torch.zeros(max(n, 4), device=dev, dtype=torch.float32)
-        for g in self.groups:
-            g['pack'] = z(tconv.pack_floats(g['k'], self.csi, g['width']))
-        # non-affine norms (the depthwise branches' second norm of a SPADE block) read gamma = 1 / beta = 0 from the concatenated vectors
-        self.gamma1, self.beta1, self.bias1 = torch.ones(max(self.hc1, 4), device=dev), z(self.hc1), z(self.hc1)
-        self.gammad, self.betad, self.biasd = torch.ones(max(self.hcd, 4), device=dev), z(self.hcd), z(self.hcd)
-        self.bias2 = z(self.cso)
-        self.w25 = z(25 * max(self.hcd, 4))
-        self.has_bias1 = any(b['conv1'].bias is not None for b in order)
-        self.has_biasd = any(b['dconv'].bias is not None for b in dws)
-        self.has_bias2 = any(b['conv2'].bias is not None for b in order)
-        po = 0
-        for b in order:
-            k2 = b['k'] if b['kind'] == 'res' else 1
-            b['k2'], b['p2off'] = k2, po
-            po += tconv.pack_floats(k2, b['w1'], self.Cout)
-        self.pack2 = z(po)
-        po = 0
-        for b in order:
-            b['d2off'] = po
-            po += tconv.pack_floats(b['k2'], self.cso, b['m'])
-        self.dpack2 = z(po)
-        # the second convs' input gradients as ONE launch (cat_tstage1_dgrad: dT is staged once for the 5 x 5 and the 3 x 3 residual branch
-        # and the N-concatenated 1 x 1 second convs of the depthwise branches) where a kernel exists for the widths
-        r5, r3 = [b for b in res if b['k'] == 5], [b for b in res if b['k'] == 3]
-        self.s1d = None
-        if _S1_DGRAD and len(r5) == 1 and len(r3) == 1 and dws and L.query('cat_tstage1_dgrad_supported', r5[0]['w1'], r3[0]['w1'], self.hcd):
-            self.s1d = (r5[0], r3[0])
-            self.dpack2_dw = z(tconv.pack_floats(1, self.cso, self.hcd))
-        po = 0
-        for b in order:
-            b['d1off'] = po
-            po += tconv.pack_floats(b['k'], b['w1'], self.Cin)
-        self.dpack1 = z(po)
-        self.gv = dict(g1=z(self.hc1), b1=z(self.hc1), c1=z(self.hc1), gd=z(self.hcd), bd=z(self.hcd), cd=z(self.hcd), c2=z(self.cso))
-        self.targets = []       # (vector name, offset, n, parameter)
-        for b in order:
-            if b['bn1'].weight is not None:
-                self.targets += [('g1', b['o1'], b['m'], b['bn1'].weight), ('b1', b['o1'], b['m'], b['bn1'].bias)]
-            if b['conv1'].bias is not None:
-                self.targets.append(('c1', b['o1'], b['m'], b['conv1'].bias))
-            if b['conv2'].bias is not None:
-                self.targets.append(('c2', 0, self.Cout, b['conv2'].bias))
-        for b in dws:
-            if b['bn2'].weight is not None:
-                self.targets += [('gd', b['od'], b['m'], b['bn2'].weight), ('bd', b['od'], b['m'], b['bn2'].bias)]
-            if b['dconv'].bias is not None:
-                self.targets.append(('cd', b['od'], b['m'], b['dconv'].bias))
-        # merged weight-gradient launches (as in fused_block): the 1 x 1 first convs of all branches are ONE GEMM over the N-concatenated dZ1
-        # slice (x is read once instead of once per branch; rows of `w1` then go to the parameters), the 1 x 1 second convs of the depthwise
-        # branches one K-concatenated GEMM over the whole depthwise hidden buffer (columns of `w2`)
-        g1 = next((g for g in self.groups if g['k'] == 1), None)
-        self.merge1 = g1 if (g1 is not None and len(g1['branches']) > 1) else None
-        if self.merge1 is not None:
-            self.gv['w1'] = z(g1['width'] * self.csi)
-            for b in g1['branches']:
-                self.targets.append(('w1', (b['o1'] - g1['off']) * self.csi, b['m'] * self.csi, b['conv1'].weight))
-        self.merge2 = len(dws) > 1
-        self.targets2d = []      # (vector, src offset, rows, cols, src stride, parameter): dst stride = the parameter's own wcs
-        if self.merge2:
-            self.gv['w2'] = z(self.Cout * self.hcd)
-            for b in dws:
-                self.targets2d.append(('w2', b['od'], self.Cout, _cs4(b['m']), self.hcd, b['conv2'].weight))
-        self.params = []
-        seen = set()
-        for m in self.mods:
+        params, seen = [], set()
+        for m in list(res_ops) + list(dw_ops):
             for q in m.parameters():
                 if id(q) not in seen:
                     seen.add(id(q))
-                    self.params.append(q)
-        self.scatter_jobs = None
-        self._build_jobs()
-        self.key = self.bkey = None
+                    params.append(q)
+        super().__init__(res, dws, cin, cout, dev, params)
 
-    def _jobs_to_dev(self, jobs):
-        arr = (L.PrepJob * len(jobs))()
-        blk = 0
-        for i, j in enumerate(jobs):
-            for f, v in j.items():
-                if f == 'srcs':
-                    for k, pv in enumerate(v):
-                        arr[i].srcs[k] = pv
-                elif f != 'threads':
-                    setattr(arr[i], f, v)
-            nb = max(1, (j['threads'] + 255) // 256)
-            arr[i].block0, arr[i].nblocks = blk, nb
-            blk += nb
-        t = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.dev)
-        self._last_arr = arr      # host copy (fused_block.prepare_plans merges the tables of all units of a generator into one launch)
-        return t, len(jobs), blk
-
-    def _pack_job(self, w, dst_ptr, mode, nn, ck, ks, nt_total, col0):
-        wcl, wcs = ops.weight_cl(w)
-        if wcl.data_ptr() != w.data_ptr():
-            raise RuntimeError('fused SPADE unit: conv weights must be in kernel layout')
-        taps = ks * ks
-        c4 = _cs4(ck)
-        nfull, rem = c4 // 16, (c4 % 16) // 4
-        groups = nfull * taps + ((taps * rem + 3) // 4 if rem else 0)
-        ntw = (col0 + nn + 15) // 16 - col0 // 16
-        return dict(kind=0, srcs=[w.data_ptr()], dst=dst_ptr, mode=mode, Nn=nn, Ck=ck, ks=ks, wcs=wcs, wn=taps * wcs, c4=c4, nt_total=nt_total, col0=col0,
-                    threads=groups * ntw * 64)
-
-    def _build_jobs(self):
-        fwd, bwd = [], []
-        vec = lambda dst, off, srcs, n: dict(kind=1, srcs=[s.data_ptr() for s in srcs], nsrc=len(srcs), dst=dst.data_ptr() + 4 * off, n=n, threads=n)
-        for g in self.groups:
-            nt = (g['width'] + 15) // 16
-            for b in g['branches']:
-                fwd.append(self._pack_job(b['conv1'].weight, g['pack'].data_ptr(), tconv.FWD, b['m'], self.Cin, g['k'], nt, b['o1'] - g['off']))
-        nt2 = (self.Cout + 15) // 16
-        nt1 = (self.Cin + 15) // 16
-        for b in self.branches:
-            if b['bn1'].weight is not None:
-                fwd.append(vec(self.gamma1, b['o1'], [b['bn1'].weight], b['m']))
-                fwd.append(vec(self.beta1, b['o1'], [b['bn1'].bias], b['m']))
-            if b['conv1'].bias is not None:
-                fwd.append(vec(self.bias1, b['o1'], [b['conv1'].bias], b['m']))
-            fwd.append(self._pack_job(b['conv2'].weight, self.pack2.data_ptr() + 4 * b['p2off'], tconv.FWD, self.Cout, b['m'], b['k2'], nt2, 0))
-            bwd.append(self._pack_job(b['conv2'].weight, self.dpack2.data_ptr() + 4 * b['d2off'], tconv.DGRAD, b['m'], self.Cout, b['k2'], (b['m'] + 15) // 16, 0))
-            bwd.append(self._pack_job(b['conv1'].weight, self.dpack1.data_ptr() + 4 * b['d1off'], tconv.DGRAD, self.Cin, b['m'], b['k'], nt1, 0))
-            if self.s1d is not None and b['kind'] == 'dw':
-                bwd.append(self._pack_job(b['conv2'].weight, self.dpack2_dw.data_ptr(), tconv.DGRAD, b['m'], self.Cout, 1, (self.hcd + 15) // 16, b['od']))
-        for b in self.dws:
-            if b['bn2'].weight is not None:
-                fwd.append(vec(self.gammad, b['od'], [b['bn2'].weight], b['m']))
-                fwd.append(vec(self.betad, b['od'], [b['bn2'].bias], b['m']))
-            if b['dconv'].bias is not None:
-                fwd.append(vec(self.biasd, b['od'], [b['dconv'].bias], b['m']))
-            kd = b['kd']
-            wd = b['dconv'].weight
-            if not wd.is_contiguous():
-                raise RuntimeError('fused SPADE unit: depthwise weights must be contiguous')
-            fwd.append(dict(kind=2, srcs=[wd.data_ptr()], dst=self.w25.data_ptr(), Nn=b['m'], ks=kd, col0=b['od'], cs=self.hcd, threads=b['m'] * kd * kd))
-        b2 = [b['conv2'].bias for b in self.branches if b['conv2'].bias is not None]
-        if b2:
-            fwd.append(vec(self.bias2, 0, b2, self.Cout))
-        self.ptrs = tuple(q.data_ptr() for q in self.params)
-        self.shapes = tuple(tuple(q.shape) for q in self.params)
-        self.ids = tuple(id(q) for q in self.params)
-        self.fwd_jobs = self._jobs_to_dev(fwd)
-        self.fwd_arr = self._last_arr
-        self.bwd_jobs = self._jobs_to_dev(bwd)
-        self.bwd_arr = self._last_arr
-        self.tables_version = getattr(self, 'tables_version', 0) + 1
-
-    def __deepcopy__(self, memo):
-        """A copied module builds its own plan at its first forward (cf. fused_block._Plan.__deepcopy__)."""
-        return None
-
-    def _epoch_key(self):
-        trainable = any(getattr(q, '_cat_grad_view', None) is not None for q in self.params)
-        return (optim.weights_epoch() if trainable else -1, tuple(q._version for q in self.params))
-
-    def ptrs_now(self):
-        return tuple(q.data_ptr() for q in self.params)
+    def _merges_dw_dgrad(self):
+        """The second convs' input gradients as ONE launch (cat_tstage1_dgrad: dT is staged once for the 5 x 5 and the 3 x 3 residual branch
+        and the N-concatenated 1 x 1 second convs of the depthwise branches) where a kernel exists for the widths."""
+        r5, r3 = [b for b in self.res if b['k'] == 5], [b for b in self.res if b['k'] == 3]
+        self.s1d = None
+        if _S1_DGRAD and len(r5) == 1 and len(r3) == 1 and self.dws and L.query('cat_tstage1_dgrad_supported', r5[0]['w1'], r3[0]['w1'], self.hcd):
+            self.s1d = (r5[0], r3[0])
+        return self.s1d is not None
 
     def prepare(self, backward=False):
         gref = getattr(self, 'group', None)      # weak reference to the generator that owns this unit (no cycle through the cached plans)
         group = gref() if gref is not None else None
         if group is not None and (self.bkey if backward else self.key) != self._epoch_key():
             # the first stale unit of a pass refreshes the operands of EVERY fused unit of the generator in one launch (round 4)
-            from . import fused_block
-            fused_block.prepare_plans(units_of(group), gref, backward)
-        if tuple(q.data_ptr() for q in self.params) != self.ptrs:       # FusedAdam re-housed the parameters: same layout, new addresses
-            self._build_jobs()
-            self.key = self.bkey = self.scatter_jobs = None
-        key = self._epoch_key()
-        if backward:
-            if self.bkey != key:
-                t, n, blocks = self.bwd_jobs
-                L.call('cat_prep_run', ops._p(t), n, blocks, 0, ops._stream())
-                self.bkey = key
-        elif self.key != key:
-            t, n, blocks = self.fwd_jobs
-            L.call('cat_prep_run', ops._p(t), n, blocks, 0, ops._stream())
-            self.key = key
+            U.prepare_plans(units_of(group), gref, backward)
+        self._prepare_own(backward)
 
 
 def units_of(generator):
@@ -479,47 +294,15 @@ def forward_g(p, x, addend, save=None):
     tiles = n * ((h + 7) // 8) * ((w + 15) // 16)
     z1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
     part1 = torch.empty((tiles, 2, p.hc1), device=dev, dtype=torch.float32)
-    by_k = {g['k']: g for g in p.groups}
-    if len(p.groups) == 3 and L.query('cat_tstage1_supported', by_k[5]['width'], by_k[3]['width'], by_k[1]['width']):
-        gs = L.Stage1Geom()
-        gs.N, gs.H, gs.W, gs.xcs, gs.cin, gs.reflect, gs.ycs, gs.scs = n, h, w, ops.act_cs(x), c, 0, p.hc1, p.hc1
-        packs = (C.c_void_p * 3)()
-        for slot, k in enumerate((5, 3, 1)):
-            g = by_k[k]
-            gs.col0[slot], gs.width[slot], gs.nvalid[slot] = g['off'], g['width'], sum(b['m'] for b in g['branches'])
-            packs[slot] = g['pack'].data_ptr()
-        L.call('cat_tstage1_fwd', C.byref(gs), ops._p(x), packs, ops._p(p.bias1) if p.has_bias1 else None, ops._p(z1), ops._p(part1), ops._stream())
-    else:
-        for g in p.groups:
-            pad = (g['k'] - 1) // 2
-            seg = tconv.Segment(x, g['k'], pad, False, 0)
-            tconv.run([seg], g['pack'], (p.bias1.data_ptr() + 4 * g['off']) if p.has_bias1 else None, None, g['width'], n, h, w, h, w, ycs=p.hc1,
-                      ycw=g['width'], yptr=z1.data_ptr() + 4 * g['off'], stats=part1.data_ptr() + 4 * g['off'], scs=p.hc1,
-                      nvalid=sum(b['m'] for b in g['branches']))
+    U.stage1(p, x, z1, part1)
     st1 = yield from _finalize_g(p, part1, p.hc1, n, h, w, p.gamma1, p.beta1, [(b['o1'], b['m'], b['bn1']) for b in p.branches])
     zd = std = None
     if p.dws:
         zd = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
         partd = torch.empty((tiles, 2, p.hcd), device=dev, dtype=torch.float32)
-        gd = L.DwmGeom()
-        gd.N, gd.H, gd.W, gd.nq, gd.xcs, gd.ycs, gd.scs = n, h, w, p.hcd // 4, p.hc1, p.hcd, p.hcd
-        gd.sstride, gd.reflect, gd.act, gd.slope = 0, 0, p.act, p.slope
-        for b in p.dws:
-            for q in range(b['od'] // 4, (b['od'] + _cs4(b['m'])) // 4):
-                gd.ks[q] = b['kd']
-        o = p.dw_in0
-        L.call('cat_dwm_fwd', C.byref(gd), C.c_void_p(z1.data_ptr() + 4 * o), C.c_void_p(st1[0][0].data_ptr() + 4 * o),
-               C.c_void_p(st1[0][1].data_ptr() + 4 * o), ops._p(p.w25), ops._p(p.biasd) if p.has_biasd else None, ops._p(zd), ops._p(partd), ops._stream())
+        U.dwm_fwd(p, z1, st1[0][0], st1[0][1], zd, partd)
         std = yield from _finalize_g(p, partd, p.hcd, n, h, w, p.gammad, p.betad, [(b['od'], b['m'], b['bn2']) for b in p.dws])
-    segs = []
-    for b in p.branches:
-        if b['kind'] == 'res':
-            k = b['k']
-            segs.append(tconv.Segment(None, k, (k - 1) // 2, False, b['p2off'], c4=b['w1'], cin=b['m'], xcs=p.hc1, ptr=z1.data_ptr() + 4 * b['o1'],
-                                      scale=st1[0][0].data_ptr() + 4 * b['o1'], shift=st1[0][1].data_ptr() + 4 * b['o1'], act=p.act, slope=p.slope))
-        else:
-            segs.append(tconv.Segment(None, 1, 0, False, b['p2off'], c4=b['w1'], cin=b['m'], xcs=p.hcd, ptr=zd.data_ptr() + 4 * b['od'],
-                                      scale=std[0][0].data_ptr() + 4 * b['od'], shift=std[0][1].data_ptr() + 4 * b['od'], act=p.act, slope=p.slope))
+    segs = U.stage2_segs(p, z1, st1[0], zd, std[0] if std is not None else None)
     y = ops.empty_act(n, p.Cout, h, w, dev)
     tconv.run(segs, p.pack2, p.bias2 if p.has_bias2 else None, y, p.Cout, n, h, w, h, w, res=addend)
     if save is not None:
@@ -564,32 +347,12 @@ def forward_eval(p, x, addend):
     n, c, h, w = x.shape
     dev = x.device
     z1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
-    for g in p.groups:
-        pad = (g['k'] - 1) // 2
-        seg = tconv.Segment(x, g['k'], pad, False, 0)
-        tconv.run([seg], g['pack'], (p.bias1.data_ptr() + 4 * g['off']) if p.has_bias1 else None, None, g['width'], n, h, w, h, w, ycs=p.hc1,
-                  ycw=g['width'], yptr=z1.data_ptr() + 4 * g['off'], nvalid=sum(b['m'] for b in g['branches']))
+    U.stage1(p, x, z1, None)
     zd = None
     if p.dws:
         zd = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
-        gd = L.DwmGeom()
-        gd.N, gd.H, gd.W, gd.nq, gd.xcs, gd.ycs, gd.scs = n, h, w, p.hcd // 4, p.hc1, p.hcd, p.hcd
-        gd.sstride, gd.reflect, gd.act, gd.slope = 0, 0, p.act, p.slope
-        for b in p.dws:
-            for q in range(b['od'] // 4, (b['od'] + _cs4(b['m'])) // 4):
-                gd.ks[q] = b['kd']
-        o = p.dw_in0
-        L.call('cat_dwm_fwd', C.byref(gd), C.c_void_p(z1.data_ptr() + 4 * o), C.c_void_p(ss1[0].data_ptr() + 4 * o), C.c_void_p(ss1[1].data_ptr() + 4 * o),
-               ops._p(p.w25), ops._p(p.biasd) if p.has_biasd else None, ops._p(zd), None, ops._stream())
-    segs = []
-    for b in p.branches:
-        if b['kind'] == 'res':
-            k = b['k']
-            segs.append(tconv.Segment(None, k, (k - 1) // 2, False, b['p2off'], c4=b['w1'], cin=b['m'], xcs=p.hc1, ptr=z1.data_ptr() + 4 * b['o1'],
-                                      scale=ss1[0].data_ptr() + 4 * b['o1'], shift=ss1[1].data_ptr() + 4 * b['o1'], act=p.act, slope=p.slope))
-        else:
-            segs.append(tconv.Segment(None, 1, 0, False, b['p2off'], c4=b['w1'], cin=b['m'], xcs=p.hcd, ptr=zd.data_ptr() + 4 * b['od'],
-                                      scale=ssd[0].data_ptr() + 4 * b['od'], shift=ssd[1].data_ptr() + 4 * b['od'], act=p.act, slope=p.slope))
+        U.dwm_fwd(p, z1, ss1[0], ss1[1], zd, None)
+    segs = U.stage2_segs(p, z1, ss1, zd, ssd)
     y = ops.empty_act(n, p.Cout, h, w, dev)
     tconv.run(segs, p.pack2, p.bias2 if p.has_bias2 else None, y, p.Cout, n, h, w, h, w, res=addend)
     return y
@@ -619,11 +382,6 @@ def _norm_bwd_g(p, n, hw, c, cs, x, dy, gamma, beta, mr, dgamma, dbeta, synced=F
     L.call('cat_norm_bwd', C.byref(g), ops._p(x), ops._p(dy), ops._p(gamma), ops._p(beta), ops._p(mr[0]), ops._p(mr[1]), ops._p(dx), ops._p(dgamma),
            ops._p(dbeta), 0, ops._p(ws), ops._stream())
     return dx
-
-
-def _channel_sum(src, m_pix, c, cs, dst):
-    ws = ops.workspace(L.query('cat_channel_sum_ws_bytes', m_pix, cs), src.device)
-    L.call('cat_channel_sum', ops._p(src), m_pix, c, cs, ops._p(dst), 0, ops._p(ws), ops._stream())
 
 
 class _UnitFn(torch.autograd.Function):
@@ -663,7 +421,6 @@ def _backward_g(ctx, dy):
     p.prepare(backward=True)
     n, c, h, w = x.shape
     dev, hw, m_pix = x.device, h * w, n * h * w
-    st = ops._stream()
     grads = {}
     side = ops.SideJobs(dev)
 
@@ -673,13 +430,11 @@ def _backward_g(ctx, dy):
         side.run(job)
 
     # ---- re-materialise the hidden activations (inputs of the second convs / of the depthwise convs)
-    a1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
-    L.call('cat_affine_res_fwd', ops._p(z1), p.hc1, ops._p(ss1[0]), ops._p(ss1[1]), 0, None, 0, ops._p(a1), p.hc1, 1, m_pix, p.hc1, p.act, p.slope, st)
+    a1 = U.rematerialise(p, z1, ss1)
     da1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
     ad = dad = None
     if ctx.has_dw:
-        ad = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
-        L.call('cat_affine_res_fwd', ops._p(zd), p.hcd, ops._p(ssd[0]), ops._p(ssd[1]), 0, None, 0, ops._p(ad), p.hcd, 1, m_pix, p.hcd, p.act, p.slope, st)
+        ad = U.rematerialise(p, zd, ssd)
         dad = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
     # ---- second convs: weight gradients from (hidden activation slice, dT); input gradients into slices of dA1 / dAd
     side.fork()
@@ -693,8 +448,7 @@ def _backward_g(ctx, dy):
 
         def kw(dst_, acc, sst, xptr=xptr, m=m, scs_=scs_, k2=k2, pad2=pad2):
             gw = ops._conv_geom(n, h, w, m, scs_, h, w, p.Cout, p.cso, k2, k2, 1, pad2, L.PAD_ZERO, wcs=ops._grad_wcs(dst_))
-            ws = ops.workspace(L.query('cat_conv2d_wgrad_ws_bytes', C.byref(gw)), dev)
-            L.call('cat_conv2d_wgrad', C.byref(gw), xptr, ops._p(dt), ops._p(dst_), acc, ops._p(ws), sst)
+            U.wgrad(gw, xptr, ops._p(dt), dst_, acc, sst)
         if res or not p.merge2:
             put_side(b['conv2'].weight, kw)
         if p.s1d is not None and (b is p.s1d[0] or b is p.s1d[1] or not res):
@@ -713,66 +467,26 @@ def _backward_g(ctx, dy):
             packs[slot], dxs[slot] = pk, dst.data_ptr()
         L.call('cat_tstage1_dgrad', C.byref(gs), ops._p(dt), packs, dxs, dxcs, ops._stream())
     if p.merge2:
-        def kw2(sst):
-            gw = ops._conv_geom(n, h, w, p.hcd, p.hcd, h, w, p.Cout, p.cso, 1, 1, 1, 0, L.PAD_ZERO, wcs=p.hcd)
-            ws = ops.workspace(L.query('cat_conv2d_wgrad_ws_bytes', C.byref(gw)), dev)
-            L.call('cat_conv2d_wgrad', C.byref(gw), ops._p(ad), ops._p(dt), ops._p(p.gv['w2']), 0, ops._p(ws), sst)
-        side.run(lambda: kw2(ops._stream()))
+        gw2 = ops._conv_geom(n, h, w, p.hcd, p.hcd, h, w, p.Cout, p.cso, 1, 1, 1, 0, L.PAD_ZERO, wcs=p.hcd)
+        side.run(lambda: U.wgrad(gw2, ops._p(ad), ops._p(dt), p.gv['w2'], 0, ops._stream()))
     if p.has_bias2:
-        _channel_sum(dt, m_pix, p.Cout, p.cso, p.gv['c2'])
+        U.channel_sum(dt, m_pix, p.Cout, p.cso, p.gv['c2'])
     # ---- depthwise stage
     if ctx.has_dw:
         dzd = yield from _norm_bwd_g(p, n, hw, p.hcd, p.hcd, zd, dad, p.gammad, p.betad, mrd, p.gv['gd'], p.gv['bd'], ctx.synced)
         if p.has_biasd:
-            _channel_sum(dzd, m_pix, p.hcd, p.hcd, p.gv['cd'])
-        nb = len(p.dws)
-        gd = L.DwmGeom()
-        gd.N, gd.H, gd.W, gd.nq, gd.xcs, gd.ycs, gd.scs = n, h, w, p.hcd // 4, p.hc1, p.hcd, p.hcd
-        gd.reflect = 0
-        for b in p.dws:
-            for q in range(b['od'] // 4, (b['od'] + _cs4(b['m'])) // 4):
-                gd.ks[q] = b['kd']
-        wts = [b['dconv'].weight for b in p.dws]
-        tg = [ops._grad_target(q) for q in wts]
-        if all(t_ is not None for t_ in tg):
-            fresh = {q._cat_grad_state['fresh'] for q in wts}
-            if len(fresh) != 1:
-                raise RuntimeError('fused SPADE unit backward: depthwise gradient buffers out of sync')
-            acc_dw, dsts = (0 if fresh.pop() else 1), tg
-            for q in wts:
-                q._cat_grad_state['fresh'] = False
-                grads[id(q)] = None
-        else:
-            acc_dw, dsts = 0, [torch.empty_like(q) for q in wts]
-            for q, d_ in zip(wts, dsts):
-                if ops._grad_target(q) is None:
-                    grads[id(q)] = d_
-        IA = C.c_int * nb
-        wsd = ops.workspace(L.query('cat_dwm_bwd_ws_bytes', C.byref(gd)), dev)
-        L.call('cat_dwm_bwd', C.byref(gd), C.c_void_p(a1.data_ptr() + 4 * p.dw_in0), ops._p(dzd), ops._p(p.w25),
-               C.c_void_p(da1.data_ptr() + 4 * p.dw_in0), p.hc1, nb, IA(*[b['od'] for b in p.dws]), IA(*[b['m'] for b in p.dws]),
-               IA(*[b['kd'] for b in p.dws]), (C.c_void_p * nb)(*[d_.data_ptr() for d_ in dsts]), acc_dw, ops._p(wsd), st)
-        if not all(t_ is not None for t_ in tg):
-            for q, d_ in zip(wts, dsts):
-                tq = ops._grad_target(q)
-                if tq is not None:
-                    (tq.copy_ if q._cat_grad_state['fresh'] else tq.add_)(d_)
-                    q._cat_grad_state['fresh'] = False
-                    grads[id(q)] = None
+            U.channel_sum(dzd, m_pix, p.hcd, p.hcd, p.gv['cd'])
+        U.dw_bwd(p, a1, da1, dzd, grads)
     # ---- stage-1 norms (all branches at once)
     dz1 = yield from _norm_bwd_g(p, n, hw, p.hc1, p.hc1, z1, da1, p.gamma1, p.beta1, mr1, p.gv['g1'], p.gv['b1'], ctx.synced)
     if p.has_bias1:
-        _channel_sum(dz1, m_pix, p.hc1, p.hc1, p.gv['c1'])
+        U.channel_sum(dz1, m_pix, p.hc1, p.hc1, p.gv['c1'])
     # ---- first convs: weight gradients from (x, dZ1 slice)
     side.refork()
     if p.merge1 is not None:
         g1 = p.merge1
-
-        def kw1m(sst):
-            gw = ops._conv_geom(n, h, w, c, ops.act_cs(x), h, w, g1['width'], p.hc1, 1, 1, 1, 0, L.PAD_ZERO, wcs=p.csi)
-            ws = ops.workspace(L.query('cat_conv2d_wgrad_ws_bytes', C.byref(gw)), dev)
-            L.call('cat_conv2d_wgrad', C.byref(gw), ops._p(x), C.c_void_p(dz1.data_ptr() + 4 * g1['off']), ops._p(p.gv['w1']), 0, ops._p(ws), sst)
-        side.run(lambda: kw1m(ops._stream()))
+        gw1 = ops._conv_geom(n, h, w, c, ops.act_cs(x), h, w, g1['width'], p.hc1, 1, 1, 1, 0, L.PAD_ZERO, wcs=p.csi)
+        side.run(lambda: U.wgrad(gw1, ops._p(x), C.c_void_p(dz1.data_ptr() + 4 * g1['off']), p.gv['w1'], 0, ops._stream()))
     for b in p.branches:
         if p.merge1 is not None and b['k'] == 1:
             continue
@@ -782,64 +496,17 @@ def _backward_g(ctx, dy):
 
         def kw1(dst_, acc, sst, dyp=dyp, m=m, k=k, pad1=pad1):
             gw = ops._conv_geom(n, h, w, c, ops.act_cs(x), h, w, m, p.hc1, k, k, 1, pad1, L.PAD_ZERO, wcs=ops._grad_wcs(dst_))
-            ws = ops.workspace(L.query('cat_conv2d_wgrad_ws_bytes', C.byref(gw)), dev)
-            L.call('cat_conv2d_wgrad', C.byref(gw), ops._p(x), dyp, ops._p(dst_), acc, ops._p(ws), sst)
+            U.wgrad(gw, ops._p(x), dyp, dst_, acc, sst)
         put_side(b['conv1'].weight, kw1)
     # ---- first convs: the input gradients as ONE K-concatenated launch
     dx = None
     if ctx.needs_input_grad[0]:
-        segs = []
-        for b in p.branches:
-            pad1 = (b['k'] - 1) // 2
-            segs.append(tconv.Segment(None, b['k'], pad1, False, b['d1off'], c4=b['w1'], cin=b['m'], xcs=p.hc1, ptr=dz1.data_ptr() + 4 * b['o1']))
+        segs = U.dgrad1_segs(p, dz1)
         dx = ops.empty_act(n, c, h, w, dev)
         tconv.run(segs, p.dpack1, None, dx, c, n, h, w, h, w)
     side.join()
     # ---- scatter the concatenated parameter gradients
-    all_t = [q for _, _, _, q in p.targets] + [t2[5] for t2 in p.targets2d]
-    owned = [getattr(q, '_cat_grad_view', None) is not None for q in all_t]
-    if all_t and all(owned):
-        fresh = {q._cat_grad_state['fresh'] for q in all_t}
-        if len(fresh) != 1:
-            raise RuntimeError('fused SPADE unit backward: gradient buffers of one unit out of sync')
-        views = tuple(q._cat_grad_view.data_ptr() for q in all_t)
-        if p.scatter_jobs is None or p.scatter_jobs[3] != views:
-            jobs = [dict(kind=3, srcs=[p.gv[v].data_ptr() + 4 * o, q._cat_grad_view.data_ptr()], nsrc=2, n=cnt, threads=cnt) for v, o, cnt, q in p.targets]
-            # a one-channel conv weight is stored unpadded (wcs 1): never more columns than the destination row holds
-            for v, o, rows, cols, sstr_, q in p.targets2d:
-                wcs_q = ops._grad_wcs(q._cat_grad_view)
-                cq = min(cols, wcs_q)
-                jobs.append(dict(kind=4, srcs=[p.gv[v].data_ptr() + 4 * o, q._cat_grad_view.data_ptr()], nsrc=2, n=rows * cq, cs=cq, wn=sstr_,
-                                 wcs=wcs_q, threads=rows * cq))
-            p.scatter_jobs = p._jobs_to_dev(jobs) + (views,)
-        tj, nj, nbk, _ = p.scatter_jobs
-        L.call('cat_prep_run', ops._p(tj), nj, nbk, 0 if fresh.pop() else 1, st)
-        for q in all_t:
-            q._cat_grad_state['fresh'] = False
-            grads[id(q)] = None
-    else:
-        def deliver(q, gq):
-            tgt = getattr(q, '_cat_grad_view', None)
-            if tgt is not None:
-                stq = q._cat_grad_state
-                (tgt.copy_ if stq['fresh'] else tgt.add_)(gq)
-                stq['fresh'] = False
-                gq = None
-            grads[id(q)] = gq
-        for v, o, cnt, q in p.targets:
-            flat = p.gv[v][o:o + cnt]
-            if q.dim() == 4:      # rows of the merged 1 x 1 weight gradient: back into the parameter's [O][1][1][wcs] storage
-                gq = ops.padded_weight_like(q.shape, dev)
-                torch.as_strided(gq, (cnt,), (1,), gq.storage_offset()).copy_(flat)
-            else:
-                gq = flat.clone()
-            deliver(q, gq)
-        for v, o, rows, cols, sstr_, q in p.targets2d:
-            gq = ops.padded_weight_like(q.shape, dev)
-            cols = min(cols, ops.weight_wcs(gq))
-            src2 = torch.as_strided(p.gv[v], (rows, cols), (sstr_, 1), o)
-            torch.as_strided(gq, (rows, cols), (ops.weight_wcs(gq), 1), gq.storage_offset()).copy_(src2)
-            deliver(q, gq)
+    U.scatter_param_grads(p, grads)
     return (dx, dt if ctx.has_add else None, None) + tuple(grads.get(id(q)) for q in p.params)
 
 

@@ -50,12 +50,12 @@ class InceptionSPADEGenerator(BaseNetwork):
             # one operand-preparation launch per pass for ALL fused units: their plans are grouped once they exist (second forward) and again
             # whenever a plan was rebuilt since (fused_spade.PLAN_GEN moves: a reducer's broadcast drops the plans, units become applicable
             # later) -- a plan without a group would silently fall back to one launch per unit.  The plans hold a weak reference to this module.
-            from . import fused_block, fused_spade
+            from . import fused_spade, fused_unit
             if self.__dict__.get('_cat_prep_gen') != fused_spade.PLAN_GEN:
                 units = fused_spade.units_of(self)
                 if units:
                     import weakref
-                    fused_block.prepare_plans(units, weakref.ref(self), False)
+                    fused_unit.prepare_plans(units, weakref.ref(self), False)
                 self.__dict__['_cat_prep_gen'] = fused_spade.PLAN_GEN      # also without units: the module walk is repeated only when PLAN_GEN moves
         seg = ops.conform(input)
         ret_acts = {}
