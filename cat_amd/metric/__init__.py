@@ -1,5 +1,5 @@
-"""Evaluation metrics of the distillers (reference metric/__init__.py): FID with its InceptionV3 feature extractor and the cityscapes mIoU
-with its DRN-D-105 segmentation network, both on the HIP kernels."""
+"""Evaluation metrics of the distillers (reference metric/__init__.py): FID with its InceptionV3 feature extractor, the cityscapes mIoU
+with its DRN-D-105 segmentation network and the kernel inception distance (metric/kid_score.py), all on the HIP kernels."""
 import numpy as np
 import torch
 
@@ -21,6 +21,18 @@ def get_fid(fakes, model, npz, device=None, batch_size=1, use_tqdm=True):
     ims = tensor2im_batch(torch.cat(fakes, dim=0)).astype(float)
     m2, s2 = _compute_statistics_of_ims(ims, model, batch_size, 2048, device, use_tqdm=use_tqdm)
     return float(calculate_frechet_distance(m1, s1, m2, s2))
+
+
+def get_kid(fakes, real_codes, model, device=None, batch_size=1, n_subsets=100, subset_size=100):
+    """KID of `fakes` (list of [B, 3, H, W] tensors in [-1, 1], as get_fid takes them) against `real_codes`, the [n, 2048] pool3 features of
+    the real set (kid_score.get_activations): (mean, std) of the subset estimates, as metric/kid_score.py:140-145 reports them.  The fakes
+    become uint8 images first (tensor2im_batch), so the number equals the one of the same images saved as PNG files and read by
+    calculate_kid_given_paths.  model = cat_amd.metric.InceptionV3([3]) on `device`."""
+    from . import kid_score
+    ims = tensor2im_batch(torch.cat(fakes, dim=0))
+    codes = kid_score._activations(kid_score._load_uint8(ims), len(ims), model, batch_size, real_codes.shape[1], device, False)
+    mmds = kid_score.polynomial_mmd_averages(real_codes, codes, n_subsets=n_subsets, subset_size=subset_size, ret_var=False, device=device)
+    return float(mmds.mean()), float(mmds.std())
 
 
 def get_mIoU(fakes, names, model, device, table_path='datasets/table.txt', data_dir='database/cityscapes', batch_size=1, num_workers=8,

@@ -303,6 +303,16 @@ int cat_seg_up_logsoftmax(const float* x, int xcs, int N, int h, int w, int C, c
  * across calls; label: uint8 [N][Hl][Wl] (255 = ignore); pred: uint8 [N][Hl][Wl] or NULL. */
 int cat_seg_confusion(const float* logp, int lcs, int N, int h, int w, int C, const unsigned char* label, int Hl, int Wl, int n_classes,
                       long long* hist, unsigned char* pred, cat_stream_t stream);
+/* ---- evaluation path: the kernel inception distance (metric/kid_score.py:184-281: polynomial_mmd + _mmd2_and_variance). ---- */
+/* For each of S subsets, the sums _mmd2_and_variance reads of the three polynomial kernels K = (gamma * A B^T + coef0)^degree of (X, X), (Y, Y)
+ * and (X, Y), in float64 on the f64 MFMA; no K is ever stored.  X: [nx][d], Y: [ny][d] float32 (may be one buffer), d % 4 == 0, 16-byte
+ * aligned; gi / ri: [S][m] int32 row numbers into X / Y (any order, repeats allowed; a number outside its matrix turns that row's sums into
+ * NaN).  out: [S][6 * m + 4] doubles, every one written: row sums of K_XX | diagonal of K_XX | row sums of K_YY | diagonal of K_YY | row sums
+ * of K_XY | column sums of K_XY | trace K_XY, sum K_XX^2, sum K_YY^2, sum K_XY^2.  ws: cat_kid_poly_sums_ws_bytes(S, m) bytes.  Two launches
+ * whatever S is; no atomics: the same inputs give the same bits. */
+size_t cat_kid_poly_sums_ws_bytes(int S, int m);
+int cat_kid_poly_sums(const float* X, int nx, const float* Y, int ny, int d, const int* gi, const int* ri, int S, int m, double gamma,
+                      double coef0, int degree, double* out, double* ws, cat_stream_t stream);
 /* SPADEModel.preprocess_input + get_edges (models/spade_model.py:142-179): label -> one-hot over nc channels,
  * instance ids -> 4-neighbour edge map in channel nc (inst may be NULL = --no_instance).  y: [N][H][W][cs]. */
 int cat_onehot_edges(const int* label, const int* inst, float* y, int N, int H, int W, int nc, int cs,
