@@ -143,6 +143,14 @@ SIGNATURES = {
     'cat_seg_confusion': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     'cat_kid_poly_sums_ws_bytes': (C.c_size_t, [c_i, c_i]),
     'cat_kid_poly_sums': (c_i, [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_d, c_d, c_i, c_p, c_p, c_p]),
+    'cat_fid_mean': (c_i, [c_p, c_i, c_i, c_p, c_p]),
+    'cat_fid_stats': (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),
+    'cat_fid_center_ws_bytes': (C.c_size_t, [c_i]),
+    'cat_fid_center': (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
+    'cat_gemm_f64': (c_i, [c_p, c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_d, c_d, c_p]),
+    'cat_f64_trace_sumsq_ws_bytes': (C.c_size_t, [c_i]),
+    'cat_f64_trace_sumsq': (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
+    'cat_f64_symmetrize': (c_i, [c_p, c_i, c_i, c_d, c_p, c_i, c_p]),
     'cat_conv2d_fwd_ws': (c_i, [_G, c_p, c_p, c_p, c_p, c_p, c_p]),
     'cat_conv2d_dgrad_ws_bytes': (C.c_size_t, [_G, c_i]),
     'cat_conv2d_dgrad_ws': (c_i, [_G, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),

@@ -82,10 +82,13 @@ def _track(model, value, best_attr, hist_attr, better):
     return sum(hist) / len(hist)
 
 
-def attach_fid(model, state_dict, real_stat_path=None, npz=None, dims=2048):
+def attach_fid(model, state_dict, real_stat_path=None, npz=None, dims=2048, frechet='host'):
     """What the reference's distiller __init__ does for FID (base_inception_distiller.py:218-234), with the feature extractor on the HIP kernels:
     `state_dict` = the torchvision-keyed FID checkpoint (pt_inception-2015-12-05-6726825d.pth, or a path to it); `real_stat_path` = the
-    dataset's precomputed {'mu', 'sigma'} file."""
+    dataset's precomputed {'mu', 'sigma'} file.  frechet='device' (opt-in): the Frechet distance runs on the GPU in float64 as well
+    (metric.get_fid(..., frechet='device')); the real set's mu and sigma are uploaded here, once."""
+    if frechet not in ('host', 'device'):
+        raise ValueError("attach_fid: frechet must be 'host' or 'device' (got %r)" % (frechet,))
     from ..metric import InceptionV3
     if dims != 2048:      # metric.get_fid compares pool3 features with the dataset's 2048-wide {mu, sigma} (metric/__init__.py:11-21)
         raise ValueError('attach_fid: the FID path uses the 2048-wide pool3 features (dims=%r)' % (dims,))
@@ -95,6 +98,10 @@ def attach_fid(model, state_dict, real_stat_path=None, npz=None, dims=2048):
     net.load_fid_state_dict(state_dict)
     model.inception_model = net.to(model.device).eval()
     model.npz = npz if npz is not None else np.load(real_stat_path)
+    model.fid_frechet = frechet
+    if frechet == 'device':
+        model.npz_device = {k: torch.from_numpy(np.ascontiguousarray(model.npz[k], dtype=np.float64)).to(model.device) for k in ('mu', 'sigma')}
+        model.fid_cache = {}
     return net
 
 
@@ -120,8 +127,13 @@ def evaluate(model, step, student, feed, images, want_fid, want_miou, save_all=F
     if want_fid and getattr(model, 'fid_fn', None) is None:
         if getattr(model, 'inception_model', None) is not None and getattr(model, 'npz', None) is not None:
             from .. import metric      # the reference's own call: get_fid(fakes, self.inception_model, self.npz, ...) (inception_distiller.py:246-249)
-            model.fid_fn = lambda fakes: metric.get_fid(fakes, model.inception_model, model.npz, device=model.device,
-                                                        batch_size=getattr(model.opt, 'eval_batch_size', 1), use_tqdm=False)
+            if getattr(model, 'fid_frechet', 'host') == 'device':
+                model.fid_fn = lambda fakes: metric.get_fid(fakes, model.inception_model, model.npz_device, device=model.device,
+                                                            batch_size=getattr(model.opt, 'eval_batch_size', 1), use_tqdm=False,
+                                                            frechet='device', cache=model.fid_cache)
+            else:
+                model.fid_fn = lambda fakes: metric.get_fid(fakes, model.inception_model, model.npz, device=model.device,
+                                                            batch_size=getattr(model.opt, 'eval_batch_size', 1), use_tqdm=False)
         else:
             raise RuntimeError('evaluate_model: call evaluation.attach_fid(model, fid_checkpoint, real_stat_path) or attach model.fid_fn '
                                '(cat_amd/distillers/evaluation.py)')

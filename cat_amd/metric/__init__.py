@@ -15,10 +15,19 @@ def tensor2im_batch(t):
     return np.clip((np.transpose(a, (0, 2, 3, 1)) + 1) / 2.0 * 255.0, 0, 255).astype(np.uint8)
 
 
-def get_fid(fakes, model, npz, device=None, batch_size=1, use_tqdm=True):
-    """metric/__init__.py:11-21: `fakes` = list of [B, 3, H, W] tensors in [-1, 1]; npz = {'mu', 'sigma'} of the real set."""
+def get_fid(fakes, model, npz, device=None, batch_size=1, use_tqdm=True, frechet='host', cache=None):
+    """metric/__init__.py:11-21: `fakes` = list of [B, 3, H, W] tensors in [-1, 1]; npz = {'mu', 'sigma'} of the real set.
+    frechet='host' (the default): the reference's numpy + scipy tail.  frechet='device': the features stay on the GPU and the distance is
+    float64 arithmetic on the f64 MFMA (fid_score.frechet_distance_from_features; no scipy); npz may then hold float64 device tensors, and
+    `cache` is the dict that keeps what depends on the real set alone between calls."""
+    if frechet not in ('host', 'device'):
+        raise ValueError("get_fid: frechet must be 'host' or 'device' (got %r)" % (frechet,))
     m1, s1 = npz['mu'], npz['sigma']
     ims = tensor2im_batch(torch.cat(fakes, dim=0)).astype(float)
+    if frechet == 'device':
+        from . import fid_score
+        feats = fid_score.get_activations_device(ims, model, batch_size, 2048, device)
+        return fid_score.frechet_distance_from_features(m1, s1, feats, device=device, cache=cache)
     m2, s2 = _compute_statistics_of_ims(ims, model, batch_size, 2048, device, use_tqdm=use_tqdm)
     return float(calculate_frechet_distance(m1, s1, m2, s2))
 

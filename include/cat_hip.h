@@ -313,6 +313,24 @@ int cat_seg_confusion(const float* logp, int lcs, int N, int h, int w, int C, co
 size_t cat_kid_poly_sums_ws_bytes(int S, int m);
 int cat_kid_poly_sums(const float* X, int nx, const float* Y, int ny, int d, const int* gi, const int* ri, int S, int m, double gamma,
                       double coef0, int degree, double* out, double* ws, cat_stream_t stream);
+/* ---- evaluation path: FID's statistics and Frechet distance in float64 (metric/fid_score.py:217-275; csrc/fid_ops.hip). ---- */
+/* All on the f64 MFMA or in fixed-order float64 sums: no atomics, the same inputs give the same bits; every output element is written.
+ * F: float32 [n][d] features.  cat_fid_mean: mu[d] = the column means.  cat_fid_stats: mu and sigma[d][d] = np.cov(F, rowvar=False) (centre
+ * first, then Xc^T Xc / (n - 1)), exactly symmetric; n >= 2, d % 4 == 0, F 16-byte aligned. */
+int cat_fid_mean(const float* F, int n, int d, double* mu, cat_stream_t stream);
+int cat_fid_stats(const float* F, int n, int d, double* mu, double* sigma, cat_stream_t stream);
+/* Xc[n][d] = F - mu in float64 and sumsq[0] = the sum of Xc^2; ws: cat_fid_center_ws_bytes(n) bytes. */
+size_t cat_fid_center_ws_bytes(int n);
+int cat_fid_center(const float* F, const double* mu, int n, int d, double* Xc, double* sumsq, double* ws, cat_stream_t stream);
+/* C[m][n] = alpha * A[m][k] * op(B) + beta_eye * I, row-major float64; op(B) = B[k][n] (transB = 0) or the transpose of B[n][k] (transB = 1).
+ * Any m, n, k >= 1 and leading dimensions >= the row lengths; C must not alias an operand. */
+int cat_gemm_f64(const double* A, int lda, const double* B, int ldb, int transB, double* C, int ldc, int m, int n, int k, double alpha,
+                 double beta_eye, cat_stream_t stream);
+/* out[0] = the trace of A[n][n]; out[1] = the sum of its squares if want_sumsq (ws: cat_f64_trace_sumsq_ws_bytes(n) bytes), NaN otherwise. */
+size_t cat_f64_trace_sumsq_ws_bytes(int n);
+int cat_f64_trace_sumsq(const double* A, int n, int lda, int want_sumsq, double* out, double* ws, cat_stream_t stream);
+/* out = scale * (A + A^T) / 2, exactly symmetric; out may be A. */
+int cat_f64_symmetrize(const double* A, int n, int lda, double scale, double* out, int ldo, cat_stream_t stream);
 /* SPADEModel.preprocess_input + get_edges (models/spade_model.py:142-179): label -> one-hot over nc channels,
  * instance ids -> 4-neighbour edge map in channel nc (inst may be NULL = --no_instance).  y: [N][H][W][cs]. */
 int cat_onehot_edges(const int* label, const int* inst, float* y, int N, int H, int W, int nc, int cs,
