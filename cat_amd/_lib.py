@@ -117,6 +117,13 @@ class DropGeom(C.Structure):
                [('slope', c_f), ('thresh', C.c_uint), ('s', c_f), ('drop_all', c_i), ('nseg', c_i), ('seg', DropSeg * DROP_MAXSEG)]
 
 
+LOSS_MULTI_MAX = 16
+
+
+class LossTerm(C.Structure):
+    _fields_ = [('a', c_p), ('b', c_p), ('da', c_p), ('M', c_l), ('kind', c_i), ('C', c_i), ('cs', c_i), ('target', c_f), ('scale', c_f)]
+
+
 PAD_ZERO, PAD_REFLECT = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_RELU6 = 0, 1, 2, 3, 4
 NORM_INSTANCE, NORM_BATCH = 0, 1
@@ -216,6 +223,9 @@ SIGNATURES = {
     'cat_loss_ws_bytes': (C.c_size_t, [c_l]),
     'cat_loss_fwd': (c_i, [c_i, c_p, c_p, c_f, c_l, c_i, c_i, c_p, c_p, c_p]),
     'cat_loss_bwd': (c_i, [c_i, c_p, c_p, c_f, c_l, c_i, c_i, c_p, c_f, c_p, c_p]),
+    'cat_loss_multi_ws_bytes': (C.c_size_t, [C.POINTER(LossTerm), c_i]),
+    'cat_loss_multi_fwd': (c_i, [C.POINTER(LossTerm), c_i, c_p, c_p, c_p]),
+    'cat_loss_multi_bwd': (c_i, [C.POINTER(LossTerm), c_i, C.POINTER(c_p), c_p]),
     'cat_adam_step': (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_p]),
     'cat_adam_step_dev': (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, c_f, c_p]),
     'cat_prof_enable': (None, [c_i]),

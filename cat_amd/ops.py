@@ -1061,6 +1061,63 @@ class LossFn(torch.autograd.Function):
         return da, None, None, None
 
 
+class MultiLossFn(torch.autograd.Function):
+    """T LossFn terms over unrelated tensors as ONE forward call and ONE backward call (cat_loss_multi_fwd / _bwd in include/cat_hip.h):
+    `MultiLossFn.apply(spec, a_0, b_0, a_1, b_1, ...)` with spec = ((kind, target), ...) and b_t = None where the kind has no second tensor.
+    Returns T 0-d tensors (views of one [T] buffer), each the unweighted mean LossFn would give; gradients flow to the a_t only, and only
+    for the terms whose a_t needs one and whose output received a seed."""
+
+    @staticmethod
+    def _table(spec, tensors, das):
+        tab = (L.LossTerm * len(spec))()
+        for t, (kind, target) in enumerate(spec):
+            a, b = tensors[2 * t], tensors[2 * t + 1]
+            n, c, h, w = a.shape
+            e = tab[t]
+            e.a, e.b, e.da = a.data_ptr(), (b.data_ptr() if b is not None else None), (das[t].data_ptr() if das[t] is not None else None)
+            e.M, e.kind, e.C, e.cs, e.target, e.scale = n * h * w, int(kind), c, act_cs(a), float(target), 1.0
+        return tab
+
+    @staticmethod
+    def forward(ctx, spec, *tensors):
+        T = len(spec)
+        if T < 1 or len(tensors) != 2 * T:
+            raise RuntimeError('MultiLossFn: %d terms need %d tensors (a_t, b_t or None), got %d' % (T, 2 * T, len(tensors)))
+        _require_cuda(tensors[0])
+        tensors = [None if t is None else conform(t) for t in tensors]
+        for t in range(T):
+            a, b = tensors[2 * t], tensors[2 * t + 1]
+            if b is not None and (b.shape != a.shape or act_cs(b) != act_cs(a)):
+                raise RuntimeError('loss: operands must share shape and pixel stride')
+        tab = MultiLossFn._table(spec, tensors, [None] * T)
+        out = torch.empty((T,), device=tensors[0].device, dtype=torch.float32)
+        ws = workspace(L.query('cat_loss_multi_ws_bytes', tab, T), out.device)
+        L.call('cat_loss_multi_fwd', tab, T, _p(out), _p(ws), _stream())
+        ctx.spec = tuple(spec)
+        ctx.present = tuple(t is not None for t in tensors)
+        ctx.save_for_backward(*[t for t in tensors if t is not None])
+        ctx.set_materialize_grads(False)
+        return tuple(out[t] for t in range(T))
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        saved = iter(ctx.saved_tensors)
+        tensors = [next(saved) if p else None for p in ctx.present]
+        T = len(ctx.spec)
+        das, seeds = [None] * T, (C.c_void_p * T)()
+        for t in range(T):
+            if ctx.needs_input_grad[1 + 2 * t] and gouts[t] is not None:
+                n, c, h, w = tensors[2 * t].shape
+                das[t] = empty_act(n, c, h, w, tensors[2 * t].device, act_cs(tensors[2 * t]))
+                seeds[t] = gouts[t].data_ptr()
+        if any(d is not None for d in das):
+            L.call('cat_loss_multi_bwd', MultiLossFn._table(ctx.spec, tensors, das), T, seeds, _stream())
+        grads = [None]
+        for d in das:
+            grads += [d, None]
+        return tuple(grads)
+
+
 def ka(x, y):
     return KAFn.apply(x, y)
 

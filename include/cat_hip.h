@@ -198,6 +198,27 @@ int cat_loss_fwd(int kind, const float* a, const float* b, float target, int64_t
 /* da = gout[0] * scale * dloss/da */
 int cat_loss_bwd(int kind, const float* a, const float* b, float target, int64_t M, int C, int cs,
                  const float* gout, float scale, float* da, cat_stream_t stream);
+/* T such losses over unrelated tensors in one launch sequence (the loss head of a multiscale discriminator: num_D * (n_layers_D + 1)
+ * feature-matching / GAN terms of a few microseconds each).  The host table is copied into the kernel arguments CAT_LOSS_MULTI_MAX terms at
+ * a time (larger tables are chunked): no device allocation, no host synchronisation, capturable.
+ *   cat_loss_multi_fwd: out[t] = the unweighted mean of term t over its M*C real elements (never the cs - C pad lanes); two launches per
+ *     chunk: per-term partials into `ws` (>= cat_loss_multi_ws_bytes), then a fixed-order final sum.  No atomics: bit-identical run to run,
+ *     and out[t] equals what cat_loss_fwd gives for the term alone.  `da` and `scale` are not read.
+ *   cat_loss_multi_bwd: da_t = gout[t][0] * scale_t * dloss_t/da for the terms with da != NULL, pad lanes written as 0 like cat_loss_bwd;
+ *     one launch per chunk.  `gout` is a HOST array of T device pointers (one float each; not read where da == NULL).  Terms with
+ *     da == NULL are skipped: nothing of theirs is read or written. */
+#define CAT_LOSS_MULTI_MAX 16
+typedef struct {
+  const float* a;
+  const float* b; /* second tensor of kinds 0 and 5, NULL otherwise */
+  float* da;
+  int64_t M;
+  int kind, C, cs;
+  float target, scale;
+} cat_loss_term_t;
+size_t cat_loss_multi_ws_bytes(const cat_loss_term_t* terms, int T);
+int cat_loss_multi_fwd(const cat_loss_term_t* terms, int T, float* out, void* ws, cat_stream_t stream);
+int cat_loss_multi_bwd(const cat_loss_term_t* terms, int T, const float* const* gout, cat_stream_t stream);
 
 /* Adam step over one flat buffer (torch.optim.Adam semantics, base_inception_distiller.py:205-214):
  * p, g, m, v: n floats; step = 1-based step count. */
