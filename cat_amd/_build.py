@@ -34,7 +34,7 @@ def build(force=False, verbose=True, diag=False):
     """diag=True: the DIAGNOSTIC build (-DCAT_DIAG, common.h kDiag) into lib/libcat_hip_diag.so -- per-phase shader clocks and the
     ablation switches that make results wrong by design; only tools/debug/* load it (CAT_LIB=diag).  Never built by build() / the driver."""
     os.makedirs(LIBDIR, exist_ok=True)
-    hdrs = [os.path.join(CSRC, 'common.h'), os.path.join(HERE, '..', 'include', 'cat_hip.h')]
+    hdrs = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'mfma_f64.h'), os.path.join(HERE, '..', 'include', 'cat_hip.h')]
     hipcc = _hipcc()
     objs, jobs = [], []
     for s in SOURCES:

@@ -8,26 +8,20 @@
 //                                  Newton-Schulz iteration for the matrix square root is made of (T = 1.5 I - 0.5 Z Y, Y <- Y T, Z <- T Z).
 //   cat_f64_trace_sumsq, cat_f64_symmetrize, cat_fid_center   the small float64 kernels between the products.
 //
-// Tiles as kid_ops.hip: a workgroup of 256 threads = 4 waves as 2 x 2; operands staged in LDS as doubles, the next K step's operands fetched
-// while the current one is multiplied.  An operand whose K index is contiguous in memory lies in LDS as [row][32 + 2] (the pad keeps the
-// one-double-per-lane reads of a half wave on distinct banks); one whose K index is the slow one lies as [k][tile + 16] for the same reason.
+// Tiles: mfma_f64.h.  An operand whose K index is contiguous in memory lies in LDS as KContig, one whose K index is the slow one as KMajor.
 // Rows, columns and K indices beyond the matrix are staged as zeros.
 //
 // Order of every sum is fixed (the MFMA's walk over K, per-thread walks, fixed LDS trees, a fixed walk over per-block partials): no atomics,
 // the same inputs give the same bits.  Every output element is written.
-//
-// f64 MFMA fragments: A[i][k] / B[k][j] with i, j = lane & 15 and k = lane >> 4, one double per lane; D[row][col] with col = lane & 15 and
-// row = (lane >> 4) + 4 * reg -- not the float32 forms' (lane >> 4) * 4 + reg.
-#include "common.h"
+#include "mfma_f64.h"
 
 namespace {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
+using cat::d4;
 
-constexpr int FID_BK = 32;               // K indices per staging step
-constexpr int FID_LDK = FID_BK + 2;      // LDS row stride of a [row][k] operand, in doubles
+constexpr int FID_BK = cat::BK;          // K indices per staging step
 constexpr int FID_CT = 64;               // covariance tile
-constexpr int FID_CLD = FID_CT + 16;     // LDS row stride of a [k][col] operand of the covariance tile
+using CovLds = cat::KMajor<FID_CT>;      // both operands of the covariance tile: the K index is the row of F
 constexpr int FID_SS_ROWS = 16;          // rows per block of the sum-of-squares pass
 
 // ------------------------------------------------------------------------------------------------------------------ column means
@@ -65,10 +59,10 @@ __global__ __launch_bounds__(256) void fid_cov_kernel(const float* __restrict__ 
                                                       double* __restrict__ sigma) {
   const int ti = blockIdx.y, tj = blockIdx.x;
   if (tj < ti) return;
-  __shared__ __attribute__((aligned(16))) double As[FID_BK * FID_CLD];
-  __shared__ __attribute__((aligned(16))) double Bs[FID_BK * FID_CLD];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wi = wave >> 1, wj = wave & 1;
-  const int fr = lane & 15, fk = lane >> 4;
+  __shared__ __attribute__((aligned(16))) double As[CovLds::SIZE];
+  __shared__ __attribute__((aligned(16))) double Bs[CovLds::SIZE];
+  const int t = threadIdx.x;
+  const cat::TileCoords c(t);
   const int sr = t >> 4, sc = (t & 15) * 4;
   const int ca = ti * FID_CT + sc, cb = tj * FID_CT + sc;
   double ma[4], mb[4];
@@ -77,58 +71,32 @@ __global__ __launch_bounds__(256) void fid_cov_kernel(const float* __restrict__ 
     ma[e] = ca < d ? mu[ca + e] : 0.0;      // d % 4 == 0: a quad is inside or outside as a whole
     mb[e] = cb < d ? mu[cb + e] : 0.0;
   }
-  d4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
-  const int nk = (n + FID_BK - 1) / FID_BK;
-  CovQuad a0 = cov_fetch(F, n, d, sr, ca), a1 = cov_fetch(F, n, d, sr + 16, ca);
-  CovQuad b0 = cov_fetch(F, n, d, sr, cb), b1 = cov_fetch(F, n, d, sr + 16, cb);
-  for (int kc = 0; kc < nk; ++kc) {
-    __syncthreads();   // the previous step's operand reads are done
-    cov_stage(As + sr * FID_CLD + sc, a0, ma);
-    cov_stage(As + (sr + 16) * FID_CLD + sc, a1, ma);
-    cov_stage(Bs + sr * FID_CLD + sc, b0, mb);
-    cov_stage(Bs + (sr + 16) * FID_CLD + sc, b1, mb);
-    __syncthreads();
-    if (kc + 1 < nk) {
-      const int r = (kc + 1) * FID_BK + sr;
-      a0 = cov_fetch(F, n, d, r, ca);
-      a1 = cov_fetch(F, n, d, r + 16, ca);
-      b0 = cov_fetch(F, n, d, r, cb);
-      b1 = cov_fetch(F, n, d, r + 16, cb);
-    }
-#pragma unroll
-    for (int ks = 0; ks < FID_BK / 4; ++ks) {
-      double a[2], b[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        a[i] = As[(ks * 4 + fk) * FID_CLD + wi * 32 + i * 16 + fr];
-        b[i] = Bs[(ks * 4 + fk) * FID_CLD + wj * 32 + i * 16 + fr];
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-  }
+  d4 acc[2][2] = {};
+  CovQuad a0, a1, b0, b1;
+  cat::pipeline((n + FID_BK - 1) / FID_BK,
+      [&] {
+        cov_stage(As + CovLds::index(sc, sr), a0, ma);
+        cov_stage(As + CovLds::index(sc, sr + 16), a1, ma);
+        cov_stage(Bs + CovLds::index(sc, sr), b0, mb);
+        cov_stage(Bs + CovLds::index(sc, sr + 16), b1, mb);
+      },
+      [&](int kc) {
+        const int r = kc * FID_BK + sr;
+        a0 = cov_fetch(F, n, d, r, ca);
+        a1 = cov_fetch(F, n, d, r + 16, ca);
+        b0 = cov_fetch(F, n, d, r, cb);
+        b1 = cov_fetch(F, n, d, r + 16, cb);
+      },
+      [&] { cat::mma_step(acc, As, Bs, CovLds(), CovLds(), c); });
   const double inv = 1.0 / (double)(n - 1);
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = ti * FID_CT + wi * 32 + i * 16 + fk + 4 * r;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = tj * FID_CT + wj * 32 + j * 16 + fr;
-        if (row < d && col < d && col >= row) {      // the diagonal tile's lower half is the mirror of its upper half
-          const double v = acc[i][j][r] * inv;
-          sigma[(int64_t)row * d + col] = v;
-          if (col > row) sigma[(int64_t)col * d + row] = v;
-        }
-      }
+  cat::for_each_acc(acc, c, [=](int, int, int, int lrow, int lcol, double g) {
+    const int row = ti * FID_CT + lrow, col = tj * FID_CT + lcol;
+    if (row < d && col < d && col >= row) {      // the diagonal tile's lower half is the mirror of its upper half
+      const double v = g * inv;
+      sigma[(int64_t)row * d + col] = v;
+      if (col > row) sigma[(int64_t)col * d + row] = v;
     }
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------------ GEMM
@@ -140,18 +108,18 @@ __global__ __launch_bounds__(256) void fid_gemm_kernel(const double* __restrict_
                                                        double beta_eye) {
   constexpr int BT = 32 * TM;                      // tile rows = tile columns
   constexpr int NE = BT * FID_BK / 256;            // doubles per thread, operand and step
-  constexpr int LDN = BT + 16;                     // row stride of a [k][col] operand
-  constexpr int BSZ = BT * FID_LDK > FID_BK * LDN ? BT * FID_LDK : FID_BK * LDN;
-  __shared__ __attribute__((aligned(16))) double As[BT * FID_LDK];
-  __shared__ __attribute__((aligned(16))) double Bs[BSZ];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wi = wave >> 1, wj = wave & 1;
-  const int fr = lane & 15, fk = lane >> 4;
+  using LK = cat::KContig<BT>;                     // A, and B if transB
+  using LN = cat::KMajor<BT>;                      // B otherwise
+  __shared__ __attribute__((aligned(16))) double As[LK::SIZE];
+  __shared__ __attribute__((aligned(16))) double Bs[LK::SIZE > LN::SIZE ? LK::SIZE : LN::SIZE];
+  const int t = threadIdx.x;
+  const cat::TileCoords c(t);
   const int row0 = blockIdx.y * BT, col0 = blockIdx.x * BT;
   // K-contiguous operand: element e = t + 256 i is row e >> 5, k index e & 31.  [k][n] operand: k index e / BT, column e % BT.
   const int ar = t >> 5, ak = t & 31;
   const int bk = transB ? ak : t / BT, bc = transB ? ar : t % BT;
   constexpr int BSTEP = 256 / BT;                  // k indices between a thread's elements of a [k][n] operand
-  const int bs_c = transB ? FID_LDK : 1, bs_k = transB ? 1 : LDN;      // LDS strides of B's column and k index
+  const cat::Strided lb{transB ? LK::LD : 1, transB ? 1 : LN::LD};      // LDS strides of B's column and k index
 
   auto fetch_a = [&](int k0, int i) -> double {
     const int r = row0 + ar + 8 * i, kk = k0 + ak;
@@ -166,61 +134,31 @@ __global__ __launch_bounds__(256) void fid_gemm_kernel(const double* __restrict_
     return (c < n && kk < k) ? B[(int64_t)kk * ldb + c] : 0.0;
   };
 
-  d4 acc[TM][TM];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TM; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+  d4 acc[TM][TM] = {};
   double va[NE], vb[NE];
+  cat::pipeline((k + FID_BK - 1) / FID_BK,
+      [=, &va, &vb] {      // scalars by value (mfma_f64.h): by reference the two B stores become one with a selected address
 #pragma unroll
-  for (int i = 0; i < NE; ++i) {
-    va[i] = fetch_a(0, i);
-    vb[i] = fetch_b(0, i);
-  }
-  const int nk = (k + FID_BK - 1) / FID_BK;
-  for (int kc = 0; kc < nk; ++kc) {
-    __syncthreads();   // the previous step's operand reads are done
+        for (int i = 0; i < NE; ++i) {
+          As[LK::index(ar + 8 * i, ak)] = va[i];
+          if (transB)
+            Bs[LK::index(bc + 8 * i, bk)] = vb[i];
+          else
+            Bs[LN::index(bc, bk + BSTEP * i)] = vb[i];
+        }
+      },
+      [&](int kc) {
 #pragma unroll
-    for (int i = 0; i < NE; ++i) {
-      As[(ar + 8 * i) * FID_LDK + ak] = va[i];
-      if (transB)
-        Bs[(bc + 8 * i) * FID_LDK + bk] = vb[i];
-      else
-        Bs[(bk + BSTEP * i) * LDN + bc] = vb[i];
-    }
-    __syncthreads();
-    if (kc + 1 < nk) {
-#pragma unroll
-      for (int i = 0; i < NE; ++i) {
-        va[i] = fetch_a((kc + 1) * FID_BK, i);
-        vb[i] = fetch_b((kc + 1) * FID_BK, i);
-      }
-    }
-#pragma unroll
-    for (int ks = 0; ks < FID_BK / 4; ++ks) {
-      double a[TM], b[TM];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        a[i] = As[(wi * 16 * TM + i * 16 + fr) * FID_LDK + ks * 4 + fk];
-        b[i] = Bs[(wj * 16 * TM + i * 16 + fr) * bs_c + (ks * 4 + fk) * bs_k];
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TM; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = row0 + wi * 16 * TM + i * 16 + fk + 4 * r;
-#pragma unroll
-      for (int j = 0; j < TM; ++j) {
-        const int col = col0 + wj * 16 * TM + j * 16 + fr;
-        if (row < m && col < n) C[(int64_t)row * ldc + col] = alpha * acc[i][j][r] + (row == col ? beta_eye : 0.0);
-      }
-    }
+        for (int i = 0; i < NE; ++i) {
+          va[i] = fetch_a(kc * FID_BK, i);
+          vb[i] = fetch_b(kc * FID_BK, i);
+        }
+      },
+      [&] { cat::mma_step(acc, As, Bs, LK(), lb, c); });
+  cat::for_each_acc(acc, c, [=](int, int, int, int lrow, int lcol, double g) {
+    const int row = row0 + lrow, col = col0 + lcol;
+    if (row < m && col < n) C[(int64_t)row * ldc + col] = alpha * g + (row == col ? beta_eye : 0.0);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------------ small kernels

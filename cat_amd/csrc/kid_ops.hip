@@ -5,12 +5,10 @@
 // and never writes a K:
 //
 //   grid (P, 4, S): P = ceil(m / 64) row panels x 4 products (XX, YY, XY and YX, whose row sums are the COLUMN sums of K_XY) x S subsets.
-//   One workgroup (256 threads = 4 waves as 2 x 2, each wave a 32 x 32 block of 2 x 2 MFMA tiles) owns 64 rows of one product and walks
-//   all P column chunks of 64.  Per chunk the Gram block accumulates over the whole feature width in steps of BK = 32: the gathered float32
-//   rows are widened to float64 on their way into LDS ([64][32 + 2] doubles per operand; the pad keeps the one-double-per-lane operand
-//   reads of a half wave on distinct banks), the next step's rows are fetched while the current one is multiplied.  The epilogue raises
-//   every Gram value to K in registers and adds it to the lane's row sums / sum of squares; rows and columns at or beyond m are staged as
-//   zeros AND masked out of the epilogue (K of a zero Gram value is coef0^degree, not 0).
+//   One workgroup (the 64 x 64 tile of mfma_f64.h, TM = 2) owns 64 rows of one product and walks all P column chunks of 64.  Per chunk the
+//   Gram block accumulates over the whole feature width: the gathered float32 rows are widened to float64 on their way into LDS, both
+//   operands K-contiguous.  The epilogue raises every Gram value to K in registers and adds it to the lane's row sums / sum of squares; rows
+//   and columns at or beyond m are staged as zeros AND masked out of the epilogue (K of a zero Gram value is coef0^degree, not 0).
 //
 // Float64 because mmd2 is a difference of order 1e-2 between means of order 1..10, and the variance estimate cancels harder still: a float32
 // restatement differs from the reference by up to 8e-5 relative in the variance.
@@ -18,19 +16,16 @@
 // Order of every sum is fixed (per lane over chunks, xor butterflies inside a wave, a fixed walk over LDS between waves, kid_finish_kernel's
 // fixed walk over the per-panel partials): no atomics, results repeat bit for bit.  An index outside its feature matrix reads nothing and
 // poisons its row with NaN instead.
-//
-// f64 MFMA fragments: A[i][k] / B[k][j] with i, j = lane & 15 and k = lane >> 4, one double per lane; D[row][col] with col = lane & 15 and
-// row = (lane >> 4) + 4 * reg -- not the float32 forms' (lane >> 4) * 4 + reg.
-#include "common.h"
+#include "mfma_f64.h"
 
 namespace {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
+using cat::d2;
+using cat::d4;
 
 constexpr int KID_BM = 64;             // rows (and columns) of a block
-constexpr int KID_BK = 32;             // feature columns per staging step
-constexpr int KID_LDK = KID_BK + 2;    // LDS row stride in doubles
+constexpr int KID_BK = cat::BK;        // feature columns per staging step
+using KidLds = cat::KContig<KID_BM>;   // both operands: the feature index is contiguous
 constexpr int KID_SCALARS = 4;         // trace K_XY, sum K_XX^2, sum K_YY^2, sum K_XY^2
 
 struct KidRow {
@@ -61,12 +56,13 @@ __device__ __forceinline__ void kid_stage(double* dst, const f4& v) {
 __global__ __launch_bounds__(256) void kid_poly_panel_kernel(const float* __restrict__ X, int nx, const float* __restrict__ Y, int ny, int d,
                                                              const int* __restrict__ gi, const int* __restrict__ ri, int m, int P, double gamma,
                                                              double coef0, int degree, double* __restrict__ out, double* __restrict__ ws) {
-  __shared__ __attribute__((aligned(16))) double As[KID_BM * KID_LDK];
-  __shared__ __attribute__((aligned(16))) double Bs[KID_BM * KID_LDK];
+  __shared__ __attribute__((aligned(16))) double As[KidLds::SIZE];
+  __shared__ __attribute__((aligned(16))) double Bs[KidLds::SIZE];
   __shared__ double red[2 * KID_BM];
   __shared__ double dg[KID_BM];
   __shared__ double wred[4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wi = wave >> 1, wj = wave & 1;
+  const int t = threadIdx.x;
+  const cat::TileCoords c(t);
   const int panel = blockIdx.x, prod = blockIdx.y, s = blockIdx.z;
   const bool ax = prod == 0 || prod == 2, bx = prod == 0 || prod == 3;
   const float* A = ax ? X : Y;
@@ -80,64 +76,39 @@ __global__ __launch_bounds__(256) void kid_poly_panel_kernel(const float* __rest
   const KidRow a0 = kid_row(A, na, d, ta, row0 + sr0, m), a1 = kid_row(A, na, d, ta, row0 + sr1, m);
   if (t < KID_BM) dg[t] = 0.0;
   const int nk = (d + KID_BK - 1) / KID_BK;
-  const int fr = lane & 15, fk = lane >> 4;
   double rs[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
   double sq = 0.0;
   for (int cb = 0; cb < P; ++cb) {
     const int col0 = cb * KID_BM;
     const KidRow b0 = kid_row(B, nb, d, tb, col0 + sr0, m), b1 = kid_row(B, nb, d, tb, col0 + sr1, m);
-    d4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
-    f4 va0 = kid_fetch(a0, sk, d), va1 = kid_fetch(a1, sk, d), vb0 = kid_fetch(b0, sk, d), vb1 = kid_fetch(b1, sk, d);
-    for (int kc = 0; kc < nk; ++kc) {
-      __syncthreads();   // the previous step's operand reads are done
-      kid_stage(As + sr0 * KID_LDK + sk, va0);
-      kid_stage(As + sr1 * KID_LDK + sk, va1);
-      kid_stage(Bs + sr0 * KID_LDK + sk, vb0);
-      kid_stage(Bs + sr1 * KID_LDK + sk, vb1);
-      __syncthreads();
-      if (kc + 1 < nk) {
-        const int k = (kc + 1) * KID_BK + sk;
-        va0 = kid_fetch(a0, k, d);
-        va1 = kid_fetch(a1, k, d);
-        vb0 = kid_fetch(b0, k, d);
-        vb1 = kid_fetch(b1, k, d);
-      }
-#pragma unroll
-      for (int ks = 0; ks < KID_BK / 4; ++ks) {
-        double a[2], b[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          a[i] = As[(wi * 32 + i * 16 + fr) * KID_LDK + ks * 4 + fk];
-          b[i] = Bs[(wj * 32 + i * 16 + fr) * KID_LDK + ks * 4 + fk];
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int lrow = wi * 32 + i * 16 + fk + 4 * r, grow = row0 + lrow;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int gcol = col0 + wj * 32 + j * 16 + fr;
-          const double v = gamma * acc[i][j][r] + coef0;
-          double k = v;
-          for (int e = 1; e < degree; ++e) k *= v;
-          const bool in = grow < m && gcol < m;
-          k = in ? k : 0.0;
-          rs[i][r] += k;
-          sq += k * k;
-          if (in && grow == gcol) dg[lrow] = k;
-        }
-      }
+    d4 acc[2][2] = {};
+    f4 va0, va1, vb0, vb1;
+    cat::pipeline(nk,
+        [&] {
+          kid_stage(As + KidLds::index(sr0, sk), va0);
+          kid_stage(As + KidLds::index(sr1, sk), va1);
+          kid_stage(Bs + KidLds::index(sr0, sk), vb0);
+          kid_stage(Bs + KidLds::index(sr1, sk), vb1);
+        },
+        [&](int kc) {
+          const int k = kc * KID_BK + sk;
+          va0 = kid_fetch(a0, k, d);
+          va1 = kid_fetch(a1, k, d);
+          vb0 = kid_fetch(b0, k, d);
+          vb1 = kid_fetch(b1, k, d);
+        },
+        [&] { cat::mma_step(acc, As, Bs, KidLds(), KidLds(), c); });
+    cat::for_each_acc(acc, c, [&](int i, int r, int, int lrow, int lcol, double g) {
+      const int grow = row0 + lrow, gcol = col0 + lcol;
+      const double v = gamma * g + coef0;
+      double k = v;
+      for (int e = 1; e < degree; ++e) k *= v;
+      const bool in = grow < m && gcol < m;
+      k = in ? k : 0.0;
+      rs[i][r] += k;
+      sq += k * k;
+      if (in && grow == gcol) dg[lrow] = k;
+    });
   }
   // row sums: the 16 lanes that share a row, then the two waves that share it
 #pragma unroll
@@ -147,11 +118,11 @@ __global__ __launch_bounds__(256) void kid_poly_panel_kernel(const float* __rest
       double v = rs[i][r];
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-      if (fr == 0) red[wj * KID_BM + wi * 32 + i * 16 + fk + 4 * r] = v;
+      if (c.fr == 0) red[c.wj * KID_BM + c.wi * 32 + i * 16 + c.fk + 4 * r] = v;
     }
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) sq += __shfl_xor(sq, o, 64);
-  if (lane == 0) wred[wave] = sq;
+  if (c.lane == 0) wred[c.wave] = sq;
   __syncthreads();
   double* o = out + (int64_t)s * (6 * (int64_t)m + KID_SCALARS);
   if (t < KID_BM && row0 + t < m) {

@@ -89,14 +89,10 @@ def attach_fid(model, state_dict, real_stat_path=None, npz=None, dims=2048, frec
     (metric.get_fid(..., frechet='device')); the real set's mu and sigma are uploaded here, once."""
     if frechet not in ('host', 'device'):
         raise ValueError("attach_fid: frechet must be 'host' or 'device' (got %r)" % (frechet,))
-    from ..metric import InceptionV3
+    from ..metric.features import load_inception
     if dims != 2048:      # metric.get_fid compares pool3 features with the dataset's 2048-wide {mu, sigma} (metric/__init__.py:11-21)
         raise ValueError('attach_fid: the FID path uses the 2048-wide pool3 features (dims=%r)' % (dims,))
-    if isinstance(state_dict, (str, bytes, os.PathLike)):
-        state_dict = torch.load(state_dict, map_location='cpu')
-    net = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]])
-    net.load_fid_state_dict(state_dict)
-    model.inception_model = net.to(model.device).eval()
+    model.inception_model = net = load_inception(dims, state_dict, model.device, 'FID')
     model.npz = npz if npz is not None else np.load(real_stat_path)
     model.fid_frechet = frechet
     if frechet == 'device':

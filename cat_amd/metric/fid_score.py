@@ -13,37 +13,34 @@ import os
 import numpy as np
 import torch
 
+from .features import add_inception_arguments, default_device, feature_batches, load_inception
+
 NS_MAX_STEPS = 100          # cap of the Newton-Schulz iteration
 NS_REL_STEP = 1e-14         # a step counts while the trace still grows by more than this, relative
+
+
+def _scaled(ims):
+    """load(start, end) over float images [N, H, W, 3] (or [N, 3, H, W]) in [0, 255]: the NCHW view of a slice, scaled IN PLACE"""
+    def load(start, end):
+        images = ims[start:end] if ims.shape[1] == 3 else ims[start:end].transpose((0, 3, 1, 2))
+        images /= 255
+        return images
+    return load
 
 
 def get_activations_from_ims(ims, model, batch_size=50, dims=2048, device=None, verbose=False, use_tqdm=True):
     """metric/fid_score.py:152-216.  ims: float array [N, H, W, 3] (or [N, 3, H, W]) in [0, 255] -- it is scaled IN PLACE like the reference
     does (`images /= 255` on a view); returns [N, dims] float64 features.  Same batching (the last batch may be short)."""
-    model.eval()
-    device = device if device is not None else torch.device('cuda', torch.cuda.current_device())
-    n_batches = (len(ims) + batch_size - 1) // batch_size
-    pred_arr = np.empty((len(ims), dims))
-    it = range(n_batches)
+    batches = feature_batches(_scaled(ims), len(ims), model, batch_size, default_device(device))
     if use_tqdm:
         try:
             from tqdm import tqdm
-            it = tqdm(it)
+            batches = tqdm(batches, total=(len(ims) + batch_size - 1) // batch_size)
         except ImportError:
             pass
-    for i in it:
-        start, end = i * batch_size, min((i + 1) * batch_size, len(ims))
-        images = ims[start:end]
-        if images.shape[1] != 3:
-            images = images.transpose((0, 3, 1, 2))
-        images /= 255
-        batch = torch.from_numpy(images).type(torch.FloatTensor).to(device)
-        with torch.no_grad():
-            pred = model(batch)[0]
-        if pred.shape[2] != 1 or pred.shape[3] != 1:      # a block below pool3 was selected: adaptive_avg_pool2d(pred, (1, 1))
-            from .inception import GlobalAvgPool
-            pred = GlobalAvgPool()(pred)
-        pred_arr[start:end] = pred.cpu().data.numpy().reshape(end - start, -1)
+    pred_arr = np.empty((len(ims), dims))
+    for start, end, feats in batches:
+        pred_arr[start:end] = feats.cpu().numpy()
     if verbose:
         print(' done')
     return pred_arr
@@ -84,30 +81,13 @@ def _compute_statistics_of_ims(ims, model, batch_size, dims, device, use_tqdm=Tr
 
 
 # ---------------------------------------------------------------------------------------------------------------- the tail on the device
-def _default_device(device):
-    return torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-
-
 def get_activations_device(ims, model, batch_size=50, dims=2048, device=None):
     """The loop of get_activations_from_ims -- the same batching, the same in-place `/= 255` -- with the float32 [N, dims] features returned
     as ONE device tensor.  The network's outputs are float32, which the host path widens to float64: nothing is lost."""
-    model.eval()
-    device = _default_device(device)
-    n_batches = (len(ims) + batch_size - 1) // batch_size
+    device = default_device(device)
     feats = torch.empty((len(ims), dims), dtype=torch.float32, device=device)
-    for i in range(n_batches):
-        start, end = i * batch_size, min((i + 1) * batch_size, len(ims))
-        images = ims[start:end]
-        if images.shape[1] != 3:
-            images = images.transpose((0, 3, 1, 2))
-        images /= 255
-        batch = torch.from_numpy(images).type(torch.FloatTensor).to(device)
-        with torch.no_grad():
-            pred = model(batch)[0]
-        if pred.shape[2] != 1 or pred.shape[3] != 1:
-            from .inception import GlobalAvgPool
-            pred = GlobalAvgPool()(pred)
-        feats[start:end] = pred.reshape(end - start, -1)
+    for start, end, f in feature_batches(_scaled(ims), len(ims), model, batch_size, device):
+        feats[start:end] = f
     return feats
 
 
@@ -150,48 +130,54 @@ def _host(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
+def _call(name, *args):
+    """A library entry on the current stream, tensors as their pointers.  Imported on first use: the argument checks need no library."""
+    from .. import _lib, ops
+    _lib.call(name, *[ops._p(a) if isinstance(a, torch.Tensor) else a for a in args], ops._stream())
+
+
+def _query(name, *args):
+    from .. import _lib
+    return _lib.query(name, *args)
+
+
+def _require_cuda(t):
+    from .. import ops
+    ops._require_cuda(t)
+
+
 def _gemm(a, b, trans_b=False, alpha=1.0, beta_eye=0.0, out=None):
     """cat_gemm_f64 on contiguous float64 device matrices: alpha * a @ (b.T if trans_b else b) + beta_eye * I"""
-    from .. import _lib as L
-    from .. import ops
     m, k = a.shape
     n = b.shape[0] if trans_b else b.shape[1]
     assert (b.shape[1] if trans_b else b.shape[0]) == k and a.is_contiguous() and b.is_contiguous()
     if out is None:
         out = torch.empty((m, n), dtype=torch.float64, device=a.device)
-    L.call('cat_gemm_f64', ops._p(a), a.shape[1], ops._p(b), b.shape[1], int(trans_b), ops._p(out), out.shape[1], m, n, k, float(alpha),
-           float(beta_eye), ops._stream())
+    _call('cat_gemm_f64', a, a.shape[1], b, b.shape[1], int(trans_b), out, out.shape[1], m, n, k, float(alpha), float(beta_eye))
     return out
 
 
 def _trace_sumsq(a, want_sumsq, out, ws):
     """(trace, sum of squares or NaN) of a square device matrix as two Python floats: a 16-byte copy"""
-    from .. import _lib as L
-    from .. import ops
-    L.call('cat_f64_trace_sumsq', ops._p(a), a.shape[0], a.shape[1], int(want_sumsq), ops._p(out), ops._p(ws), ops._stream())
-    tr, ss = out.tolist()
-    return tr, ss
+    _call('cat_f64_trace_sumsq', a, a.shape[0], a.shape[1], int(want_sumsq), out, ws)
+    return tuple(out.tolist())
 
 
 def _symmetrize(a, scale=1.0, out=None):
-    from .. import _lib as L
-    from .. import ops
     out = a if out is None else out
-    L.call('cat_f64_symmetrize', ops._p(a), a.shape[0], a.shape[1], float(scale), ops._p(out), out.shape[1], ops._stream())
+    _call('cat_f64_symmetrize', a, a.shape[0], a.shape[1], float(scale), out, out.shape[1])
     return out
 
 
 def statistics_device(feats):
     """(mu [d], sigma [d, d]) of float32 device features as float64 device tensors: np.mean(axis=0) and np.cov(rowvar=False) by cat_fid_stats"""
-    from .. import _lib as L
-    from .. import ops
     n, d = _check_features(feats)
-    ops._require_cuda(feats)
+    _require_cuda(feats)
     feats = feats.contiguous()
     mu = torch.empty(d, dtype=torch.float64, device=feats.device)
     sigma = torch.empty((d, d), dtype=torch.float64, device=feats.device)
     with torch.cuda.device(feats.device):
-        L.call('cat_fid_stats', ops._p(feats), n, d, ops._p(mu), ops._p(sigma), ops._stream())
+        _call('cat_fid_stats', feats, n, d, mu, sigma)
     return mu, sigma
 
 
@@ -206,11 +192,10 @@ def _newton_schulz(m_sym):
     the iteration is unstable once it has converged, so it stops at the first step whose trace is not finite or does not exceed the
     previous one by more than 1e-14 relative, and keeps the iterate with the larger finite trace.
     Returns (Y or None, c, Tr Y, steps, converged): converged is False at the cap or on a non-finite trace."""
-    from .. import _lib as L
     n = m_sym.shape[0]
     dev = m_sym.device
     out = torch.empty(2, dtype=torch.float64, device=dev)
-    ws = torch.empty(max(1, L.query('cat_f64_trace_sumsq_ws_bytes', n) // 8), dtype=torch.float64, device=dev)
+    ws = torch.empty(max(1, _query('cat_f64_trace_sumsq_ws_bytes', n) // 8), dtype=torch.float64, device=dev)
     _, ss = _trace_sumsq(m_sym, True, out, ws)
     if not np.isfinite(ss):
         return None, float('nan'), float('nan'), 0, False
@@ -240,8 +225,7 @@ def sqrtm_trace_device(M):
     steps, or a non-finite value) means the trace must not be used."""
     if not isinstance(M, torch.Tensor) or M.dim() != 2 or M.shape[0] != M.shape[1] or M.dtype != torch.float64:
         raise ValueError('sqrtm_trace_device: a square float64 device matrix is required')
-    from .. import ops
-    ops._require_cuda(M)
+    _require_cuda(M)
     with torch.cuda.device(M.device):
         _, c, tr, steps, ok = _newton_schulz(M.contiguous())
     return float(np.sqrt(c) * tr) if ok else float('nan'), steps, ok
@@ -258,6 +242,13 @@ def _root_device(sigma):
 def _trace_device(a):
     out = torch.empty(2, dtype=torch.float64, device=a.device)      # without the sum of squares the workspace is not used
     return _trace_sumsq(a, False, out, out)[0]
+
+
+def _real_side(cache, sigma1, device):      # (sigma1 on the device, its trace): uploaded and taken once per `cache`
+    if 'sigma1' not in cache:
+        cache['sigma1'] = _f64_device(sigma1, device)
+        cache['tr1'] = _trace_device(cache['sigma1'])
+    return cache['sigma1'], cache['tr1']
 
 
 def _full_form(sigma1, sigma2, cache):
@@ -285,28 +276,23 @@ def frechet_distance_from_features(mu1, sigma1, feats2, device=None, cache=None,
     form.  cache: a dict the caller keeps per real set -- the uploaded sigma1, its trace and, in the full form, its root are computed once.
     info: a dict that receives `form`, `steps`, `converged`.  Falls back to the host calculate_frechet_distance, with a warning, if the
     iteration does not converge."""
-    from .. import _lib as L
-    from .. import ops
     n, d = _check_features(feats2)
     _check_stats(mu1, sigma1, d)
-    ops._require_cuda(feats2)
+    _require_cuda(feats2)
     device = feats2.device if device is None else torch.device(device)
     cache = {} if cache is None else cache
     info = {} if info is None else info
     feats2 = feats2.contiguous()
     with torch.cuda.device(device):
-        if 'sigma1' not in cache:
-            cache['sigma1'] = _f64_device(sigma1, device)
-            cache['tr1'] = _trace_device(cache['sigma1'])
-        s1, tr1 = cache['sigma1'], cache['tr1']
+        s1, tr1 = _real_side(cache, sigma1, device)
         if n <= d:
             info['form'] = 'gram'
             mu2 = torch.empty(d, dtype=torch.float64, device=device)
-            L.call('cat_fid_mean', ops._p(feats2), n, d, ops._p(mu2), ops._stream())
+            _call('cat_fid_mean', feats2, n, d, mu2)
             xc = torch.empty((n, d), dtype=torch.float64, device=device)
             ss = torch.empty(1, dtype=torch.float64, device=device)
-            ws = torch.empty(max(1, L.query('cat_fid_center_ws_bytes', n) // 8), dtype=torch.float64, device=device)
-            L.call('cat_fid_center', ops._p(feats2), ops._p(mu2), n, d, ops._p(xc), ops._p(ss), ops._p(ws), ops._stream())
+            ws = torch.empty(max(1, _query('cat_fid_center_ws_bytes', n) // 8), dtype=torch.float64, device=device)
+            _call('cat_fid_center', feats2, mu2, n, d, xc, ss, ws)
             m = _symmetrize(_gemm(_gemm(xc, s1), xc, trans_b=True, alpha=1.0 / (n - 1)))
             tr2 = float(ss.item()) / (n - 1)
             tr, steps, ok = sqrtm_trace_device(m)
@@ -331,22 +317,20 @@ def calculate_frechet_distance_device(mu1, sigma1, mu2, sigma2, device=None, cac
     d = _check_stats(mu1, sigma1)
     _check_stats(mu2, sigma2, d)
     tensors = [a for a in (mu1, sigma1, mu2, sigma2) if isinstance(a, torch.Tensor)]
-    device = torch.device(device) if device is not None else (tensors[0].device if tensors else _default_device(None))
+    device = torch.device(device) if device is not None else (tensors[0].device if tensors else default_device(None))
     if device.type != 'cuda':
         raise ValueError('calculate_frechet_distance_device: a GPU device is required (got %s)' % (device,))
     cache = {} if cache is None else cache
     info = {} if info is None else info
     with torch.cuda.device(device):
-        if 'sigma1' not in cache:
-            cache['sigma1'] = _f64_device(sigma1, device)
-            cache['tr1'] = _trace_device(cache['sigma1'])
+        s1, tr1 = _real_side(cache, sigma1, device)
         s2 = _f64_device(sigma2, device)
-        tr, steps, ok = _full_form(cache['sigma1'], s2, cache)
+        tr, steps, ok = _full_form(s1, s2, cache)
         info['form'], info['steps'], info['converged'] = 'full', steps, ok
         if not ok:
             return _fall_back(mu1, sigma1, mu2, sigma2, steps)
         diff = _host(mu1) - _host(mu2)
-        return float(diff.dot(diff) + cache['tr1'] + _trace_device(s2) - 2.0 * tr)
+        return float(diff.dot(diff) + tr1 + _trace_device(s2) - 2.0 * tr)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the real-statistics writer
@@ -381,7 +365,7 @@ def real_statistics(path, model, batch_size=32, dims=2048, device=None, chunk_ba
     """(mu, sigma) of an image set as float64 numpy arrays; the images are read `chunk_batches` batches at a time, the features and both
     statistics stay on the device"""
     load, n = load_images(path)
-    device = _default_device(device)
+    device = default_device(device)
     feats = torch.empty((n, dims), dtype=torch.float32, device=device)
     step = batch_size * chunk_batches
     for start in range(0, n, step):
@@ -393,18 +377,11 @@ def real_statistics(path, model, batch_size=32, dims=2048, device=None, chunk_ba
 
 def parse_args(argv=None):
     from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
-    from .inception import InceptionV3
     parser = ArgumentParser(prog='python -m cat_amd.metric.fid_score', formatter_class=ArgumentDefaultsHelpFormatter,
                             description='Write the {mu, sigma} file of a real image set that --real_stat_path names')
     parser.add_argument('--images', type=str, required=True, help='a directory of *.jpg / *.png, or a .npy array [N, 3, H, W] in [-1, 1]')
     parser.add_argument('--output', type=str, required=True, help='the .npz file to write (keys mu, sigma; float64)')
-    parser.add_argument('--batch-size', type=int, default=32, help='Batch size to use')
-    parser.add_argument('--dims', type=int, default=2048, choices=list(InceptionV3.BLOCK_INDEX_BY_DIM),
-                        help='Dimensionality of Inception features to use. By default, uses pool3 features')
-    parser.add_argument('-c', '--gpu', default='0', type=str, help='GPU to use (there is no CPU path)')
-    parser.add_argument('--inception-path', type=str, required=True,
-                        help='the FID InceptionV3 checkpoint with torchvision keys (pt_inception-2015-12-05-6726825d.pth); never downloaded')
-    return parser.parse_args(argv)
+    return add_inception_arguments(parser, batch_size=32).parse_args(argv)
 
 
 def main(argv=None):
@@ -412,11 +389,8 @@ def main(argv=None):
     print(args)
     if args.gpu == '':
         raise SystemExit('fid_score: --gpu must name a GPU; the kernels have no CPU path')
-    from .inception import InceptionV3
     device = torch.device('cuda', int(args.gpu))
-    model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[args.dims]])
-    model.load_fid_state_dict(torch.load(args.inception_path, map_location='cpu'))
-    mu, sigma = real_statistics(args.images, model.to(device).eval(), args.batch_size, args.dims, device)
+    mu, sigma = real_statistics(args.images, load_inception(args.dims, args.inception_path, device, 'FID'), args.batch_size, args.dims, device)
     np.savez(args.output, mu=mu, sigma=sigma)
     print('wrote %s: mu %s, sigma %s' % (args.output, mu.shape, sigma.shape))
 

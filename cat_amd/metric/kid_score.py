@@ -17,20 +17,15 @@ from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 import numpy as np
 import torch
 
-from .inception import InceptionV3
+from .features import add_inception_arguments, default_device as _default_device, feature_batches, load_inception
 
 SUM_KEYS = ('rs_xx', 'dg_xx', 'rs_yy', 'dg_yy', 'rs_xy', 'cs_xy')      # [S, m] each, in the order of the kernel's output row
 SCALAR_KEYS = ('tr_xy', 'sq_xx', 'sq_yy', 'sq_xy')                      # [S] each
 
 
 # ---------------------------------------------------------------------------------------------------------------- features
-def _default_device(device):
-    return torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-
-
 def _activations(load, n, model, batch_size, dims, device, verbose):
     """The loop of get_activations (:51-97): `load(start, end)` returns the float32 [B, 3, H, W] batch in [0, 1]."""
-    model.eval()
     if n % batch_size != 0:
         print(('Warning: number of images is not a multiple of the '
                'batch size. Some samples are going to be ignored.'))
@@ -39,21 +34,11 @@ def _activations(load, n, model, batch_size, dims, device, verbose):
                'Setting batch size to data size'))
         batch_size = n
     n_batches = n // batch_size
-    n_used_imgs = n_batches * batch_size
-    pred_arr = np.empty((n_used_imgs, dims))
-    device = _default_device(device)
-    for i in range(n_batches):
+    pred_arr = np.empty((n_batches * batch_size, dims))
+    for start, end, feats in feature_batches(load, n, model, batch_size, _default_device(device), full_only=True):
         if verbose:
-            print('\rPropagating batch %d/%d' % (i + 1, n_batches), end='', flush=True)
-        start = i * batch_size
-        end = start + batch_size
-        batch = torch.from_numpy(load(start, end)).type(torch.FloatTensor).to(device)
-        with torch.no_grad():
-            pred = model(batch)[0]
-        if pred.shape[2] != 1 or pred.shape[3] != 1:      # a block below pool3 was selected: adaptive_avg_pool2d(pred, (1, 1))
-            from .inception import GlobalAvgPool
-            pred = GlobalAvgPool()(pred)
-        pred_arr[start:end] = pred.cpu().data.numpy().reshape(batch_size, -1)
+            print('\rPropagating batch %d/%d' % (end // batch_size, n_batches), end='', flush=True)
+        pred_arr[start:end] = feats.cpu().numpy()
     if verbose:
         print(' done')
     return pred_arr
@@ -104,17 +89,7 @@ def _compute_activations(path, model, batch_size, dims, device):
 
 
 def _inception_for(dims, inception, device):
-    block_idx = InceptionV3.BLOCK_INDEX_BY_DIM[dims]
-    if isinstance(inception, torch.nn.Module):
-        return inception.to(device).eval()
-    if inception is None:
-        raise RuntimeError('KID needs the FID InceptionV3 checkpoint (pt_inception-2015-12-05-6726825d.pth, torchvision keys): pass its path '
-                           'or state_dict; this package does not download it')
-    if isinstance(inception, (str, bytes, os.PathLike)):
-        inception = torch.load(inception, map_location='cpu')
-    model = InceptionV3([block_idx])
-    model.load_fid_state_dict(inception)
-    return model.to(device).eval()
+    return load_inception(dims, inception, device, 'KID')
 
 
 def calculate_kid_given_paths(paths, batch_size, device, dims, inception=None):
@@ -340,13 +315,7 @@ def parse_args(argv=None):
     parser = ArgumentParser(prog='python -m cat_amd.metric.kid_score', formatter_class=ArgumentDefaultsHelpFormatter)
     parser.add_argument('--real', type=str, required=True, help=('Path to the real images'))
     parser.add_argument('--fake', type=str, nargs='+', required=True, help=('Path to the generated images'))
-    parser.add_argument('--batch-size', type=int, default=2, help='Batch size to use')
-    parser.add_argument('--dims', type=int, default=2048, choices=list(InceptionV3.BLOCK_INDEX_BY_DIM),
-                        help=('Dimensionality of Inception features to use. By default, uses pool3 features'))
-    parser.add_argument('-c', '--gpu', default='0', type=str, help='GPU to use (there is no CPU path)')
-    parser.add_argument('--inception-path', type=str, required=True,
-                        help='the FID InceptionV3 checkpoint with torchvision keys (pt_inception-2015-12-05-6726825d.pth); never downloaded')
-    return parser.parse_args(argv)
+    return add_inception_arguments(parser, batch_size=2).parse_args(argv)
 
 
 def main(argv=None):
