@@ -82,6 +82,8 @@ struct DwMultiArgs {
   long long run_base[CAT_DWMULTI_MAXRUN + 1];      // first thread index of the run; [nrun] = total
 };
 
+__device__ __attribute__((aligned(16))) float g_zero[4] = {0.f, 0.f, 0.f, 0.f};      // global (not constant) address space: the loads stay global_load
+
 template <int K>
 __device__ __forceinline__ f4 dw_multi_taps(const DwMultiArgs& p, const float* sw, const float* xn, int oy, int ox, int c, int cs, f4 acc) {
   constexpr int R = K / 2, O = 2 - R;
@@ -102,15 +104,15 @@ __device__ __forceinline__ f4 dw_multi_taps(const DwMultiArgs& p, const float* s
 #pragma unroll
   for (int ky = 0; ky < K; ++ky)
 #pragma unroll
-    for (int kx = 0; kx < K; ++kx) xv[ky][kx] = *reinterpret_cast<const f4*>(xn + offy[ky] + offx[kx]);
+    for (int kx = 0; kx < K; ++kx)      // out-of-plane taps load the zero line: never x * 0 (a non-finite pixel (0, 0) would turn every border output into NaN)
+      xv[ky][kx] = *reinterpret_cast<const f4*>((vy[ky] && vx[kx]) ? xn + offy[ky] + offx[kx] : g_zero);
 #pragma unroll
   for (int ky = 0; ky < K; ++ky)
 #pragma unroll
     for (int kx = 0; kx < K; ++kx) {
       const f4 wv = *reinterpret_cast<const f4*>(sw + ((O + ky) * 5 + O + kx) * cs + c);
-      const float mk = (vy[ky] && vx[kx]) ? 1.f : 0.f;      // out-of-plane taps read pixel (0, 0): masked, never skipped
 #pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] = fmaf(xv[ky][kx][e] * mk, wv[e], acc[e]);
+      for (int e = 0; e < 4; ++e) acc[e] = fmaf(xv[ky][kx][e], wv[e], acc[e]);
     }
   return acc;
 }
