@@ -223,6 +223,11 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
 }
 
 // dx = gamma * inv_std * (g - sum(g)/count - xhat * sum(g*xhat)/count); dgamma / dbeta from the LOCAL sums
+// One formula serves both inv_std rules of bn_finalize_kernel.  Known and accepted divergence: with clamp != 0 a channel with 0 < var < eps has
+// inv_std = eps^-1/2, a constant, and autograd through bias_var.clamp(eps) (sync_batchnorm/batchnorm.py:140) then drops the
+// xhat * sum(g*xhat)/count term, which this kernel keeps (cat_bn_apply_bwd is told neither eps nor clamp).  Such a channel is constant to
+// within sqrt(eps) = 3e-3; for var == 0 (xhat == 0) and for var >= eps the two agree.  tests/test_spade_eval_kernels_gpu.py holds that
+// channel to the reference on the forward only.
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            const float* __restrict__ a, const float* __restrict__ b,

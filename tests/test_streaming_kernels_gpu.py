@@ -17,8 +17,9 @@ E (GPU):  cat_loss_fwd / cat_loss_bwd (kinds 0..7, the size ladder up to both bl
 Bars: TOL = 1e-4 with rel() of test_kernels_gpu.py (5 * TOL for the norm's and KA's gradients, as test_norm_fwd_bwd / test_ka have them), 1e-5
 absolute for the KA value, 1e-6 for the scalar losses, Adam and add_n; exact equality for zero lanes, sentinels and repeated runs.  Workspaces and
 fresh-write destinations start as NaN, everything a kernel must not touch as the sentinel 7.0.  The element-walk norm kernels (CAT_NORM_WALK=0)
-and csrc/spade.hip are not covered here.  Largest distances observed on an MI355X: B 2.2e-6 (origin case 1.1e-5), C 1.8e-7, D 3.2e-7 on the
-gradient and 9.0e-8 on the value, E 2.6e-9 / 5.6e-8 on a loss value / gradient, 1.7e-7 channel sum, 8.5e-8 add_n, Adam's second moment 1.3e-5."""
+are not covered here; csrc/spade.hip and csrc/eval_ops.hip are in test_spade_eval_kernels_gpu.py.  Largest distances observed on an MI355X:
+B 2.2e-6 (origin case 1.1e-5), C 1.8e-7, D 3.2e-7 on the gradient and 9.0e-8 on the value, E 2.6e-9 / 5.6e-8 on a loss value / gradient,
+1.7e-7 channel sum, 8.5e-8 add_n, Adam's second moment 1.3e-5."""
 import ctypes as C
 import functools
 
