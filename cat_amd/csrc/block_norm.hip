@@ -235,32 +235,55 @@ __global__ __launch_bounds__(256) void reflect_fold2_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------- depthwise stage of a block
 // All depthwise convs of a block (k = 1 / 3 / 5 per channel quad) in one launch, reading channel slices of the first-stage buffer
 // with that stage's normalise + ReLU applied while the 12 x 20 pixel patch is staged in LDS, writing the concatenated pre-norm output
-// and its per-tile statistics.  One workgroup = 8 x 16 output pixels x all quads; thread = (pixel, quad parity).
+// and its per-tile statistics.  One workgroup = 8 x 16 output pixels x one GROUP of at most kDwGroup consecutive channel quads of one kernel
+// size (common.h: dw_quad_groups); thread = (pixel, quad parity within the group).  The groups of a tile share nothing: the patch of a group
+// is 15 KB, so several workgroups share a CU and one's staging overlaps another's taps.  Per channel the arithmetic does not depend on the
+// grouping: taps in (ky, kx) order, tile sums by wave_sum over the same 64 pixels, lower + upper half tile, two passes (sum, then M2).
+constexpr int DWM_PS = (TH + 4) * (TW + 4) + 2;      // f4 per quad plane of a patch: + 2 spreads the staging stores of a pixel's 4 quads over the banks
+constexpr int DWM_GCS = cat::kDwGroup * 4;           // floats per tap / per wave row of a group
+
 struct DwmArgs {
   const float* x; const float* scale; const float* shift; const float* w; const float* bias; float* y; float* stats;
   int xcs, sstride, ycs, scs;
   int N, H, W, nq, reflect, act;
   float slope;
   int tiles_x, tiles;
-  int ks[CAT_DWM_MAXQ];   // kernel size of each channel quad
+  int ng;                                        // quad groups
+  unsigned char gq0[CAT_DWM_MAXQ], gnq[CAT_DWM_MAXQ], gks[CAT_DWM_MAXQ];      // first quad, quad count, kernel size of each group
 };
 
-// MAXQ = compile-time bound of p.nq (16: the training blocks; 24: frozen SPADE units with 3 x 21 -> 72 hidden channels)
-template <int MAXQ>
+// the k x k taps of one pixel of one quad, fully unrolled; pl = the quad's plane of the patch, sw = its column of the [25][DWM_GCS] frame
+template <int K>
+__device__ __forceinline__ f4 dwm_taps(const f4* pl, const float* sw, int py, int pxx, f4 a) {
+  constexpr int TC = TW + 4, O = 2 - K / 2;
+#pragma unroll
+  for (int ky = 0; ky < K; ++ky)
+#pragma unroll
+    for (int kx = 0; kx < K; ++kx)
+      a += pl[(py + O + ky) * TC + pxx + O + kx] * *reinterpret_cast<const f4*>(sw + ((O + ky) * 5 + O + kx) * DWM_GCS);
+  return a;
+}
+
 __global__ __launch_bounds__(256) void dwm_fwd_kernel(DwmArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int TR = TH + 4, TC = TW + 4;
-  const int cs = p.nq * 4;
-  float* tile = smem;                    // [TR * TC][cs]
-  float* sw = smem + TR * TC * cs;       // [25][cs] filters in a 5 x 5 frame
-  float* red = sw + 25 * cs;             // [4 waves][cs]
+  constexpr int TR = TH + 4, TC = TW + 4, G = cat::kDwGroup;
+  f4* tile = reinterpret_cast<f4*>(smem);      // [G][DWM_PS] one plane per quad of the group
+  float* sw = smem + G * DWM_PS * 4;           // [25][DWM_GCS] filters in a 5 x 5 frame
+  float* red = sw + 25 * DWM_GCS;              // [4 waves][DWM_GCS]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tt = blockIdx.x, n = tt / p.tiles, t = tt - n * p.tiles;
+  int tt, grp;
+  cat::dw_tile_group(blockIdx.x, p.N * p.tiles, p.ng, tt, grp);
+  const int q0 = p.gq0[grp], gn = p.gnq[grp], ks = p.gks[grp];
+  const int n = tt / p.tiles, t = tt - n * p.tiles;
   const int oy0 = (t / p.tiles_x) * TH, ox0 = (t % p.tiles_x) * TW;
   const int g = p.sstride ? n : 0;       // per-image statistics (InstanceNorm) or one group
-  for (int i = tid; i < 25 * p.nq; i += 256) *reinterpret_cast<f4*>(sw + i * 4) = *reinterpret_cast<const f4*>(p.w + i * 4);
+  const int cs = p.nq * 4;
+  for (int i = tid; i < 25 * gn; i += 256) {
+    const int tap = i / gn, ql = i - tap * gn;
+    *reinterpret_cast<f4*>(sw + tap * DWM_GCS + ql * 4) = *reinterpret_cast<const f4*>(p.w + tap * cs + (q0 + ql) * 4);
+  }
   const float neg = p.act == CAT_ACT_RELU ? 0.f : (p.act == CAT_ACT_LRELU ? p.slope : 1.f);
-  constexpr int SIT = (TR * TC * MAXQ + 255) / 256;     // all of the thread's loads in flight before the first LDS store
+  constexpr int SIT = (TR * TC * G + 255) / 256;     // all of the thread's loads in flight before the first LDS store
   f4 xv[SIT];
   {
     const f4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -268,8 +291,8 @@ __global__ __launch_bounds__(256) void dwm_fwd_kernel(DwmArgs p) {
     for (int it = 0; it < SIT; ++it) {
       const int i = tid + it * 256;
       xv[it] = zero;
-      if (i < TR * TC * p.nq) {
-        const int pix = i / p.nq, q = i - pix * p.nq;
+      if (i < TR * TC * gn) {
+        const int pix = i / gn, q = q0 + i - pix * gn;
         const int r = pix / TC, c = pix - r * TC;
         int iy = oy0 - 2 + r, ix = ox0 - 2 + c;
         bool v;
@@ -294,7 +317,7 @@ __global__ __launch_bounds__(256) void dwm_fwd_kernel(DwmArgs p) {
 #pragma unroll
     for (int it = 0; it < SIT; ++it) {
       const int i = tid + it * 256;
-      if (i < TR * TC * p.nq) *reinterpret_cast<f4*>(tile + (i / p.nq) * cs + (i % p.nq) * 4) = xv[it];
+      if (i < TR * TC * gn) tile[(i % gn) * DWM_PS + i / gn] = xv[it];
     }
   }
   __syncthreads();
@@ -302,19 +325,17 @@ __global__ __launch_bounds__(256) void dwm_fwd_kernel(DwmArgs p) {
   const int py = px >> 4, pxx = px & 15;
   const bool pv = oy0 + py < p.H && ox0 + pxx < p.W;
   const int cnt = min(TH, p.H - oy0) * min(TW, p.W - ox0);
-  constexpr int MAXH = MAXQ / 2;
+  constexpr int MAXH = G / 2;
   f4 out[MAXH];
 #pragma unroll
   for (int k = 0; k < MAXH; ++k) {
-    const int q = half + 2 * k;
+    const int ql = half + 2 * k, q = q0 + ql;
     out[k] = f4{0.f, 0.f, 0.f, 0.f};
-    if (q < p.nq) {
-      const int ks = p.ks[q], o = 2 - (ks >> 1);
+    if (ql < gn) {
       f4 a = p.bias ? *reinterpret_cast<const f4*>(p.bias + q * 4) : f4{0.f, 0.f, 0.f, 0.f};
-      for (int ky = 0; ky < ks; ++ky)
-        for (int kx = 0; kx < ks; ++kx)
-          a += *reinterpret_cast<const f4*>(tile + ((py + o + ky) * TC + pxx + o + kx) * cs + q * 4) *
-               *reinterpret_cast<const f4*>(sw + ((o + ky) * 5 + o + kx) * cs + q * 4);
+      if (ks == 5) a = dwm_taps<5>(tile + ql * DWM_PS, sw + ql * 4, py, pxx, a);
+      else if (ks == 3) a = dwm_taps<3>(tile + ql * DWM_PS, sw + ql * 4, py, pxx, a);
+      else a = dwm_taps<1>(tile + ql * DWM_PS, sw + ql * 4, py, pxx, a);
       out[k] = a;
       if (pv) *reinterpret_cast<f4*>(p.y + (((int64_t)n * p.H + oy0 + py) * p.W + ox0 + pxx) * p.ycs + q * 4) = a;
     }
@@ -327,8 +348,8 @@ __global__ __launch_bounds__(256) void dwm_fwd_kernel(DwmArgs p) {
   for (int pass = 0; pass < 2; ++pass) {
 #pragma unroll
     for (int k = 0; k < MAXH; ++k) {
-      const int q = half + 2 * k;
-      if (q < p.nq) {
+      const int ql = half + 2 * k;
+      if (ql < gn) {
         f4 v = out[k];
         if (pass == 1) {
           v = v - mean[k];
@@ -337,17 +358,17 @@ __global__ __launch_bounds__(256) void dwm_fwd_kernel(DwmArgs p) {
         if (!pv) v = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = cat::wave_sum(v[e]);
-        if (lane == 0) *reinterpret_cast<f4*>(red + wave * cs + q * 4) = v;
+        if (lane == 0) *reinterpret_cast<f4*>(red + wave * DWM_GCS + ql * 4) = v;
       }
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < MAXH; ++k) {
-      const int q = half + 2 * k;
-      if (q < p.nq) {
-        const f4 tot = *reinterpret_cast<const f4*>(red + (2 * half) * cs + q * 4) + *reinterpret_cast<const f4*>(red + (2 * half + 1) * cs + q * 4);
+      const int ql = half + 2 * k;
+      if (ql < gn) {
+        const f4 tot = *reinterpret_cast<const f4*>(red + (2 * half) * DWM_GCS + ql * 4) + *reinterpret_cast<const f4*>(red + (2 * half + 1) * DWM_GCS + ql * 4);
         if (pass == 0) mean[k] = tot / (float)cnt;
-        if ((tid & 127) == 0) *reinterpret_cast<f4*>(dst + pass * p.scs + q * 4) = tot;
+        if ((tid & 127) == 0) *reinterpret_cast<f4*>(dst + pass * p.scs + (q0 + ql) * 4) = tot;
       }
     }
     __syncthreads();
@@ -439,25 +460,15 @@ int cat_dwm_fwd(const cat_dwm_t* g, const float* x, const float* scale, const fl
   a.N = g->N; a.H = g->H; a.W = g->W; a.nq = g->nq; a.reflect = g->reflect; a.act = g->act; a.slope = g->slope;
   a.tiles_x = cdiv(g->W, TW);
   a.tiles = a.tiles_x * cdiv(g->H, TH);
-  for (int q = 0; q < g->nq; ++q) {
-    CAT_REQUIRE(g->ks[q] == 1 || g->ks[q] == 3 || g->ks[q] == 5, "dwm: kernel size %d", g->ks[q]);
-    a.ks[q] = g->ks[q];
-  }
-  const int cs = g->nq * 4;
-  const size_t lds = (size_t)((TH + 4) * (TW + 4) * cs + 25 * cs + 4 * cs) * sizeof(float);
-  CAT_REQUIRE(lds <= 112 * 1024, "dwm: %zu bytes of LDS (max 112 KB)", lds);
+  for (int q = 0; q < g->nq; ++q) CAT_REQUIRE(g->ks[q] == 1 || g->ks[q] == 3 || g->ks[q] == 5, "dwm: kernel size %d", g->ks[q]);
+  a.ng = cat::dw_quad_groups(g->ks, g->nq, a.gq0, a.gnq);
+  for (int k = 0; k < a.ng; ++k) a.gks[k] = (unsigned char)g->ks[a.gq0[k]];
+  constexpr size_t lds = (size_t)(cat::kDwGroup * DWM_PS * 4 + 25 * DWM_GCS + 4 * DWM_GCS) * sizeof(float);
+  static_assert(4 * lds <= 160 * 1024, "dwm: four workgroups per CU by LDS");
   double taps = 0.0;
   for (int q = 0; q < g->nq; ++q) taps += 4.0 * g->ks[q] * g->ks[q];
   cat::ProfScope prof("dwconv_fwd", 2.0 * (double)g->N * g->H * g->W * taps, 0.0, stream);
-  if (g->nq <= 16) {
-    static cat::LdsOptIn optin;
-    cat::lds_optin(optin, (const void*)dwm_fwd_kernel<16>, 96 * 1024);
-    dwm_fwd_kernel<16><<<g->N * a.tiles, 256, lds, (hipStream_t)stream>>>(a);
-  } else {
-    static cat::LdsOptIn optin;
-    cat::lds_optin(optin, (const void*)dwm_fwd_kernel<CAT_DWM_MAXQ>, 112 * 1024);
-    dwm_fwd_kernel<CAT_DWM_MAXQ><<<g->N * a.tiles, 256, lds, (hipStream_t)stream>>>(a);
-  }
+  dwm_fwd_kernel<<<g->N * a.tiles * a.ng, 256, lds, (hipStream_t)stream>>>(a);
   return cat::check_launch("dwm_fwd");
 }
 
@@ -541,11 +552,15 @@ extern "C" int cat_prep_run(const cat_prep_job_t* jobs_dev, int njobs, int total
 
 // ---------------------------------------------------------------------------------------------- depthwise stage, backward
 // Input gradient and filter gradient of ALL depthwise convs of a block in one launch (+ a small final reduction): replaces, per branch,
-// cat_dwconv2d_dgrad + the reflect fold + two slice copies + cat_dwconv2d_wgrad.  One workgroup = 8 x 16 pixels x all channel quads.
+// cat_dwconv2d_dgrad + the reflect fold + two slice copies + cat_dwconv2d_wgrad.  One workgroup = 8 x 16 pixels x one group of at most
+// kDwGroup channel quads of one kernel size, as in dwm_fwd_kernel: its two patches are 31 KB (all quads of a block: 89 - 142 KB, one
+// workgroup per CU with nothing to overlap its staging).
 //   dA[i]      = sum over the padded positions j that mirror onto i (j = i, and near a border -i / 2(H-1)-i) of
 //                sum_k dZ[j + p - k] * w[k]            (reflect padding; zero padding: j = i only, dZ = 0 outside the plane)
 //   dW[c][k]  += sum over the tile's output pixels o of dZ[o][c] * a[reflect(o - p + k)][c]     -> per-tile partials, reduced by
 //                dwm_wgrad_final_kernel straight into the parameters' gradient buffers
+// The filter-gradient partial of a (tap, quad) is summed by one thread over the tile's pixels in row-major order: deterministic, no atomics,
+// and the same order for every grouping.
 namespace {
 
 struct DwmBwdArgs {
@@ -553,30 +568,59 @@ struct DwmBwdArgs {
   int acs, zcs, dacs;
   int N, H, W, nq, reflect;
   int tiles_x, tiles;
-  int ks[CAT_DWM_MAXQ];
+  int ng;
+  unsigned char gq0[CAT_DWM_MAXQ_BWD], gnq[CAT_DWM_MAXQ_BWD], gks[CAT_DWM_MAXQ_BWD];
 };
+
+// dA of one pixel of one quad: (mirror position, ky, kx) order, the k x k loops fully unrolled
+template <int K>
+__device__ __forceinline__ f4 dwm_dgrad_taps(const f4* tz, const float* sw, const int* ys, int ny, const int* xs, int nx, int oy0, int ox0) {
+  constexpr int TR = TH + 4, TC = TW + 4, pd = K / 2, o = 2 - pd;
+  f4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int a = 0; a < ny; ++a)
+    for (int b = 0; b < nx; ++b) {
+      const int jy = ys[a], jx = xs[b];
+#pragma unroll
+      for (int ky = 0; ky < K; ++ky) {
+        const int zy = jy + pd - ky - (oy0 - 2);          // row of dZ in the patch
+        if ((unsigned)zy >= (unsigned)TR) continue;
+#pragma unroll
+        for (int kx = 0; kx < K; ++kx) {
+          const int zx = jx + pd - kx - (ox0 - 2);
+          if ((unsigned)zx >= (unsigned)TC) continue;
+          acc += tz[zy * TC + zx] * *reinterpret_cast<const f4*>(sw + ((o + ky) * 5 + o + kx) * DWM_GCS);
+        }
+      }
+    }
+  return acc;
+}
 
 __global__ __launch_bounds__(256) void dwm_bwd_kernel(DwmBwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int TR = TH + 4, TC = TW + 4;
-  const int cs = p.nq * 4;
-  float* ta = smem;                       // [TR * TC][cs]   input activation patch (reflect- or zero-padded)
-  float* tz = ta + TR * TC * cs;          // [TR * TC][cs]   dZ patch (zero outside the plane)
-  float* sw = tz + TR * TC * cs;          // [25][cs]
+  constexpr int TR = TH + 4, TC = TW + 4, G = cat::kDwGroup;
+  f4* ta = reinterpret_cast<f4*>(smem);   // [G][DWM_PS]   input activation patch (reflect- or zero-padded), one plane per quad
+  f4* tz = ta + G * DWM_PS;               // [G][DWM_PS]   dZ patch (zero outside the plane)
+  float* sw = reinterpret_cast<float*>(tz + G * DWM_PS);      // [25][DWM_GCS]
   const int tid = threadIdx.x;
-  const int tt = blockIdx.x, n = tt / p.tiles, t = tt - n * p.tiles;
+  int tt, grp;
+  cat::dw_tile_group(blockIdx.x, p.N * p.tiles, p.ng, tt, grp);
+  const int q0 = p.gq0[grp], gn = p.gnq[grp], ks = p.gks[grp];
+  const int n = tt / p.tiles, t = tt - n * p.tiles;
   const int oy0 = (t / p.tiles_x) * TH, ox0 = (t % p.tiles_x) * TW;
-  for (int i = tid; i < 25 * p.nq; i += 256) *reinterpret_cast<f4*>(sw + i * 4) = *reinterpret_cast<const f4*>(p.w + i * 4);
-  // staging in two phases (all global loads of the thread in flight, then the LDS stores): one workgroup per CU (89 KB of LDS), so
-  // nothing else would hide a load-store-load chain
-  constexpr int SIT = (TR * TC * CAT_DWM_MAXQ_BWD + 255) / 256;
+  const int cs = p.nq * 4;
+  for (int i = tid; i < 25 * gn; i += 256) {
+    const int tap = i / gn, ql = i - tap * gn;
+    *reinterpret_cast<f4*>(sw + tap * DWM_GCS + ql * 4) = *reinterpret_cast<const f4*>(p.w + tap * cs + (q0 + ql) * 4);
+  }
+  // staging in two phases: all global loads of the thread in flight, then the LDS stores
+  constexpr int SIT = (TR * TC * G + 255) / 256;
   f4 zv[SIT], av[SIT];
 #pragma unroll
   for (int it = 0; it < SIT; ++it) {
     const int i = tid + it * 256;
     zv[it] = av[it] = f4{0.f, 0.f, 0.f, 0.f};
-    if (i < TR * TC * p.nq) {
-      const int pix = i / p.nq, q = i - pix * p.nq;
+    if (i < TR * TC * gn) {
+      const int pix = i / gn, q = q0 + i - pix * gn;
       const int r = pix / TC, c = pix - r * TC;
       const int iy = oy0 - 2 + r, ix = ox0 - 2 + c;
       const bool in = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
@@ -594,69 +638,63 @@ __global__ __launch_bounds__(256) void dwm_bwd_kernel(DwmBwdArgs p) {
 #pragma unroll
   for (int it = 0; it < SIT; ++it) {
     const int i = tid + it * 256;
-    if (i < TR * TC * p.nq) {
-      const int pix = i / p.nq, q = i - pix * p.nq;
-      *reinterpret_cast<f4*>(tz + pix * cs + q * 4) = zv[it];
-      *reinterpret_cast<f4*>(ta + pix * cs + q * 4) = av[it];
+    if (i < TR * TC * gn) {
+      const int pix = i / gn, ql = i - pix * gn;
+      tz[ql * DWM_PS + pix] = zv[it];
+      ta[ql * DWM_PS + pix] = av[it];
     }
   }
   __syncthreads();
-  // ---- input gradient: thread = (pixel, quad parity)
+  // ---- input gradient: thread = (pixel, quad parity within the group)
   {
     const int px = tid & 127, half = tid >> 7;
     const int py = px >> 4, pxx = px & 15;
     const int iy = oy0 + py, ix = ox0 + pxx;
     if (iy < p.H && ix < p.W) {
       // padded positions that mirror onto (iy, ix); zero padding: the pixel itself only
-      int ys[3], xs[3], ny = 0, nx = 0;
-      ys[ny++] = iy;
-      xs[nx++] = ix;
-      for (int q = half; q < p.nq; q += 2) {
-        const int ks = p.ks[q], pd = ks >> 1, o = 2 - pd;
-        ny = nx = 1;
-        if (p.reflect) {
-          if (iy >= 1 && iy <= pd) ys[ny++] = -iy;
-          if (iy <= p.H - 2 && iy >= p.H - 1 - pd) ys[ny++] = 2 * (p.H - 1) - iy;
-          if (ix >= 1 && ix <= pd) xs[nx++] = -ix;
-          if (ix <= p.W - 2 && ix >= p.W - 1 - pd) xs[nx++] = 2 * (p.W - 1) - ix;
-        }
-        f4 acc = {0.f, 0.f, 0.f, 0.f};
-        for (int a = 0; a < ny; ++a)
-          for (int b = 0; b < nx; ++b) {
-            const int jy = ys[a], jx = xs[b];
-            for (int ky = 0; ky < ks; ++ky) {
-              const int zy = jy + pd - ky - (oy0 - 2);          // row of dZ in the patch
-              if ((unsigned)zy >= (unsigned)TR) continue;
-              for (int kx = 0; kx < ks; ++kx) {
-                const int zx = jx + pd - kx - (ox0 - 2);
-                if ((unsigned)zx >= (unsigned)TC) continue;
-                acc += *reinterpret_cast<const f4*>(tz + (zy * TC + zx) * cs + q * 4) *
-                       *reinterpret_cast<const f4*>(sw + ((o + ky) * 5 + o + kx) * cs + q * 4);
-              }
-            }
-          }
-        *reinterpret_cast<f4*>(p.da + (((int64_t)n * p.H + iy) * p.W + ix) * p.dacs + q * 4) = acc;
+      int ys[3], xs[3], ny = 1, nx = 1;
+      ys[0] = iy;
+      xs[0] = ix;
+      const int pd = ks >> 1;
+      if (p.reflect) {
+        if (iy >= 1 && iy <= pd) ys[ny++] = -iy;
+        if (iy <= p.H - 2 && iy >= p.H - 1 - pd) ys[ny++] = 2 * (p.H - 1) - iy;
+        if (ix >= 1 && ix <= pd) xs[nx++] = -ix;
+        if (ix <= p.W - 2 && ix >= p.W - 1 - pd) xs[nx++] = 2 * (p.W - 1) - ix;
+      }
+      for (int ql = half; ql < gn; ql += 2) {
+        f4 acc;
+        if (ks == 5) acc = dwm_dgrad_taps<5>(tz + ql * DWM_PS, sw + ql * 4, ys, ny, xs, nx, oy0, ox0);
+        else if (ks == 3) acc = dwm_dgrad_taps<3>(tz + ql * DWM_PS, sw + ql * 4, ys, ny, xs, nx, oy0, ox0);
+        else acc = dwm_dgrad_taps<1>(tz + ql * DWM_PS, sw + ql * 4, ys, ny, xs, nx, oy0, ox0);
+        *reinterpret_cast<f4*>(p.da + (((int64_t)n * p.H + iy) * p.W + ix) * p.dacs + (q0 + ql) * 4) = acc;
       }
     }
   }
-  // ---- filter gradient partials: work item = (tap of the 5 x 5 frame, quad), summed over the tile's 128 output pixels
+  // ---- filter gradient partials of the tile: [25][cs] frame, zero outside the k x k window.  Work item = (tap of the window, quad), summed
+  // over the tile's output pixels in row-major order by ONE thread: the sum of a (tap, channel) keeps the order it always had, whatever the
+  // grouping (a training step's parameters stay bit-comparable).  The 16 columns of a row are unrolled: their 32 LDS reads are in flight
+  // together, and the other workgroups of the CU cover the dependent adds
   float* part = p.part + (int64_t)tt * 25 * cs;
-  for (int wi = tid; wi < 25 * p.nq; wi += 256) {
-    const int tap = wi / p.nq, q = wi - tap * p.nq;
-    const int ks = p.ks[q], o = 2 - (ks >> 1);
-    const int fy = tap / 5, fx = tap - fy * 5;            // frame coordinates; the filter occupies [o, o + ks)
+  const int o = 2 - (ks >> 1), items = ks * ks * gn;
+  for (int i = tid; i < 25 * gn; i += 256) {
+    const int tap = i / gn, ql = i - tap * gn;
+    const int fy = tap / 5, fx = tap - fy * 5;
+    if (fy < o || fy >= o + ks || fx < o || fx >= o + ks) *reinterpret_cast<f4*>(part + tap * cs + (q0 + ql) * 4) = f4{0.f, 0.f, 0.f, 0.f};
+  }
+  if (tid < items) {
+    const int wt = tid / gn, ql = tid - wt * gn;
+    const int fy = o + wt / ks, fx = o + wt % ks;           // frame coordinates; the filter occupies [o, o + ks)
+    const int nrow = min(TH, p.H - oy0), ncol = min(TW, p.W - ox0);
+    const f4* zq = tz + ql * DWM_PS + 2 * TC + 2;
+    const f4* aq = ta + ql * DWM_PS + fy * TC + fx;
     f4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (fy >= o && fy < o + ks && fx >= o && fx < o + ks) {
-      for (int py = 0; py < TH; ++py) {
-        if (oy0 + py >= p.H) break;
-        for (int pxx = 0; pxx < TW; ++pxx) {
-          if (ox0 + pxx >= p.W) break;
-          acc += *reinterpret_cast<const f4*>(tz + ((py + 2) * TC + pxx + 2) * cs + q * 4) *
-                 *reinterpret_cast<const f4*>(ta + ((py + fy) * TC + pxx + fx) * cs + q * 4);
-        }
-      }
+    for (int py = 0; py < nrow; ++py) {
+#pragma unroll
+      for (int pxx = 0; pxx < TW; ++pxx)
+        if (pxx < ncol) acc += zq[py * TC + pxx] * aq[py * TC + pxx];
     }
-    *reinterpret_cast<f4*>(part + tap * cs + q * 4) = acc;
+    *reinterpret_cast<f4*>(part + (fy * 5 + fx) * cs + (q0 + ql) * 4) = acc;
   }
 }
 
@@ -702,17 +740,21 @@ int cat_dwm_bwd(const cat_dwm_t* g, const float* a, const float* dz, const float
   p.tiles = p.tiles_x * cdiv(g->H, TH);
   double taps = 0.0;
   for (int q = 0; q < g->nq; ++q) {
-    p.ks[q] = g->ks[q];
+    CAT_REQUIRE(g->ks[q] == 1 || g->ks[q] == 3 || g->ks[q] == 5, "dwm bwd: kernel size %d", g->ks[q]);
     taps += 4.0 * g->ks[q] * g->ks[q];
   }
+  p.ng = cat::dw_quad_groups(g->ks, g->nq, p.gq0, p.gnq);
+  for (int k = 0; k < p.ng; ++k) p.gks[k] = (unsigned char)g->ks[p.gq0[k]];
   const int cs = g->nq * 4, ntiles = g->N * p.tiles;
-  const size_t lds = (size_t)(2 * (TH + 4) * (TW + 4) * cs + 25 * cs) * sizeof(float);
-  CAT_REQUIRE(lds <= 144 * 1024, "dwm bwd: %zu bytes of LDS (max 144 KB)", lds);
-  static cat::LdsOptIn optin;
-  cat::lds_optin(optin, (const void*)dwm_bwd_kernel, 144 * 1024);
+  constexpr size_t lds = (size_t)(2 * cat::kDwGroup * DWM_PS * 4 + 25 * DWM_GCS) * sizeof(float);
+  static_assert(4 * lds <= 160 * 1024 || cat::kDwGroup > 4, "dwm bwd: four workgroups per CU by LDS");
   hipStream_t s = (hipStream_t)stream;
   cat::ProfScope prof("dwconv_bwd", 4.0 * (double)g->N * g->H * g->W * taps, 0.0, stream);
-  dwm_bwd_kernel<<<ntiles, 256, lds, s>>>(p);
+  if (lds > 64 * 1024) {
+    static cat::LdsOptIn optin;
+    cat::lds_optin(optin, (const void*)dwm_bwd_kernel, (int)lds);
+  }
+  dwm_bwd_kernel<<<ntiles * p.ng, 256, lds, s>>>(p);
   if (int e = cat::check_launch("dwm_bwd")) return e;
   DwmFinArgs fa{};
   fa.nbr = nbranch;

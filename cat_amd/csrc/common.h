@@ -112,6 +112,44 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return base + idx;
 }
 
+// The depthwise tile kernels (block_norm.hip: dwm_fwd / dwm_bwd, dwconv.hip: dw_multi_tile) deal a tile's channel quads out over several
+// workgroups: every quad of a depthwise conv -- its output, its tile statistics, its filter gradient -- is independent of every other.
+// kDwGroup = most quads of one workgroup (a 12 x 20 patch of 4 quads is 15 KB of LDS: 4+ workgroups per CU even with dwm_bwd's two patches).
+#ifndef CAT_DW_GROUP
+#define CAT_DW_GROUP 4
+#endif
+constexpr int kDwGroup = CAT_DW_GROUP;
+static_assert(kDwGroup >= 2 && kDwGroup <= 8 && (kDwGroup & (kDwGroup - 1)) == 0, "CAT_DW_GROUP: 2, 4 or 8");
+
+// Groups = the runs of equal kernel size cut into pieces of at most kDwGroup quads, so a group has ONE kernel size (fully unrolled tap loops)
+// and never straddles a run boundary.  q0 / gn: first quad and quad count of each group; returns the number of groups (<= nq).
+static inline int dw_quad_groups(const int* ks, int nq, unsigned char* q0, unsigned char* gn) {
+  int ng = 0;
+  for (int q = 0; q < nq; ++q) {
+    if (ng && ks[q] == ks[q - 1] && gn[ng - 1] < kDwGroup) {
+      ++gn[ng - 1];
+      continue;
+    }
+    q0[ng] = (unsigned char)q;
+    gn[ng] = 1;
+    ++ng;
+  }
+  return ng;
+}
+
+// Workgroup -> (tile, group), bijective on [0, ntiles * ng).  With ntiles % 8 == 0 each XCD (workgroup id mod 8) owns a contiguous
+// eighth of the tiles and all their groups: the groups of a tile share cache lines, neighbouring tiles share their halo -- in one L2.
+__device__ __forceinline__ void dw_tile_group(int bid, int ntiles, int ng, int& tt, int& grp) {
+  if ((ntiles & 7) == 0) {
+    const int idx = bid >> 3;
+    tt = (bid & 7) * (ntiles >> 3) + idx / ng;
+    grp = idx % ng;
+  } else {
+    tt = bid / ng;
+    grp = bid % ng;
+  }
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -71,6 +71,8 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(DwArgs p) {
 // residual branch's hidden slice, were four launches of 10 - 32 us over the same 176-channel buffers).  Per channel quad a kernel size
 // k in {1, 3, 5}; the filters sit in a 5 x 5 frame [25][cs] (k < 5: centred, the rest zero -- only the k x k window is read), a quad that is
 // merely copied carries k = 1, centre weight 1, bias 0.  Lane = (pixel, quad): a pixel's quads are consecutive lanes (one coalesced row).
+// cat_dwconv2d_multi_fwd launches this 1-D walk for planes of fewer than DW_MULTI_TILE_MIN_WG tile workgroups (and under CAT_DWMULTI_TILE=0);
+// larger planes go to dw_multi_tile_kernel below.
 struct DwMultiArgs {
   const float* x; const float* w25; const float* bias; float* y;
   int N, H, W, nq, xcs, ycs, reflect, act;
@@ -148,6 +150,104 @@ __global__ __launch_bounds__(256) void dw_multi_fwd_kernel(DwMultiArgs p) {
     *reinterpret_cast<f4*>(p.y + opix * p.ycs + c) = acc;
   }
 }
+
+// The same conv for planes large enough to fill the chip (cat_dwconv2d_multi_fwd routes them here): the 1-D walk above re-reads the 25 taps
+// of a 5 x 5 quad from L2 in workgroups five image rows apart (2.3 x the compulsory fetch on the 176-channel 64 x 64 teacher block).  Here one
+// workgroup = 8 x 16 output pixels x one group of at most kDwGroup consecutive quads of one kernel size (common.h: dw_quad_groups), the
+// (8 + k - 1) x (16 + k - 1) patch staged in LDS once: a pixel is fetched once per tile, plus halo.  No affine on staging, bias + activation in
+// the epilogue, no statistics.  Thread = (pixel, quad parity within the group), as in the fused block's dwm_fwd_kernel.  Per output the
+// arithmetic is dw_multi_taps': bias, then fmaf over the taps in (ky, kx) order.
+constexpr int DWT_TH = 8, DWT_TW = 16;
+constexpr int DWT_PS = (DWT_TH + 4) * (DWT_TW + 4) + 2;      // f4 per quad plane: + 2 spreads the staging stores of a pixel's 4 quads over the banks
+constexpr int DWT_GCS = cat::kDwGroup * 4;
+constexpr size_t DWT_LDS = (size_t)(cat::kDwGroup * DWT_PS * 4 + 26 * DWT_GCS) * sizeof(float);      // 17 KB at 4 quads
+
+struct DwTileArgs {
+  const float* x; const float* w25; const float* bias; float* y;
+  int N, H, W, nq, xcs, ycs, reflect, act;
+  float slope;
+  int tiles_x, tiles, ng;
+  unsigned char gq0[CAT_DWMULTI_MAXQ], gnq[CAT_DWMULTI_MAXQ], gks[CAT_DWMULTI_MAXQ];
+};
+
+template <int K>
+__device__ __forceinline__ void dw_multi_tile_body(const DwTileArgs& p, f4* tile, float* sw, int n, int oy0, int ox0, int q0, int gn) {
+  constexpr int R = K / 2, O = 2 - R, PR = DWT_TH + 2 * R, PC = DWT_TW + 2 * R, G = cat::kDwGroup;
+  const int tid = threadIdx.x;
+  constexpr int SIT = (PR * PC * G + 255) / 256;      // all of the thread's loads in flight before the first LDS store
+  f4 xv[SIT];
+#pragma unroll
+  for (int it = 0; it < SIT; ++it) {
+    const int i = tid + it * 256;
+    xv[it] = f4{0.f, 0.f, 0.f, 0.f};      // out-of-plane taps of zero padding stay literal zeros: never x * 0 (dw_multi_taps)
+    if (i < PR * PC * gn) {
+      const int pix = i / gn, q = q0 + i - pix * gn;
+      const int r = pix / PC, c = pix - r * PC;
+      int iy = oy0 - R + r, ix = ox0 - R + c;
+      bool v;
+      if (p.reflect) {
+        v = iy > -p.H && iy < 2 * p.H - 1 && ix > -p.W && ix < 2 * p.W - 1;      // beyond a ragged tile's mirror range: never read
+        iy = cat::reflect_idx(iy, p.H);
+        ix = cat::reflect_idx(ix, p.W);
+      } else {
+        v = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
+      }
+      if (v) xv[it] = *reinterpret_cast<const f4*>(p.x + (((int64_t)n * p.H + iy) * p.W + ix) * p.xcs + q * 4);
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < SIT; ++it) {
+    const int i = tid + it * 256;
+    if (i < PR * PC * gn) tile[(i % gn) * DWT_PS + i / gn] = xv[it];
+  }
+  __syncthreads();
+  const int px = tid & 127, half = tid >> 7, py = px / DWT_TW, pxx = px % DWT_TW;
+  if (oy0 + py >= p.H || ox0 + pxx >= p.W) return;
+#pragma unroll      // (a runtime loop over the quads keeps all 25 taps and weights of the next quad in flight: 200 registers)
+  for (int k = 0; k < G / 2; ++k) {
+    const int ql = half + 2 * k;
+    if (ql >= gn) break;
+    const f4* pl = tile + ql * DWT_PS;
+    const float* wq = sw + ql * 4;
+    f4 acc = *reinterpret_cast<const f4*>(sw + 25 * DWT_GCS + ql * 4);
+#pragma unroll
+    for (int ky = 0; ky < K; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < K; ++kx) {
+        const f4 xq = pl[(py + ky) * PC + pxx + kx];
+        const f4 wv = *reinterpret_cast<const f4*>(wq + ((O + ky) * 5 + O + kx) * DWT_GCS);
+        acc = __builtin_elementwise_fma(xq, wv, acc);
+      }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = cat::apply_act(acc[e], p.act, p.slope);
+    *reinterpret_cast<f4*>(p.y + (((int64_t)n * p.H + oy0 + py) * p.W + ox0 + pxx) * p.ycs + (q0 + ql) * 4) = acc;
+  }
+}
+
+__global__ __launch_bounds__(256) void dw_multi_tile_kernel(DwTileArgs p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  f4* tile = reinterpret_cast<f4*>(smem);             // [G][DWT_PS] one plane per quad of the group
+  float* sw = smem + cat::kDwGroup * DWT_PS * 4;      // [25][DWT_GCS] frame, then [DWT_GCS] bias
+  int tt, grp;
+  cat::dw_tile_group(blockIdx.x, p.N * p.tiles, p.ng, tt, grp);
+  const int q0 = p.gq0[grp], gn = p.gnq[grp], k = p.gks[grp];
+  const int n = tt / p.tiles, t = tt - n * p.tiles;
+  const int oy0 = (t / p.tiles_x) * DWT_TH, ox0 = (t % p.tiles_x) * DWT_TW;
+  const int cs = p.nq * 4;
+  for (int i = threadIdx.x; i < 26 * gn; i += 256) {
+    const int tap = i / gn, c = (q0 + i - tap * gn) * 4;
+    const f4 v = tap < 25 ? *reinterpret_cast<const f4*>(p.w25 + tap * cs + c)
+                          : (p.bias ? *reinterpret_cast<const f4*>(p.bias + c) : f4{0.f, 0.f, 0.f, 0.f});
+    *reinterpret_cast<f4*>(sw + tap * DWT_GCS + (i - tap * gn) * 4) = v;
+  }
+  if (k == 1) dw_multi_tile_body<1>(p, tile, sw, n, oy0, ox0, q0, gn);
+  else if (k == 3) dw_multi_tile_body<3>(p, tile, sw, n, oy0, ox0, q0, gn);
+  else dw_multi_tile_body<5>(p, tile, sw, n, oy0, ox0, q0, gn);
+}
+
+// Fewest workgroups (tiles x quad groups) for which cat_dwconv2d_multi_fwd takes the tile kernel: four per CU of the 256.  Below, the tile
+// kernel's fixed cost per workgroup (staging, a barrier) buys nothing -- the plane sits in L2 -- and the 1-D walk's finer lanes fill more CUs.
+constexpr int64_t DW_MULTI_TILE_MIN_WG = 1024;
 
 // dxp[n,py,px,c] = sum_k dy[n, py+pe-ky, px+pe-kx, c] * w[c,ky,kx]; (Hin,Win,pe) = (H+2p,W+2p,0) for reflect, (H,W,p) for zero pad.
 __global__ __launch_bounds__(256) void dw_dgrad_kernel(DwArgs p, int Hin, int Win, int pe, int dxcs) {
@@ -318,6 +418,18 @@ int cat_dwconv2d_multi_fwd(const cat_dwmulti_t* g, const float* x, const float* 
   for (int r = 0; r < a.nrun; ++r) a.run_base[r + 1] = a.run_base[r] + npix * a.run_nq[r];
   const double pix = (double)npix;
   cat::ProfScope prof("dwconv_fwd", 2.0 * pix * taps, 2 * 4.0 * pix * 4 * g->nq, stream);
+  static const int tile_on = getenv("CAT_DWMULTI_TILE") ? atoi(getenv("CAT_DWMULTI_TILE")) : 1;      // 0: always the 1-D walk (A/B runs)
+  DwTileArgs t{};
+  t.tiles_x = cdiv(g->W, DWT_TW);
+  t.tiles = t.tiles_x * cdiv(g->H, DWT_TH);
+  t.ng = cat::dw_quad_groups(g->ks, g->nq, t.gq0, t.gnq);
+  if (tile_on && (int64_t)g->N * t.tiles * t.ng >= DW_MULTI_TILE_MIN_WG && (int64_t)g->N * t.tiles * t.ng < (int64_t)2147483647) {
+    t.x = x; t.w25 = w25; t.bias = bias; t.y = y;
+    t.N = g->N; t.H = g->H; t.W = g->W; t.nq = g->nq; t.xcs = g->xcs; t.ycs = g->ycs; t.reflect = g->reflect; t.act = g->act; t.slope = g->slope;
+    for (int k = 0; k < t.ng; ++k) t.gks[k] = (unsigned char)g->ks[t.gq0[k]];
+    dw_multi_tile_kernel<<<g->N * t.tiles * t.ng, 256, DWT_LDS, (hipStream_t)stream>>>(t);
+    return cat::check_launch("dwconv2d_multi_fwd");
+  }
   dw_multi_fwd_kernel<<<ew_grid(npix * g->nq), 256, (size_t)26 * 4 * g->nq * sizeof(float), (hipStream_t)stream>>>(a);
   return cat::check_launch("dwconv2d_multi_fwd");
 }
