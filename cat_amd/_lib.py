@@ -76,7 +76,8 @@ class QConv(C.Structure):
 
 
 class QPlan(C.Structure):
-    _fields_ = [(n, c_i) for n in ('cs', 'nq', 'nsplit', 'th', 'tw', 'tiles')] + [('pack_floats', c_l)]
+    _fields_ = [(n, c_i) for n in ('cs', 'nq', 'nsplit', 'th', 'tw', 'tiles')] + [('pack_floats', c_l)] + \
+               [(n, c_i) for n in ('maxit', 'nbuf', 'nblk')]
 
 
 TNORM_MAXSLICE, DWM_MAXQ, PREP_MAXSRC = 8, 24, 8

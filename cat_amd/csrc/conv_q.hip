@@ -630,6 +630,9 @@ int cat_qconv_plan(const cat_qconv_t* g, cat_qplan_t* out) {
   out->tw = cat_q::TW;
   out->tiles = P.tiles * g->ncls;
   out->pack_floats = cat_q::stream_floats(P);
+  out->maxit = P.maxit;
+  out->nbuf = P.nbuf;
+  out->nblk = P.nblk;
   return 0;
 }
 

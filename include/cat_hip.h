@@ -606,6 +606,8 @@ typedef struct {
   int th, tw;          /* output-lattice tile of one workgroup = one statistics entry per class */
   int tiles;           /* statistics entries per image (tiles x ncls) */
   int64_t pack_floats; /* floats of the launch's packed stream: [LDS offset table of every step][filters of every step], all segments */
+  int maxit, nbuf, nblk; /* which kernel runs: staging iterations per thread (2 | 4 | 8; with nq = the instantiation), staged buffers
+                          * (2 if any program has more than one chunk), N blocks over the grid (nsplit = nblk * 16 / th) */
 } cat_qplan_t;
 int cat_qconv_plan(const cat_qconv_t* g, cat_qplan_t* plan);
 /* fewest 16 x 16 lattice tiles for which narrow outputs (<= 8 quads) take the 16 x 16 tiling (default 1024); v < 0 only queries.  Returns the
