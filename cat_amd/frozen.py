@@ -74,8 +74,7 @@ def _plan(block):
     tensors = _tensors(block)
     # weights owned by a FusedAdam change under torch's feet (raw-pointer kernels): such blocks -- a BatchNorm student run in eval mode by
     # evaluate_model between training steps -- re-fold after every optimizer step; the frozen teacher (no optimizer) folds once
-    trainable = any(getattr(t, '_cat_grad_view', None) is not None for t in tensors)
-    key = (tuple((t.data_ptr(), t._version) for t in tensors), optim.weights_epoch() if trainable else -1)
+    key = optim.weights_key(tensors)
     cached = getattr(block, '_cat_frozen', None)
     if cached is not None and cached['key'] == key:
         return cached

@@ -29,6 +29,7 @@ import torch
 from . import _lib as L
 from . import nn as cnn
 from . import ops
+from . import optim
 from . import rng
 from . import tconv
 from . import fused_unit as U
@@ -289,15 +290,11 @@ class _BlockFn(torch.autograd.Function):
         if ops.act_cs(dy) != p.cs:
             raise RuntimeError('fused block backward: gradient pixel stride differs from the activation')
         if pw.weight is not None:
-            tg, tb = ops._grad_target(pw.weight), ops._grad_target(pw.bias)
-            if tg is not None and tb is not None:       # FusedAdam-owned: written (or accumulated) in place
-                sg, sb = pw.weight._cat_grad_state, pw.bias._cat_grad_state
-                dt = _norm_bwd(p, n, hw, c, p.cs, t, dy, pw.weight, pw.bias, mrp, L.ACT_NONE, 0.0, tg, tb, 0 if sg['fresh'] else 1)
-                sg['fresh'] = sb['fresh'] = False
-            else:
-                dgp, dbp = torch.empty_like(pw.weight), torch.empty_like(pw.bias)
-                dt = _norm_bwd(p, n, hw, c, p.cs, t, dy, pw.weight, pw.bias, mrp, L.ACT_NONE, 0.0, dgp, dbp)
-                grads[id(pw.weight)], grads[id(pw.bias)] = dgp, dbp
+            sink = optim.claim([pw.weight, pw.bias], 'fused block backward')       # FusedAdam-owned: written (or accumulated) in place
+            (dgp, dbp), acc = sink or ((torch.empty_like(pw.weight), torch.empty_like(pw.bias)), 0)
+            dt = _norm_bwd(p, n, hw, c, p.cs, t, dy, pw.weight, pw.bias, mrp, L.ACT_NONE, 0.0, dgp, dbp, acc)
+            if sink is None:
+                grads[id(pw.weight)], grads[id(pw.bias)] = optim.deliver(pw.weight, dgp), optim.deliver(pw.bias, dbp)
         else:
             dt = _norm_bwd(p, n, hw, c, p.cs, t, dy, None, None, mrp, L.ACT_NONE, 0.0, None, None)
         # ---- 2. re-materialise the hidden activations (inputs of the second convs / of the depthwise convs); with dropout the forward's

@@ -318,8 +318,7 @@ def _eval_affine(p):
         tensors += [b['bn1'].weight, b['bn1'].bias, b['bn1'].running_mean, b['bn1'].running_var]
     for b in p.dws:
         tensors += [b['bn2'].weight, b['bn2'].bias, b['bn2'].running_mean, b['bn2'].running_var]
-    trainable = any(getattr(t, '_cat_grad_view', None) is not None for t in tensors if t is not None)
-    key = (tuple((t.data_ptr(), t._version) if t is not None else None for t in tensors), optim.weights_epoch() if trainable else -1)
+    key = optim.weights_key(tensors)
     cached = getattr(p, 'eval_ss', None)
     if cached is not None and cached[0] == key:
         return cached[1], cached[2]

@@ -214,8 +214,7 @@ class Plan:
         self.tables_version = getattr(self, 'tables_version', 0) + 1
 
     def _epoch_key(self):
-        trainable = any(getattr(q, '_cat_grad_view', None) is not None for q in self.params)
-        return (optim.weights_epoch() if trainable else -1, tuple(q._version for q in self.params))
+        return (optim.epoch_of(self.params), tuple(q._version for q in self.params))
 
     def ptrs_now(self):
         return tuple(q.data_ptr() for q in self.params)
@@ -382,32 +381,15 @@ def dw_bwd(p, a1, da1, dzd, grads, reflect=False):
     nb = len(p.dws)
     gd = dwm_geom(p, n, h, w, reflect)
     wts = [b['dconv'].weight for b in p.dws]
-    tg = [ops._grad_target(q) for q in wts]
-    owned = all(t_ is not None for t_ in tg)
-    if owned:
-        fresh = {q._cat_grad_state['fresh'] for q in wts}
-        if len(fresh) != 1:
-            raise RuntimeError(f'{p.what} backward: depthwise gradient buffers out of sync')
-        acc_dw, dsts = (0 if fresh.pop() else 1), tg
-        for q in wts:
-            q._cat_grad_state['fresh'] = False
-            grads[id(q)] = None
-    else:
-        acc_dw, dsts = 0, [torch.empty_like(q) for q in wts]
-        for q, d_, tq in zip(wts, dsts, tg):
-            if tq is None:
-                grads[id(q)] = d_
+    sink = optim.claim(wts, f'{p.what} backward (depthwise)')
+    dsts, acc_dw = sink or ([torch.empty_like(q) for q in wts], 0)
     IA = C.c_int * nb
     wsd = ops.workspace(L.query('cat_dwm_bwd_ws_bytes', C.byref(gd)), a1.device)
     L.call('cat_dwm_bwd', C.byref(gd), C.c_void_p(a1.data_ptr() + 4 * p.dw_in0), ops._p(dzd), ops._p(p.w25),
            C.c_void_p(da1.data_ptr() + 4 * p.dw_in0), p.hc1, nb, IA(*[b['od'] for b in p.dws]), IA(*[b['m'] for b in p.dws]),
            IA(*[b['kd'] for b in p.dws]), (C.c_void_p * nb)(*[d_.data_ptr() for d_ in dsts]), acc_dw, ops._p(wsd), ops._stream())
-    if not owned:          # mixed ownership (tests): deliver into the owned views by hand
-        for q, d_, tq in zip(wts, dsts, tg):
-            if tq is not None:
-                (tq.copy_ if q._cat_grad_state['fresh'] else tq.add_)(d_)
-                q._cat_grad_state['fresh'] = False
-                grads[id(q)] = None
+    for q, d_ in zip(wts, dsts):          # not all owned (tests): fresh tensors, copied / added into the views of those that are
+        grads[id(q)] = None if sink is not None else optim.deliver(q, d_)
 
 
 def dgrad1_segs(p, dz1, M=0):
@@ -422,36 +404,23 @@ def scatter_param_grads(p, grads):
     buffers when all targets are FusedAdam-owned, tensors recorded in `grads` (or copies into the owned views) otherwise."""
     dev = p.dev
     all_t = [q for _, _, _, q in p.targets] + [t2[5] for t2 in p.targets2d]
-    owned = [getattr(q, '_cat_grad_view', None) is not None for q in all_t]
-    if all_t and all(owned):
-        fresh = {q._cat_grad_state['fresh'] for q in all_t}
-        if len(fresh) != 1:
-            raise RuntimeError(f'{p.what} backward: gradient buffers of one unit out of sync')
-        views = tuple(q._cat_grad_view.data_ptr() for q in all_t)
+    sink = optim.claim(all_t, f'{p.what} backward')
+    if sink is not None:
+        views = tuple(gv.data_ptr() for gv in sink[0])
         if p.scatter_jobs is None or p.scatter_jobs[3] != views:
-            jobs = [dict(kind=3, srcs=[p.gv[v].data_ptr() + 4 * o, q._cat_grad_view.data_ptr()], nsrc=2, n=cnt, threads=cnt) for v, o, cnt, q in p.targets]
+            dst = dict(zip(map(id, all_t), sink[0]))
+            jobs = [dict(kind=3, srcs=[p.gv[v].data_ptr() + 4 * o, dst[id(q)].data_ptr()], nsrc=2, n=cnt, threads=cnt) for v, o, cnt, q in p.targets]
             # a one-channel conv weight is stored unpadded (wcs 1): never more columns than the destination row holds
             for v, o, rows, cols, sstr_, q in p.targets2d:
-                wcs_q = ops._grad_wcs(q._cat_grad_view)
+                wcs_q = ops._grad_wcs(dst[id(q)])
                 cq = min(cols, wcs_q)
-                jobs.append(dict(kind=4, srcs=[p.gv[v].data_ptr() + 4 * o, q._cat_grad_view.data_ptr()], nsrc=2, n=rows * cq, cs=cq, wn=sstr_,
+                jobs.append(dict(kind=4, srcs=[p.gv[v].data_ptr() + 4 * o, dst[id(q)].data_ptr()], nsrc=2, n=rows * cq, cs=cq, wn=sstr_,
                                  wcs=wcs_q, threads=rows * cq))
             p.scatter_jobs = p._jobs_to_dev(jobs) + (views,)
         tj, nj, nb, _ = p.scatter_jobs
-        L.call('cat_prep_run', ops._p(tj), nj, nb, 0 if fresh.pop() else 1, ops._stream())
-        for q in all_t:
-            q._cat_grad_state['fresh'] = False
-            grads[id(q)] = None
+        L.call('cat_prep_run', ops._p(tj), nj, nb, sink[1], ops._stream())
+        grads.update((id(q), None) for q in all_t)
         return
-
-    def deliver(q, gq):
-        tgt = getattr(q, '_cat_grad_view', None)
-        if tgt is not None:
-            stq = q._cat_grad_state
-            (tgt.copy_ if stq['fresh'] else tgt.add_)(gq)
-            stq['fresh'] = False
-            gq = None
-        grads[id(q)] = gq
     for v, o, cnt, q in p.targets:
         flat = p.gv[v][o:o + cnt]
         if q.dim() == 4:      # rows of a merged weight gradient: back into the parameter's [O][kh][kw][wcs] storage
@@ -459,10 +428,10 @@ def scatter_param_grads(p, grads):
             torch.as_strided(gq, (cnt,), (1,), gq.storage_offset()).copy_(flat)
         else:
             gq = flat.clone()
-        deliver(q, gq)
+        grads[id(q)] = optim.deliver(q, gq)
     for v, o, rows, cols, sstr_, q in p.targets2d:
         gq = ops.padded_weight_like(q.shape, dev)
         cols = min(cols, ops.weight_wcs(gq))
         src2 = torch.as_strided(p.gv[v], (rows, cols), (sstr_, 1), o)
         torch.as_strided(gq, (rows, cols), (ops.weight_wcs(gq), 1), gq.storage_offset()).copy_(src2)
-        deliver(q, gq)
+        grads[id(q)] = optim.deliver(q, gq)

@@ -145,8 +145,7 @@ def _folded_eval_bn(conv, bn, out_dim):
     One-time setup arithmetic, not part of the per-step kernel stream."""
     tensors = [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
     # optimizer-owned weights are updated through raw pointers (no version bump): such layers re-fold after every optimizer step
-    trainable = any(getattr(t, '_cat_grad_view', None) is not None for t in tensors if t is not None)
-    key = (tuple((t.data_ptr(), t._version) if t is not None else None for t in tensors), optim.weights_epoch() if trainable else -1)
+    key = optim.weights_key(tensors)
     cache = getattr(conv, '_cat_fold', None)
     if cache is not None and cache[0] == key:
         return cache[1], cache[2]

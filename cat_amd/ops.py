@@ -10,7 +10,7 @@ import warnings
 
 import torch
 
-from . import _lib as L
+from . import _lib as L, optim
 from ._lib import ConvGeom, NormGeom
 
 STATS = {'conform_copies': 0}   # non-native layout fix-ups; must stay 0 on the distillation hot path
@@ -285,19 +285,12 @@ def _conv_geom(n, h, w, cin, xcs, ho, wo, cout, ycs, kh, kw, stride, pad, pad_mo
     return ConvGeom(n, h, w, cin, xcs, ho, wo, cout, ycs, kh, kw, stride, pad, pad_mode, act, slope, ycw, wcs)
 
 
-def _grad_target(param):
-    """FusedAdam registers a flat gradient buffer view on its parameters: wgrad kernels then write (or
-    accumulate) straight into it and autograd sees no weight gradient at all."""
-    return getattr(param, '_cat_grad_view', None)
-
-
 def _write_param_grad(param, kernel):
     """kernel(dst_tensor, accumulate_flag).  Returns the tensor to hand back to autograd (None if direct)."""
-    tgt = _grad_target(param)
-    if tgt is not None:
-        st = param._cat_grad_state
-        kernel(tgt, 0 if st['fresh'] else 1)
-        st['fresh'] = False
+    sink = optim.claim([param], 'weight gradient')
+    if sink is not None:
+        (dst,), accumulate = sink
+        kernel(dst, accumulate)
         return None
     if param.dim() == 4 and param.shape[1] > 1:
         g = padded_weight_like(param.shape, param.device)
@@ -378,12 +371,11 @@ def packed_filter(weight, wcl, mode):
     """The conv weight in the MFMA-group order cat_tconv_fwd consumes, cached on the tensor and re-packed (in place) when the
     weight changed: torch's version counter for ordinary tensors, the optimizer epoch for FusedAdam-owned parameters (updated
     through raw pointers).  One ~2 us launch per layer and direction per step."""
-    from . import optim, tconv
+    from . import tconv
     owner = weight if weight is not None else wcl
     if owner is not wcl and owner.data_ptr() != wcl.data_ptr():      # a re-laid-out temporary (foreign layout): nothing to key a cache on
         return tconv.pack(wcl, mode)
-    trainable = getattr(owner, '_cat_grad_view', None) is not None
-    key = (wcl.data_ptr(), wcl._version, optim.weights_epoch() if trainable else -1)
+    key = (wcl.data_ptr(), wcl._version, optim.epoch_of([owner]))
     cache = getattr(owner, '_cat_pk', None)
     if cache is None:
         cache = owner._cat_pk = {}
@@ -412,10 +404,8 @@ def _conv_fwd(g, x, w, bias, y, st):
 def transposed_filter(weight, wcl, g):
     """[Cin][kh][kw][Cout] copy of a conv weight for cat_conv2d_dgrad_t, cached on the tensor and refreshed when the weight changed (same
     keying as packed_filter: version counter, or the optimizer epoch for FusedAdam-owned parameters)."""
-    from . import optim
     owner = weight if weight is not None else wcl
-    trainable = getattr(owner, '_cat_grad_view', None) is not None
-    key = (wcl.data_ptr(), wcl._version, optim.weights_epoch() if trainable else -1)
+    key = (wcl.data_ptr(), wcl._version, optim.epoch_of([owner]))
     ent = getattr(owner, '_cat_wt', None)
     if ent is not None and ent[0] == key:
         return ent[1]
@@ -755,24 +745,12 @@ class NormActFn(torch.autograd.Function):
         st = _stream()
         need_g = gamma is not None and ctx.needs_input_grad[1]
         need_b = beta is not None and ctx.needs_input_grad[2]
-        dgamma = dbeta = None
-        tg = _grad_target(ctx.gamma) if need_g else None
-        tb = _grad_target(ctx.beta) if need_b else None
-        direct = need_g and need_b and tg is not None and tb is not None
-        if direct:
-            sg, sb = ctx.gamma._cat_grad_state, ctx.beta._cat_grad_state
-            if sg['fresh'] != sb['fresh']:
-                raise RuntimeError('norm backward: gamma / beta gradient buffers out of sync')
-            acc = 0 if sg['fresh'] else 1
-            L.call('cat_norm_bwd', C.byref(g), _p(x), _p(dy), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx), _p(tg), _p(tb), acc,
-                   _p(ws), st)
-            sg['fresh'] = sb['fresh'] = False
-        else:
-            dgamma = torch.empty_like(gamma) if need_g else None
-            dbeta = torch.empty_like(beta) if need_b else None
-            L.call('cat_norm_bwd', C.byref(g), _p(x), _p(dy), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta), 0,
-                   _p(ws), st)
-        return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None
+        sink = optim.claim([ctx.gamma, ctx.beta], 'norm backward') if need_g and need_b else None
+        dgamma = torch.empty_like(gamma) if need_g and sink is None else None
+        dbeta = torch.empty_like(beta) if need_b and sink is None else None
+        (pg, pb), acc = sink or ((dgamma, dbeta), 0)
+        L.call('cat_norm_bwd', C.byref(g), _p(x), _p(dy), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx), _p(pg), _p(pb), acc, _p(ws), st)
+        return dx, optim.deliver(ctx.gamma, dgamma), optim.deliver(ctx.beta, dbeta), None, None, None, None, None, None, None, None, None
 
 
 def norm_from_tiles(tiles, n, c, groups, gamma, beta, running_mean, running_var, num_batches, eps, momentum, mean=None, rstd=None):
@@ -1206,23 +1184,13 @@ class SyncBNFn(torch.autograd.Function):
         need_g = gamma is not None and ctx.needs_input_grad[1]
         need_b = beta is not None and ctx.needs_input_grad[2]
         dx = empty_act(n, c, h, w, x.device, cs) if ctx.needs_input_grad[0] else None
-        dgamma = dbeta = None
-        tg = _grad_target(ctx.gamma) if need_g else None
-        tb = _grad_target(ctx.beta) if need_b else None
-        if need_g and need_b and tg is not None and tb is not None:
-            sg, sb = ctx.gamma._cat_grad_state, ctx.beta._cat_grad_state
-            if sg['fresh'] != sb['fresh']:
-                raise RuntimeError('batch norm backward: gamma / beta gradient buffers out of sync')
-            acc = 0 if sg['fresh'] else 1
-            pg, pb = tg, tb
-            sg['fresh'] = sb['fresh'] = False
-        else:
-            acc = 0
-            pg = dgamma = torch.empty_like(gamma) if need_g else None
-            pb = dbeta = torch.empty_like(beta) if need_b else None
+        sink = optim.claim([ctx.gamma, ctx.beta], 'batch norm backward') if need_g and need_b else None
+        dgamma = torch.empty_like(gamma) if need_g and sink is None else None
+        dbeta = torch.empty_like(beta) if need_b and sink is None else None
+        (pg, pb), acc = sink or ((dgamma, dbeta), 0)
         L.call('cat_bn_apply_bwd', _p(x), _p(dy), _p(gamma), _p(beta), _p(a), _p(b), _p(sums), float(count), _p(local), _p(dx), _p(pg), _p(pb),
                acc, m, c, cs, act, slope, st)
-        return dx, dgamma, dbeta, None, None, None, None, None, None
+        return dx, optim.deliver(ctx.gamma, dgamma), optim.deliver(ctx.beta, dbeta), None, None, None, None, None, None
 
 
 class SpadeFn(torch.autograd.Function):

@@ -29,6 +29,54 @@ def _bump_weights_epoch():
     _WEIGHTS_EPOCH += 1
 
 
+# ---- what the rest of the package needs to know about a FusedAdam-owned tensor: how to key a cache on it, and where its gradient goes
+def owned(t):
+    """True iff a FusedAdam registered `t` (its gradient lives in a flat buffer, its value changes without a `_version` bump)."""
+    return getattr(t, '_cat_grad_view', None) is not None
+
+
+def epoch_of(tensors):
+    """The weights epoch if any of `tensors` (None entries allowed) is owned, -1 otherwise: the part of a cache key `_version` cannot give."""
+    return _WEIGHTS_EPOCH if any(owned(t) for t in tensors if t is not None) else -1
+
+
+def weights_key(tensors):
+    """Cache key of an operand derived from `tensors` (None entries allowed): changes when any of them moved or changed value."""
+    return (tuple((t.data_ptr(), t._version) if t is not None else None for t in tensors), epoch_of(tensors))
+
+
+def _adopt(p, view):
+    """Register `view` (a slice of a flat gradient buffer) as the gradient sink of `p`."""
+    p._cat_grad_view = view
+    p._cat_grad_state = {'fresh': True}
+    p.grad = view
+
+
+def claim(params, what):
+    """The gradient sinks of parameters ONE launch writes.  All owned: (views, accumulate), accumulate 0 for the first writer after
+    zero_grad() and 1 afterwards; the launch must then write (or add to) every view, and autograd is handed None for them.  Any parameter
+    not owned (or none at all): None, and nothing is touched -- the caller writes fresh tensors and passes each through deliver()."""
+    if not params or not all(owned(p) for p in params):
+        return None
+    states = [p._cat_grad_state for p in params]
+    fresh = states[0]['fresh']
+    if any(s['fresh'] != fresh for s in states):
+        raise RuntimeError(f'{what}: gradient buffers out of sync')
+    for s in states:
+        s['fresh'] = False
+    return [p._cat_grad_view for p in params], 0 if fresh else 1
+
+
+def deliver(param, g):
+    """A gradient computed outside the sink (mixed ownership): copied or added into an owned parameter's view; returns what autograd gets."""
+    if g is None or not owned(param):
+        return g
+    state = param._cat_grad_state
+    (param._cat_grad_view.copy_ if state['fresh'] else param._cat_grad_view.add_)(g)
+    state['fresh'] = False
+    return None
+
+
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
@@ -80,10 +128,7 @@ class FusedAdam(torch.optim.Optimizer):
                 fp[off:off + span].copy_(torch.as_strided(p.data, (span,), (1,), p.storage_offset()))
                 shape, stride = tuple(p.shape), tuple(p.stride())
                 p.data = torch.as_strided(fp, shape, stride, off)
-                gv = torch.as_strided(fg, shape, stride, off)
-                p._cat_grad_view = gv
-                p._cat_grad_state = {'fresh': True}
-                p.grad = gv
+                _adopt(p, torch.as_strided(fg, shape, stride, off))
             flats.append(dict(p=fp, g=fg, m=torch.zeros_like(fp), v=torch.zeros_like(fp), n=total, step=0, params=params,
                               offs=offs, hyper=torch.zeros(8, device=dev, dtype=torch.float32), hyper_host=None))
         self._flat = flats

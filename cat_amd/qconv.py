@@ -156,9 +156,8 @@ class Layer:
             plan = self._plans[key] = plan_of(g)
         # packed stream: keyed like ops.packed_filter (version counter, or the optimizer epoch for FusedAdam-owned parameters)
         wcl, wcs = ops.weight_cl(self.weight)
-        trainable = getattr(self.weight, '_cat_grad_view', None) is not None
         sig = (plan.cs, plan.nq, plan.nsplit, int(plan.pack_floats), plan.th)
-        wkey = (wcl.data_ptr(), wcl._version, optim.weights_epoch() if trainable else -1, sig, key)
+        wkey = (wcl.data_ptr(), wcl._version, optim.epoch_of([self.weight]), sig, key)
         if self._pk is None or self._pk[0] != wkey:
             same_layout = self._pk is not None and self._pk[0][3:] == wkey[3:] and self._pk[1].device == x.device
             # a new weight version re-packs in place; another geometry gets a fresh zeroed stream (its spare table rows / filter step must read 0)

@@ -185,3 +185,69 @@ def test_fused_block_plan_follows_replaced_parameters():
     new = blk.res_ops[0][1][1].weight
     assert new.grad is not None and blk.pw_bn.bias.grad is not None
     assert rel(new.grad, g_old) < 1e-4      # (running statistics moved between the two steps: batch statistics did not)
+
+
+def _small_case(dev):
+    """The smallest plane of this file (8 x 40 x 32 x 48: exactly the fewest tiles the fused path accepts), batch-norm block, NHWC operands."""
+    from cat_amd import ops
+    blk = _block('batch', dev, 40, (7, 0, 9), (16, 5, 0), 'reflect')
+    x = ops.to_nhwc(detfill.normal((8, 40, 32, 48), 5).to(dev))
+    gy = ops.to_nhwc(detfill.normal((8, 40, 32, 48), 6).to(dev))
+    return blk, x, gy
+
+
+def _backward(blk, x, gy):
+    from cat_amd import fused_block
+    xg = x.detach().requires_grad_(True)
+    assert fused_block.applicable(blk, xg)
+    blk(xg).backward(gy)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize('streams', [False, True])
+def test_fused_block_second_backward_accumulates_into_optimizer_buffers(streams):
+    """Without a zero_grad() in between, a second backward ADDS to the gradients in FusedAdam's flat buffer: the first writer after
+    zero_grad() overwrites, every later one accumulates.  Same input twice -> exactly twice the gradient (g + g is exact in fp32 and the
+    reductions have a fixed order), on one stream (batched weight gradients) and with the side-stream jobs."""
+    from cat_amd import _lib, ops
+    from cat_amd.optim import FusedAdam
+    _lib.load()
+    blk, x, gy = _small_case(torch.device('cuda:0'))
+    opt = FusedAdam(list(blk.parameters()), lr=0.0)
+    was = ops.branch_streams_enabled()
+    ops.set_branch_streams(streams)
+    try:
+        opt.zero_grad()
+        _backward(blk, x, gy)
+        once = {k: q.grad.clone() for k, q in blk.named_parameters()}
+        _backward(blk, x, gy)
+    finally:
+        ops.set_branch_streams(was)
+    for k, q in blk.named_parameters():
+        assert float(once[k].abs().max()) > 0.0, k
+        assert q.grad.data_ptr() == q._cat_grad_view.data_ptr(), k
+        assert torch.equal(q.grad, once[k] + once[k]), k
+
+
+def test_fused_block_backward_with_mixed_parameter_ownership():
+    """FusedAdam owns every other parameter only: those find their gradient in their flat-buffer view (p.grad aliases it), the others get
+    theirs through autograd, and both are bitwise what the same block computes with no optimizer at all."""
+    from cat_amd import _lib
+    from cat_amd.optim import FusedAdam
+    _lib.load()
+    blk, x, gy = _small_case(torch.device('cuda:0'))
+    plain = copy.deepcopy(blk)
+    _backward(plain, x, gy)
+    params = list(blk.parameters())
+    mine = {id(q) for q in params[::2]}
+    FusedAdam(params[::2], lr=0.0).zero_grad()
+    _backward(blk, x, gy)
+    ref = dict(plain.named_parameters())
+    for k, q in blk.named_parameters():
+        view = getattr(q, '_cat_grad_view', None)
+        assert (view is not None) == (id(q) in mine), k
+        assert q.grad is not None, k
+        if view is not None:
+            assert q.grad.data_ptr() == view.data_ptr(), k
+        assert float(q.grad.abs().max()) > 0.0, k
+        assert torch.equal(q.grad, ref[k].grad), k
