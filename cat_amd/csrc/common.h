@@ -99,6 +99,33 @@ __device__ __forceinline__ float act_grad_from_out(float y, int act, float slope
   }
 }
 
+// One element of a scalar loss (cat_loss_fwd / cat_loss_multi_fwd) and its derivative in a: ka_loss.hip and loss_multi.hip evaluate these two and
+// nothing else, which is what makes cat_loss_multi_* bit-identical to cat_loss_fwd/bwd term by term.  CAT_LOSS_MSE is the default arm.
+__device__ __forceinline__ float loss_term(int kind, float a, float b, float t) {
+  switch (kind) {
+    case CAT_LOSS_L1: return fabsf(a - b);
+    case CAT_LOSS_LSGAN: return (a - t) * (a - t);
+    case CAT_LOSS_HINGE_D_REAL: return -fminf(a - 1.f, 0.f);
+    case CAT_LOSS_HINGE_D_FAKE: return -fminf(-a - 1.f, 0.f);
+    case CAT_LOSS_NEG_MEAN: return -a;
+    case CAT_LOSS_BCE_LOGITS: return (1.f - t) * a + fmaxf(-a, 0.f) + log1pf(expf(-fabsf(a)));   // BCE with logits against the constant target t
+    case CAT_LOSS_MEAN: return a;
+    default: return (a - b) * (a - b);
+  }
+}
+__device__ __forceinline__ float loss_grad(int kind, float a, float b, float t) {
+  switch (kind) {
+    case CAT_LOSS_L1: return a > b ? 1.f : (a < b ? -1.f : 0.f);
+    case CAT_LOSS_LSGAN: return 2.f * (a - t);
+    case CAT_LOSS_HINGE_D_REAL: return a - 1.f < 0.f ? -1.f : 0.f;   // torch.min(x-1, 0): ties send the gradient to ... see tests (measure zero)
+    case CAT_LOSS_HINGE_D_FAKE: return -a - 1.f < 0.f ? 1.f : 0.f;
+    case CAT_LOSS_NEG_MEAN: return -1.f;
+    case CAT_LOSS_BCE_LOGITS: return 1.f / (1.f + expf(-a)) - t;   // sigmoid(a) - t
+    case CAT_LOSS_MEAN: return 1.f;
+    default: return 2.f * (a - b);
+  }
+}
+
 __device__ __forceinline__ int reflect_idx(int i, int n) {
   i = i < 0 ? -i : i;
   return i >= n ? 2 * n - 2 - i : i;

@@ -211,31 +211,6 @@ int launch_gram(const float* X, int64_t D, int N, float* part, const GramPlan& p
 }
 
 // ------------------------------------------------------------------------------------------------ scalar losses
-__device__ __forceinline__ float loss_term(int kind, float a, float b, float t) {
-  switch (kind) {
-    case 0: return fabsf(a - b);
-    case 1: return (a - t) * (a - t);
-    case 2: return -fminf(a - 1.f, 0.f);
-    case 3: return -fminf(-a - 1.f, 0.f);
-    case 4: return -a;
-    case 6: return (1.f - t) * a + fmaxf(-a, 0.f) + log1pf(expf(-fabsf(a)));   // BCE with logits against the constant target t
-    case 7: return a;
-    default: return (a - b) * (a - b);
-  }
-}
-__device__ __forceinline__ float loss_grad(int kind, float a, float b, float t) {
-  switch (kind) {
-    case 0: return a > b ? 1.f : (a < b ? -1.f : 0.f);
-    case 1: return 2.f * (a - t);
-    case 2: return a - 1.f < 0.f ? -1.f : 0.f;   // torch.min(x-1, 0): ties send the gradient to ... see tests (measure zero)
-    case 3: return -a - 1.f < 0.f ? 1.f : 0.f;
-    case 4: return -1.f;
-    case 6: return 1.f / (1.f + expf(-a)) - t;   // sigmoid(a) - t
-    case 7: return 1.f;
-    default: return 2.f * (a - b);
-  }
-}
-
 __global__ __launch_bounds__(256) void loss_partial_kernel(int kind, const float* __restrict__ a, const float* __restrict__ b, float t,
                                                            int64_t nquads, int nq, int C, float* __restrict__ part) {
   __shared__ float red[4];
@@ -247,7 +222,7 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(int kind, const float
     if (b) bv = *reinterpret_cast<const f4*>(b + i * 4);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      if (c + e < C) s += loss_term(kind, av[e], bv[e], t);
+      if (c + e < C) s += cat::loss_term(kind, av[e], bv[e], t);
   }
   s = cat::wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -274,7 +249,7 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(int kind, const float* __
     if (b) bv = *reinterpret_cast<const f4*>(b + i * 4);
     f4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = c + e < C ? g * loss_grad(kind, av[e], bv[e], t) : 0.f;
+    for (int e = 0; e < 4; ++e) o[e] = c + e < C ? g * cat::loss_grad(kind, av[e], bv[e], t) : 0.f;
     *reinterpret_cast<f4*>(da + i * 4) = o;
   }
 }
@@ -322,8 +297,8 @@ size_t cat_loss_ws_bytes(int64_t M) { (void)M; return 1024 * sizeof(float); }
 
 int cat_loss_fwd(int kind, const float* a, const float* b, float target, int64_t M, int C, int cs, float* out, void* ws,
                  cat_stream_t stream) {
-  CAT_REQUIRE(kind >= 0 && kind <= 7 && cs % 4 == 0 && cs >= C && ws, "loss: bad arguments");
-  CAT_REQUIRE((kind != 0 && kind != 5) || b, "loss: kind %d needs a second tensor", kind);
+  CAT_REQUIRE(kind >= 0 && kind <= CAT_LOSS_MEAN && cs % 4 == 0 && cs >= C && ws, "loss: bad arguments");
+  CAT_REQUIRE((kind != CAT_LOSS_L1 && kind != CAT_LOSS_MSE) || b, "loss: kind %d needs a second tensor", kind);
   const int64_t nquads = M * (cs / 4);
   const int nb = loss_nb(nquads);
   cat::ProfScope prof("loss", 0.0, 4.0 * M * cs * (b ? 2 : 1), stream);
@@ -335,7 +310,7 @@ int cat_loss_fwd(int kind, const float* a, const float* b, float target, int64_t
 
 int cat_loss_bwd(int kind, const float* a, const float* b, float target, int64_t M, int C, int cs, const float* gout, float scale,
                  float* da, cat_stream_t stream) {
-  CAT_REQUIRE(kind >= 0 && kind <= 7 && cs % 4 == 0 && cs >= C, "loss: bad arguments");
+  CAT_REQUIRE(kind >= 0 && kind <= CAT_LOSS_MEAN && cs % 4 == 0 && cs >= C, "loss: bad arguments");
   const int64_t nquads = M * (cs / 4);
   int64_t nb = (nquads + 255) / 256;
   if (nb > 8192) nb = 8192;

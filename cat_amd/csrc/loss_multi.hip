@@ -18,31 +18,6 @@ struct MultiArgs {
   int T;
 };
 
-__device__ __forceinline__ float term_value(int kind, float a, float b, float t) {
-  switch (kind) {
-    case 0: return fabsf(a - b);
-    case 1: return (a - t) * (a - t);
-    case 2: return -fminf(a - 1.f, 0.f);
-    case 3: return -fminf(-a - 1.f, 0.f);
-    case 4: return -a;
-    case 6: return (1.f - t) * a + fmaxf(-a, 0.f) + log1pf(expf(-fabsf(a)));
-    case 7: return a;
-    default: return (a - b) * (a - b);
-  }
-}
-__device__ __forceinline__ float term_grad(int kind, float a, float b, float t) {
-  switch (kind) {
-    case 0: return a > b ? 1.f : (a < b ? -1.f : 0.f);
-    case 1: return 2.f * (a - t);
-    case 2: return a - 1.f < 0.f ? -1.f : 0.f;
-    case 3: return -a - 1.f < 0.f ? 1.f : 0.f;
-    case 4: return -1.f;
-    case 6: return 1.f / (1.f + expf(-a)) - t;
-    case 7: return 1.f;
-    default: return 2.f * (a - b);
-  }
-}
-
 __device__ __forceinline__ int find_term(const MultiArgs& A, int bid) {
   int t = 0;
   while (t + 1 < A.T && bid >= A.blk0[t + 1]) ++t;
@@ -66,7 +41,7 @@ __global__ __launch_bounds__(256) void loss_multi_partial_kernel(const MultiArgs
     if (b) bv = *reinterpret_cast<const f4*>(b + i * 4);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      if (c + e < C) s += term_value(kind, av[e], bv[e], L.target);
+      if (c + e < C) s += cat::loss_term(kind, av[e], bv[e], L.target);
   }
   s = cat::wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -106,7 +81,7 @@ __global__ __launch_bounds__(256) void loss_multi_bwd_kernel(const MultiArgs A) 
     if (b) bv = *reinterpret_cast<const f4*>(b + i * 4);
     f4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = c + e < C ? g * term_grad(kind, av[e], bv[e], L.target) : 0.f;
+    for (int e = 0; e < 4; ++e) o[e] = c + e < C ? g * cat::loss_grad(kind, av[e], bv[e], L.target) : 0.f;
     *reinterpret_cast<f4*>(da + i * 4) = o;
   }
 }
@@ -124,8 +99,8 @@ int check_terms(const cat_loss_term_t* terms, int T, const char* what) {
   CAT_REQUIRE(terms && T >= 1, "%s: empty table", what);
   for (int t = 0; t < T; ++t) {
     const cat_loss_term_t& L = terms[t];
-    CAT_REQUIRE(L.a && L.kind >= 0 && L.kind <= 7 && L.M >= 1 && L.C >= 1 && L.cs % 4 == 0 && L.cs >= L.C, "%s: term %d: bad arguments", what, t);
-    CAT_REQUIRE((L.kind != 0 && L.kind != 5) || L.b, "%s: term %d: kind %d needs a second tensor", what, t, L.kind);
+    CAT_REQUIRE(L.a && L.kind >= 0 && L.kind <= CAT_LOSS_MEAN && L.M >= 1 && L.C >= 1 && L.cs % 4 == 0 && L.cs >= L.C, "%s: term %d: bad arguments", what, t);
+    CAT_REQUIRE((L.kind != CAT_LOSS_L1 && L.kind != CAT_LOSS_MSE) || L.b, "%s: term %d: kind %d needs a second tensor", what, t, L.kind);
   }
   return 0;
 }

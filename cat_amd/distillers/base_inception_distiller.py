@@ -3,46 +3,19 @@ distillers/base_inception_distiller.py:103-312 for everything on the hot path.  
 reference constructor are host-side I/O that stays with CAT: they are only touched when `opt` carries the corresponding
 paths.  The FID / mIoU networks run on the HIP kernels and are attached with evaluation.attach_fid / attach_miou."""
 import itertools
-import os
-from collections import OrderedDict
 
 import torch
 
+from .. import host
 from .. import loss as closs
 from .. import networks, ops
 from .. import nn as cnn
+from ..lossvalue import LossValue
 from ..optim import FusedAdam
 
 
-class LossValue:
-    """A scalar loss kept on the device: sum_i w_i * t_i.  float() synchronises (trainer.py:135-139 does that only every
-    print_freq iterations); the hot loop never builds these sums with torch arithmetic kernels."""
-
-    def __init__(self, terms):
-        self.terms = [(float(w), t) for w, t in terms]
-
-    def __float__(self):
-        return float(sum(w * float(t) for w, t in self.terms))
-
-    def item(self):
-        return float(self)
-
-    def __mul__(self, k):
-        return LossValue([(w * k, t) for w, t in self.terms])
-
-    __rmul__ = __mul__
-
-    def __add__(self, other):
-        if isinstance(other, (int, float)) and other == 0:
-            return self
-        if isinstance(other, torch.Tensor):
-            other = LossValue([(1.0, other)])
-        return LossValue(self.terms + other.terms)
-
-    __radd__ = __add__
-
-
-class BaseInceptionDistiller:
+class BaseInceptionDistiller(host.StepHost):
+    _NOUN = 'distillers'
     _FLAGS = [  # base_inception_distiller.py:29-101
         ('--teacher_netG', dict(type=str, default='inception_9blocks')),
         ('--student_netG', dict(type=str, default='inception_9blocks')),
@@ -71,23 +44,13 @@ class BaseInceptionDistiller:
 
     def __init__(self, opt):
         assert opt.isTrain
-        self.opt = opt
-        self.gpu_ids = list(getattr(opt, 'gpu_ids', [0]))
-        self.isTrain = opt.isTrain
-        if not torch.cuda.is_available():
-            raise RuntimeError('cat_amd distillers need an MI355X (HIP kernels only; there is no CPU path)')
+        super().__init__(opt)
         ops.default_branch_streams(False)      # one stream: the blocks are a few chip-filling launches (ops.py, branch-level concurrency)
-        # one process drives one GPU (torch.distributed / RCCL handles data parallelism): gpu_ids[0] or LOCAL_RANK
-        dev_index = int(os.environ.get('LOCAL_RANK', self.gpu_ids[0] if self.gpu_ids else 0))
-        self.device = torch.device('cuda', dev_index)
-        torch.cuda.set_device(self.device)
-        self.save_dir = os.path.join(getattr(opt, 'log_dir', '.'), 'checkpoints')
         self.loss_names = ['G_gan', 'G_distill', 'G_recon', 'D_fake', 'D_real']
         self.optimizers = []
-        self.image_paths = []
         self.visual_names = ['real_A', 'Sfake_B', 'Tfake_B', 'real_B']
         self.model_names = ['netG_student', 'netG_teacher', 'netD']
-        dev = [dev_index]
+        dev = self._dev_ids
         self.netG_teacher = networks.define_G(opt.input_nc, opt.output_nc, opt.teacher_ngf, opt.teacher_netG, opt.norm,
                                               opt.teacher_dropout_rate, opt.init_type, opt.init_gain, dev, opt=opt)
         self.netG_student = networks.define_G(opt.input_nc, opt.output_nc, opt.student_ngf, opt.student_netG, opt.norm,
@@ -125,15 +88,10 @@ class BaseInceptionDistiller:
         self.optimizers += [self.optimizer_G, self.optimizer_D]
         self.is_best = False
         self.mapping_hooks = []
-        self._seeds = {}
-        self.dp = None     # cat_amd.parallel.DataParallelReducer when world_size > 1
 
     # -- setup / hooks (base_inception_distiller.py:237-269) -------------------------------------------
     def setup(self, opt, verbose=True):
-        self.schedulers = [networks.get_scheduler(optimizer, opt) for optimizer in self.optimizers]
-        self.load_networks(verbose)
-        if verbose:
-            self.print_networks()
+        super().setup(opt, verbose)
         self.add_mapping_hook()
 
     def add_mapping_hook(self):
@@ -187,15 +145,6 @@ class BaseInceptionDistiller:
         self.image_paths = input.get('path' if self.opt.dataset_mode == 'cityscapes' else 'A_paths', [])
 
     # -- the D half of the step (base_inception_distiller.py:293-312) --------------------------------------
-    def seed(self, value):
-        """Constant 0-d device tensors used as backward seeds (d total / d term)."""
-        value = float(value)
-        t = self._seeds.get(value)
-        if t is None:
-            t = torch.full((), value, device=self.device, dtype=torch.float32)
-            self._seeds[value] = t
-        return t
-
     def backward_D(self):
         with torch.no_grad():
             if self.opt.dataset_mode == 'aligned':
@@ -209,8 +158,7 @@ class BaseInceptionDistiller:
         pred_real = self.netD(real)
         self.loss_D_real = self.criterionGAN(pred_real, True, for_discriminator=True)
         self.loss_D = LossValue([(0.5, self.loss_D_fake), (0.5, self.loss_D_real)])
-        torch.autograd.backward([self.loss_D_fake, self.loss_D_real], [self.seed(0.5), self.seed(0.5)])
-        ops.sync_side_streams()
+        self.backward_terms([(0.5, self.loss_D_fake), (0.5, self.loss_D_real)])
 
     # -- backward_D in gradient-ready STAGES (data-parallel schedule, SURVEY 8e legal overlap 2) ---------------------------------------
     def d_stage_plan(self):
@@ -288,92 +236,29 @@ class BaseInceptionDistiller:
             ops.sync_side_streams()
         return [stage0, stage1, stage2], [slices[2], slices[1], slices[0]]
 
-    # -- bookkeeping shared with models/base_model.py:146-232 -------------------------------------------------
-    def set_requires_grad(self, nets, requires_grad=False):
-        if not isinstance(nets, list):
-            nets = [nets]
-        for net in nets:
-            if net is not None:
-                for param in net.parameters():
-                    param.requires_grad = requires_grad
-
-    def get_current_losses(self):
-        errors_set = OrderedDict()
-        for name in self.loss_names:
-            if not hasattr(self, 'loss_' + name):
-                continue
-            if any(ch.isdigit() for ch in name):
-                key = 'Specific_loss/' + name
-            elif name.startswith('D_'):
-                key = 'D_loss/' + name
-            elif name.startswith('G_'):
-                key = 'G_loss/' + name
-            else:
-                assert False
-            errors_set[key] = float(getattr(self, 'loss_' + name))
-        return errors_set
-
-    def finish_pending(self):
-        """Complete work a schedule deferred past optimize_parameters (the data-parallel step keeps the student's gradient all-reduce
-        and Adam update in flight until the weights are needed): called by everything that reads weights or optimizer state."""
-
-    def get_current_visuals(self):
-        self.finish_pending()
-        return OrderedDict((n, getattr(self, n)) for n in self.visual_names if hasattr(self, n))
-
-    def update_learning_rate(self, logger=None):
-        self.finish_pending()       # a pending Adam step must use the learning rate of the step that produced its gradient
-        for scheduler in self.schedulers:
-            scheduler.step()
-        lr = self.optimizers[0].param_groups[0]['lr']
-        (logger.print_info if logger is not None else print)('learning rate = %.7f\n' % lr)
-
-    def print_networks(self):
-        for name in self.model_names:
-            net = getattr(self, name, None)
-            if net is not None:
-                n = sum(p.numel() for p in net.parameters())
-                print('[Network %s] Total number of parameters : %.3f M' % (name, n / 1e6))
+    def _networks(self):
+        return [(name, getattr(self, name)) for name in self.model_names if getattr(self, name, None) is not None]
 
     # -- checkpoints: same file names / state_dict keys as base_inception_distiller.py:342-396 ------------------
-    def _load(self, net, path, verbose=True):
-        if verbose:
-            print('Load network at %s' % path)
-        net.load_state_dict(torch.load(path, map_location='cpu'))
-
     def load_networks(self, verbose=True, teacher_only=False, restore_pretrain=True):
         opt = self.opt
         if getattr(opt, 'restore_teacher_G_path', None):
-            self._load(self.netG_teacher, opt.restore_teacher_G_path, verbose)
+            host.load_state(self.netG_teacher, opt.restore_teacher_G_path, verbose)
         else:       # the reference loads it unconditionally (base_inception_distiller.py:343): distilling from a random teacher is never intended
             import warnings
             warnings.warn('restore_teacher_G_path is not set: the teacher keeps its initialisation (synthetic-weight runs only)')
         if getattr(opt, 'restore_student_G_path', None):
-            self._load(self.netG_student, opt.restore_student_G_path, verbose)
+            host.load_state(self.netG_student, opt.restore_student_G_path, verbose)
         if getattr(opt, 'restore_D_path', None):
-            self._load(self.netD, opt.restore_D_path, verbose)
+            host.load_state(self.netD, opt.restore_D_path, verbose)
         if getattr(opt, 'restore_A_path', None):
             for i, netA in enumerate(self.netAs):
-                self._load(netA, '%s-%d.pth' % (opt.restore_A_path, i), verbose)
-        if getattr(opt, 'restore_O_path', None):
-            for i, optimizer in enumerate(self.optimizers):
-                optimizer.load_state_dict(torch.load('%s-%d.pth' % (opt.restore_O_path, i), map_location='cpu'))
-                for param_group in optimizer.param_groups:
-                    param_group['lr'] = opt.lr
+                host.load_state(netA, '%s-%d.pth' % (opt.restore_A_path, i), verbose)
+        self.restore_optimizers([opt.lr] * len(self.optimizers))
 
-    def save_networks(self, epoch):
-        self.finish_pending()
-        os.makedirs(self.save_dir, exist_ok=True)
-
-        def cpu_sd(net):   # NCHW/OIHW-contiguous values, the checkpoint wire format
-            return OrderedDict((k, v.detach().cpu().contiguous()) for k, v in net.state_dict().items())
-
-        torch.save(cpu_sd(self.netG_student), os.path.join(self.save_dir, '%s_net_G.pth' % epoch))
-        torch.save(cpu_sd(self.netD), os.path.join(self.save_dir, '%s_net_D.pth' % epoch))
-        for i, net in enumerate(self.netAs):
-            torch.save(cpu_sd(net), os.path.join(self.save_dir, '%s_net_A-%d.pth' % (epoch, i)))
-        for i, optimizer in enumerate(self.optimizers):
-            torch.save(optimizer.state_dict(), os.path.join(self.save_dir, '%s_optim-%d.pth' % (epoch, i)))
+    def _save(self, epoch):
+        host.save_nets(host.distilled_nets(self), epoch, self.save_dir)
+        self.save_optimizers(epoch)
 
     def evaluate_model(self, step, save_image=False):
         """reference inception_distiller.py:204-281: student (and teacher) inference over `self.eval_dataloader` on the HIP kernels, image

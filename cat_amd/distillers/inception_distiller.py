@@ -6,10 +6,11 @@ terms are means over the global batch, the KA term is the SUM of per-shard KAs."
 import torch
 from torch import nn
 
-from .. import ops
+from .. import host, ops
 from ..loss import KA
+from ..lossvalue import LossValue
 from ..prune import model_profiling
-from .base_inception_distiller import BaseInceptionDistiller, LossValue
+from .base_inception_distiller import BaseInceptionDistiller
 
 
 class InceptionDistiller(BaseInceptionDistiller):
@@ -56,7 +57,7 @@ class InceptionDistiller(BaseInceptionDistiller):
             from ..weight_transfer import load_pretrained_weight
             pre = networks.define_G(opt.input_nc, opt.output_nc, opt.pretrained_ngf, opt.pretrained_netG, opt.norm, 0, opt.init_type,
                                     opt.init_gain, [], opt=opt)
-            self._load(pre, opt.restore_pretrained_G_path, verbose)
+            host.load_state(pre, opt.restore_pretrained_G_path, verbose)
             load_pretrained_weight(opt.pretrained_netG, opt.student_netG, pre, self.netG_student, opt.pretrained_ngf, opt.student_ngf)
             del pre
         super(InceptionDistiller, self).load_networks(verbose, teacher_only=teacher_only, restore_pretrain=restore_pretrain)
@@ -101,20 +102,18 @@ class InceptionDistiller(BaseInceptionDistiller):
         gan = self.criterionGAN(pred_fake, True, for_discriminator=False)
         self.loss_G_recon = LossValue([(opt.lambda_recon, recon)])
         self.loss_G_gan = LossValue([(opt.lambda_gan, gan)])
-        terms, seeds = [gan, recon], [self.seed(opt.lambda_gan), self.seed(opt.lambda_recon)]
+        terms = [(opt.lambda_gan, gan), (opt.lambda_recon, recon)]
         if opt.lambda_distill > 0:
             kas = self.calc_distill_loss()
             sign = -1.0 if opt.distill_G_loss_type == 'ka' else 1.0
             self.loss_G_distill = LossValue([(sign * opt.lambda_distill, k) for k in kas])
-            terms += kas
             # DataParallel sums the per-shard distillation terms (KA, or the per-device MSE) while every other term is a mean over
             # the gathered batch: with gradient AVERAGING across ranks their seed therefore carries a factor world_size
-            seeds += [self.seed(sign * opt.lambda_distill * ws)] * len(kas)
+            terms += [(sign * opt.lambda_distill * ws, k) for k in kas]
         else:
             self.loss_G_distill = 0
         self.loss_G = self.loss_G_gan + self.loss_G_recon + self.loss_G_distill
-        torch.autograd.backward(terms, seeds)
-        ops.sync_side_streams()
+        self.backward_terms(terms)
 
     def optimize_parameters(self, steps):
         """forward -> D step -> G step (inception_distiller.py:179-188).  Optionally (`teacher_side_stream`) the frozen teacher's

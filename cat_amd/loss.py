@@ -16,27 +16,29 @@ class GANLoss(nn.Module):
             raise NotImplementedError('gan mode %s not implemented' % gan_mode)
         self.gan_mode = gan_mode
 
-    def __call__(self, prediction, target_is_real, for_discriminator=True):
+    def kind(self, target_is_real, for_discriminator=True):
+        """(kind, target) of one term: the LOSS_* reduction of cat_loss_fwd and its constant target (reference loss.py:33-34, 63-82)."""
         if self.gan_mode == 'lsgan':
-            target = self.real_label if target_is_real else self.fake_label
-            return ops.LossFn.apply(prediction, None, L.LOSS_LSGAN, target)
-        if self.gan_mode == 'vanilla':      # nn.BCEWithLogitsLoss against the expanded label, loss.py:33-34,63-65
-            target = self.real_label if target_is_real else self.fake_label
-            return ops.LossFn.apply(prediction, None, L.LOSS_BCE_LOGITS, target)
-        if self.gan_mode == 'wgangp':       # loss.py:66-70
-            return ops.LossFn.apply(prediction, None, L.LOSS_NEG_MEAN if target_is_real else L.LOSS_MEAN, 0.0)
-        if isinstance(prediction, list):   # multiscale form, loss.py:71-82
+            return L.LOSS_LSGAN, self.real_label if target_is_real else self.fake_label
+        if self.gan_mode == 'vanilla':      # nn.BCEWithLogitsLoss against the expanded label
+            return L.LOSS_BCE_LOGITS, self.real_label if target_is_real else self.fake_label
+        if self.gan_mode == 'wgangp':
+            return (L.LOSS_NEG_MEAN if target_is_real else L.LOSS_MEAN), 0.0
+        if for_discriminator:
+            return (L.LOSS_HINGE_D_REAL if target_is_real else L.LOSS_HINGE_D_FAKE), 0.0
+        assert target_is_real
+        return L.LOSS_NEG_MEAN, 0.0
+
+    def __call__(self, prediction, target_is_real, for_discriminator=True):
+        if self.gan_mode == 'hinge' and isinstance(prediction, list):   # multiscale form, loss.py:71-82
             loss = 0
             for pred_i in prediction:
                 if isinstance(pred_i, list):
                     pred_i = pred_i[-1]
                 loss = loss + self(pred_i, target_is_real, for_discriminator)
             return loss / len(prediction)
-        if for_discriminator:
-            kind = L.LOSS_HINGE_D_REAL if target_is_real else L.LOSS_HINGE_D_FAKE
-            return ops.LossFn.apply(prediction, None, kind, 0.0)
-        assert target_is_real
-        return ops.LossFn.apply(prediction, None, L.LOSS_NEG_MEAN, 0.0)
+        kind, target = self.kind(target_is_real, for_discriminator)
+        return ops.LossFn.apply(prediction, None, kind, target)
 
 
 class L1Loss(nn.Module):

@@ -8,7 +8,7 @@ import torch
 
 from .. import loss as closs
 from .. import networks, ops
-from ..distillers.base_inception_distiller import LossValue
+from ..lossvalue import LossValue
 from ..optim import FusedAdam
 from .base_model import BaseModel
 from .image_pool import ImagePool

@@ -3,7 +3,7 @@ kernels -- generator forward, PatchGAN D step (0.5 * (fake + real)), G step (GAN
 Same op set as the distillation step; LossValue / seeded backward keep torch arithmetic off the path."""
 from .. import loss as closs
 from .. import networks, ops
-from ..distillers.base_inception_distiller import LossValue
+from ..lossvalue import LossValue
 from ..optim import FusedAdam
 from .base_model import BaseModel
 

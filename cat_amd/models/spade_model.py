@@ -4,16 +4,16 @@ VGG losses, two FusedAdam updates (G first, then D) -- with the surface the refe
 cat_amd/spade_model_modules.py; the device, data and bookkeeping halves follow distillers/base_spade_distiller.py; evaluation goes through
 distillers/evaluation.py.  One process drives one GPU: multi-rank training of the teacher is not built."""
 import argparse
-import os
 
 import torch
 
 from .. import ops
 from ..spade_model_modules import SPADEModelModules
+from ..spade_modules import SPADEStep
 from .base_model import BaseModel
 
 
-class SPADEModel(BaseModel):
+class SPADEModel(SPADEStep, BaseModel):
     _FLAGS = [  # spade_model.py:27-39
         ('--norm_G', dict(type=str, default='spadesyncbatch3x3', help='instance normalization or batch normalization')),
         ('--num_upsampling_layers', dict(choices=('normal', 'more', 'most'), default='more')),
@@ -81,25 +81,6 @@ class SPADEModel(BaseModel):
     def netD(self):
         return self.modules_on_one_gpu.netD
 
-    # -- data (spade_model.py:132-179) ----------------------------------------------------------------------------------------
-    def set_input(self, input):
-        self.data = input
-        self.image_paths = input.get('path', [])
-        self.labels = input['label'].to(self.device)
-        self.input_semantics, self.real_B = self.preprocess_input(input)
-
-    def preprocess_input(self, data):
-        label = data['label'].to(self.device)
-        nc = self.opt.input_nc + 1 if getattr(self.opt, 'contain_dontcare_label', False) else self.opt.input_nc
-        inst = None if getattr(self.opt, 'no_instance', False) else data['instance'].to(self.device)
-        input_semantics = ops.onehot_edges(label, inst, nc)
-        return input_semantics, ops.to_nhwc(data['image'].to(self.device, dtype=torch.float32))
-
-    def get_edges(self, t):
-        n, c, h, w = t.shape
-        zero = torch.zeros((n, 1, h, w), device=self.device, dtype=torch.int32)
-        return ops.onehot_edges(zero, t.to(self.device), 0)
-
     # -- the step (spade_model.py:163-215) ------------------------------------------------------------------------------------
     def forward(self, on_one_gpu=False):
         self.fake_B = self.modules_on_one_gpu(self.input_semantics)
@@ -115,19 +96,9 @@ class SPADEModel(BaseModel):
         return macs, params
 
     def backward_G(self):
-        losses = self.modules(self.input_semantics, self.real_B, mode='G_loss')
-        for loss_name in self.loss_names:
-            if loss_name.startswith('G'):
-                setattr(self, 'loss_%s' % loss_name, losses[loss_name])
+        losses = self._losses('G_loss')
         self.fake_B = self.modules_on_one_gpu._last
         losses['loss_G'].backward()
-
-    def backward_D(self):
-        losses = self.modules(self.input_semantics, self.real_B, mode='D_loss')
-        for loss_name in self.loss_names:
-            if loss_name.startswith('D'):
-                setattr(self, 'loss_%s' % loss_name, losses[loss_name])
-        losses['loss_D'].backward()
 
     def optimize_parameters(self, steps):
         self.set_requires_grad(self.modules_on_one_gpu.netD, False)
@@ -175,23 +146,8 @@ class SPADEModel(BaseModel):
     # -- bookkeeping (spade_model.py:290-342) -----------------------------------------------------------------------------------
     def load_networks(self, verbose=True, teacher_only=False, restore_pretrain=True):
         self.modules_on_one_gpu.load_networks(verbose)
-        if self.isTrain and getattr(self.opt, 'restore_O_path', None) is not None:
-            for i, optimizer in enumerate(self.optimizers):
-                optimizer.load_state_dict(torch.load('%s-%d.pth' % (self.opt.restore_O_path, i), map_location='cpu'))
-            if self.opt.no_TTUR:
-                G_lr, D_lr = self.opt.lr, self.opt.lr
-            else:
-                G_lr, D_lr = self.opt.lr / 2, self.opt.lr * 2
-            for param_group in self.optimizer_G.param_groups:
-                param_group['lr'] = G_lr
-            for param_group in self.optimizer_D.param_groups:
-                param_group['lr'] = D_lr
-
-    def save_networks(self, epoch):
-        os.makedirs(self.save_dir, exist_ok=True)
-        self.modules_on_one_gpu.save_networks(epoch, self.save_dir)
-        for i, optimizer in enumerate(self.optimizers):
-            torch.save(optimizer.state_dict(), os.path.join(self.save_dir, '%s_optim-%d.pth' % (epoch, i)))
+        if self.isTrain:
+            self.restore_optimizers(self.modules_on_one_gpu._ttur()[2:])
 
 
 class _EvalView:

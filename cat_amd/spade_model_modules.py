@@ -8,21 +8,20 @@ DESIGN §7).
 The discriminator's loss head -- num_D * n_layers_D feature-matching L1 terms + num_D GAN terms in the G step, 2 * num_D hinge terms in the D
 step -- is ONE ops.MultiLossFn call each (two forward launches, one backward launch) instead of a LossFn reduction pair and a backward
 launch per term.  CAT_LOSS_MULTI=0 selects the per-term path (A/B switch, read once at import).  Either way the losses are LossValue objects
-(spade_modules.py): the weights travel as backward seeds, nothing is added with torch arithmetic.  The VGG terms stay per-term: they are
+(lossvalue.py): the weights travel as backward seeds, nothing is added with torch arithmetic.  The VGG terms stay per-term: they are
 interleaved with the VGG slices."""
 import copy
 import os
-from collections import OrderedDict
 
 import torch
-from torch import nn
 
 from . import _lib as L
 from . import loss as closs
 from . import networks, ops
 from .optim import FusedAdam
+from .lossvalue import LossValue
 from .prune import model_profiling
-from .spade_modules import LossValue
+from .spade_modules import SPADEModules
 
 _LOSS_MULTI = os.environ.get('CAT_LOSS_MULTI', '1') != '0'
 
@@ -31,7 +30,7 @@ def loss_multi_enabled():
     return _LOSS_MULTI
 
 
-class SPADEModelModules(nn.Module):
+class SPADEModelModules(SPADEModules):
     def __init__(self, opt):
         opt = copy.deepcopy(opt)
         if len(opt.gpu_ids) > 0:
@@ -57,35 +56,15 @@ class SPADEModelModules(nn.Module):
         else:
             self.netG.eval()
 
-    def train(self, mode=True):
-        """nn.Module.train, except that the frozen VGG stays in eval mode."""
-        super().train(mode)
-        if hasattr(self, 'criterionVGG'):
-            self.criterionVGG.eval()
-        return self
-
     def create_optimizers(self):
-        """spade_model_modules.py:52-65 (TTUR: betas (0, 0.9), lr/2 for G, lr*2 for D)."""
-        if self.opt.no_TTUR:
-            beta1, beta2 = self.opt.beta1, self.opt.beta2
-            G_lr, D_lr = self.opt.lr, self.opt.lr
-        else:
-            beta1, beta2 = 0.0, 0.9
-            G_lr, D_lr = self.opt.lr / 2, self.opt.lr * 2
+        """spade_model_modules.py:52-65."""
+        beta1, beta2, G_lr, D_lr = self._ttur()
         optimizer_G = FusedAdam(list(self.netG.parameters()), lr=G_lr, betas=(beta1, beta2))
         optimizer_D = FusedAdam(list(self.netD.parameters()), lr=D_lr, betas=(beta1, beta2))
         return optimizer_G, optimizer_D
 
-    def forward(self, input_semantics, real_B=None, mode='generate_fake'):
-        if mode == 'generate_fake':
-            return self.netG(input_semantics)
-        elif mode == 'G_loss':
-            assert real_B is not None
-            return self.compute_G_loss(input_semantics, real_B)
-        elif mode == 'D_loss':
-            assert real_B is not None
-            return self.compute_D_loss(input_semantics, real_B)
-        raise NotImplementedError('Unknown forward mode [%s]!!!' % mode)
+    def generate_fake(self, input_semantics):
+        return self.netG(input_semantics)
 
     def profile(self, input_semantics):
         """spade_model_modules.py:80-91: (macs, params) of the generator at the input's geometry."""
@@ -93,20 +72,6 @@ class SPADEModelModules(nn.Module):
         return model_profiling(self.netG, height_, width_, batch_, channel_, verbose=False)
 
     # -- losses -------------------------------------------------------------------------------------------------------------
-    def _gan_kind(self, target_is_real, for_discriminator):
-        """(kind, target) of one GANLoss term (cat_amd/loss.py GANLoss.__call__ on a single tensor)."""
-        c = self.criterionGAN
-        if c.gan_mode == 'lsgan':
-            return L.LOSS_LSGAN, c.real_label if target_is_real else c.fake_label
-        if c.gan_mode == 'vanilla':
-            return L.LOSS_BCE_LOGITS, c.real_label if target_is_real else c.fake_label
-        if c.gan_mode == 'wgangp':
-            return (L.LOSS_NEG_MEAN if target_is_real else L.LOSS_MEAN), 0.0
-        if for_discriminator:
-            return (L.LOSS_HINGE_D_REAL if target_is_real else L.LOSS_HINGE_D_FAKE), 0.0
-        assert target_is_real
-        return L.LOSS_NEG_MEAN, 0.0
-
     def _head(self, terms):
         """terms: [(kind, target, a, b)] -> their 0-d means, in order: one MultiLossFn call, or one LossFn per term (CAT_LOSS_MULTI=0)."""
         if not _LOSS_MULTI:
@@ -124,7 +89,7 @@ class SPADEModelModules(nn.Module):
         f_d, f_v = ops.fanout(fake_B, 2)
         pred_fake, pred_real = self.discriminate(input_semantics, f_d, real_B)
         num_D = len(pred_fake)
-        kind, target = self._gan_kind(True, False)
+        kind, target = self.criterionGAN.kind(True, False)
         terms = [(kind, target, p[-1], None) for p in pred_fake]
         for i in range(num_D):
             for j in range(len(pred_fake[i]) - 1):
@@ -144,38 +109,9 @@ class SPADEModelModules(nn.Module):
             fake_B = self.netG(input_semantics)
         pred_fake, pred_real = self.discriminate(input_semantics, fake_B, real_B)
         num_D = len(pred_fake)
-        kf, tf = self._gan_kind(False, True)
-        kr, tr = self._gan_kind(True, True)
+        kf, tf = self.criterionGAN.kind(False, True)
+        kr, tr = self.criterionGAN.kind(True, True)
         vals = self._head([(kf, tf, p[-1], None) for p in pred_fake] + [(kr, tr, p[-1], None) for p in pred_real])
         loss_D_fake = LossValue([(1.0 / num_D, v) for v in vals[:num_D]])
         loss_D_real = LossValue([(1.0 / num_D, v) for v in vals[num_D:]])
         return {'loss_D': loss_D_fake + loss_D_real, 'D_fake': loss_D_fake, 'D_real': loss_D_real}
-
-    def discriminate(self, input_semantics, fake_B, real_B):
-        """spade_model_modules.py:136-141: ONE discriminator pass over the 2N batch [sem|fake ; sem|real]."""
-        fake_and_real = ops.DiscInputFn.apply(input_semantics, fake_B, real_B)
-        return self.divide_pred(self.netD(fake_and_real))
-
-    def divide_pred(self, pred):
-        """spade_model_modules.py:143-155.  Intermediate features feed the next layer AND the feature-matching loss."""
-        fake, real = [], []
-        for p in pred:
-            halves = [ops.BatchHalvesFn.apply(t) for t in p]
-            fake.append([h[0] for h in halves])
-            real.append([h[1] for h in halves])
-        return fake, real
-
-    # -- checkpoints (spade_model_modules.py:157-174) -------------------------------------------------------------------------
-    def load_networks(self, verbose=True):
-        for name in self.model_names:
-            path = getattr(self.opt, 'restore_%s_path' % name, None)
-            if path is not None:
-                if verbose:
-                    print('Load network at %s' % path)
-                getattr(self, 'net' + name).load_state_dict(torch.load(path, map_location='cpu'))
-
-    def save_networks(self, epoch, save_dir):
-        for name in self.model_names:
-            net = getattr(self, 'net' + name)
-            sd = OrderedDict((k, v.detach().cpu().contiguous()) for k, v in net.state_dict().items())
-            torch.save(sd, os.path.join(save_dir, '%s_net_%s.pth' % (epoch, name)))

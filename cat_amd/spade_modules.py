@@ -14,64 +14,106 @@ import copy
 import torch
 from torch import nn
 
+from . import host
 from . import loss as closs
 from . import networks, ops
 from . import nn as cnn
+from .lossvalue import LossValue
 from .optim import FusedAdam
 
 
-class LossValue:
-    """sum_i w_i * t_i over 0-d device tensors; float() synchronises."""
+class SPADEStep:
+    """The data half and the loss bookkeeping that the GauGAN teacher step (models/spade_model.py) and the GauGAN distillation step
+    (distillers/base_spade_distiller.py) share, on top of host.StepHost (reference models/spade_model.py:132-203)."""
 
-    def __init__(self, terms):
-        self.terms = [(float(w), t) for w, t in terms]
+    def set_input(self, input):
+        self.data = input
+        self.image_paths = input.get('path', [])
+        self.labels = input['label'].to(self.device)
+        self.input_semantics, self.real_B = self.preprocess_input(input)
 
-    def __float__(self):
-        return float(sum(w * float(t) for w, t in self.terms))
+    def preprocess_input(self, data):
+        label = data['label'].to(self.device)
+        nc = self.opt.input_nc + 1 if getattr(self.opt, 'contain_dontcare_label', False) else self.opt.input_nc
+        inst = None if getattr(self.opt, 'no_instance', False) else data['instance'].to(self.device)
+        input_semantics = ops.onehot_edges(label, inst, nc)
+        return input_semantics, ops.to_nhwc(data['image'].to(self.device, dtype=torch.float32))
 
-    def item(self):
-        return float(self)
+    def get_edges(self, t):
+        n, c, h, w = t.shape
+        zero = torch.zeros((n, 1, h, w), device=self.device, dtype=torch.int32)
+        return ops.onehot_edges(zero, t.to(self.device), 0)
 
-    def detach(self):
+    def _losses(self, mode):
+        """modules(mode='G_loss' | 'D_loss'); its entries for this class's loss names of that side become the loss_<name> attributes."""
+        losses = self.modules(self.input_semantics, self.real_B, mode=mode)
+        for loss_name in self.loss_names:
+            if loss_name.startswith(mode[0]):
+                setattr(self, 'loss_%s' % loss_name, losses[loss_name])
+        return losses
+
+    def backward_D(self):
+        self._losses('D_loss')['loss_D'].backward()
+
+    def _save(self, epoch):
+        self.modules_on_one_gpu.save_networks(epoch, self.save_dir)
+        self.save_optimizers(epoch)
+
+
+class SPADEModules(nn.Module):
+    """The methods SPADEModelModules and SPADEDistillerModules share.  No __init__: the order in which a subclass registers its
+    networks fixes its state_dict key order and the layout of FusedAdam's flat buffers."""
+
+    def train(self, mode=True):
+        """nn.Module.train, except that the frozen VGG stays in eval mode."""
+        super().train(mode)
+        if hasattr(self, 'criterionVGG'):
+            self.criterionVGG.eval()
         return self
 
-    def mean(self):          # losses['loss_G'].mean() in models/spade_model.py:191 (one replica per process)
-        return self
+    def _ttur(self):
+        """(beta1, beta2, G_lr, D_lr) -- TTUR: betas (0, 0.9), lr/2 for G, lr*2 for D (spade_model_modules.py:52-65)."""
+        if self.opt.no_TTUR:
+            return self.opt.beta1, self.opt.beta2, self.opt.lr, self.opt.lr
+        return 0.0, 0.9, self.opt.lr / 2, self.opt.lr * 2
 
-    def __mul__(self, k):
-        return LossValue([(w * k, t) for w, t in self.terms])
+    def forward(self, input_semantics, real_B=None, mode='generate_fake'):
+        if mode == 'generate_fake':
+            return self.generate_fake(input_semantics)
+        elif mode == 'G_loss':
+            assert real_B is not None
+            return self.compute_G_loss(input_semantics, real_B)
+        elif mode == 'D_loss':
+            assert real_B is not None
+            return self.compute_D_loss(input_semantics, real_B)
+        raise NotImplementedError('Unknown forward mode [%s]!!!' % mode)
 
-    __rmul__ = __mul__
+    def discriminate(self, input_semantics, fake_B, real_B):
+        """spade_model_modules.py:136-141: ONE discriminator pass over the 2N batch [sem|fake ; sem|real]."""
+        fake_and_real = ops.DiscInputFn.apply(input_semantics, fake_B, real_B)
+        return self.divide_pred(self.netD(fake_and_real))
 
-    def __truediv__(self, k):
-        return self * (1.0 / k)
+    def divide_pred(self, pred):
+        """spade_model_modules.py:143-155.  Intermediate features feed the next layer AND the feature-matching loss."""
+        fake, real = [], []
+        for p in pred:
+            halves = [ops.BatchHalvesFn.apply(t) for t in p]
+            fake.append([h[0] for h in halves])
+            real.append([h[1] for h in halves])
+        return fake, real
 
-    def __add__(self, other):
-        if isinstance(other, (int, float)) and other == 0:
-            return self
-        if isinstance(other, torch.Tensor):
-            other = LossValue([(1.0, other)])
-        return LossValue(self.terms + other.terms)
+    # -- checkpoints (spade_model_modules.py:157-174) -------------------------------------------------------------------------
+    def _saved_nets(self):
+        return host.named_nets(self)
 
-    __radd__ = __add__
+    def load_networks(self, verbose=True):
+        host.restore_named(self, verbose)
 
-    _SEEDS = {}
-
-    def backward(self):
-        terms = [(w, t) for w, t in self.terms if t.requires_grad]
-        seeds = []
-        for w, t in terms:
-            key = (t.device, w)
-            s = self._SEEDS.get(key)
-            if s is None:
-                s = torch.full((), w, device=t.device, dtype=torch.float32)
-                self._SEEDS[key] = s
-            seeds.append(s)
-        torch.autograd.backward([t for _, t in terms], seeds)
-        ops.sync_side_streams()
+    def save_networks(self, epoch, save_dir):
+        host.save_nets(self._saved_nets(), epoch, save_dir)
 
 
-class SPADEDistillerModules(nn.Module):
+class SPADEDistillerModules(SPADEModules):
     def __init__(self, opt):
         assert opt.isTrain
         opt = copy.deepcopy(opt)
@@ -115,20 +157,14 @@ class SPADEDistillerModules(nn.Module):
         self.netG_teacher.eval()
 
     def train(self, mode=True):
-        """nn.Module.train, except that the frozen teacher and VGG stay in eval mode (base_spade_distiller_modules.py:89)."""
+        """... and the frozen teacher stays in eval mode too (base_spade_distiller_modules.py:89)."""
         super().train(mode)
         self.netG_teacher.eval()
-        self.criterionVGG.eval()
         return self
 
     def create_optimizers(self):
-        """base_spade_distiller_modules.py:91-107 (TTUR: betas (0, 0.9), lr/2 for G, lr*2 for D)."""
-        if self.opt.no_TTUR:
-            beta1, beta2 = self.opt.beta1, self.opt.beta2
-            G_lr, D_lr = self.opt.lr, self.opt.lr
-        else:
-            beta1, beta2 = 0.0, 0.9
-            G_lr, D_lr = self.opt.lr / 2, self.opt.lr * 2
+        """base_spade_distiller_modules.py:91-107."""
+        beta1, beta2, G_lr, D_lr = self._ttur()
         G_params = list(self.netG_student.parameters())
         for netA in self.netAs:
             G_params += list(netA.parameters())
@@ -136,19 +172,11 @@ class SPADEDistillerModules(nn.Module):
         optimizer_D = FusedAdam(list(self.netD.parameters()), lr=D_lr, betas=(beta1, beta2))
         return optimizer_G, optimizer_D
 
-    def forward(self, input_semantics, real_B=None, mode='generate_fake'):
-        if mode == 'generate_fake':
-            with torch.no_grad():
-                Tfake_B = self.netG_teacher(input_semantics)
-                Sfake_B = self.netG_student(input_semantics)
-            return Tfake_B, Sfake_B
-        elif mode == 'G_loss':
-            assert real_B is not None
-            return self.compute_G_loss(input_semantics, real_B)
-        elif mode == 'D_loss':
-            assert real_B is not None
-            return self.compute_D_loss(input_semantics, real_B)
-        raise NotImplementedError('Unknown forward mode [%s]!!!' % mode)
+    def generate_fake(self, input_semantics):
+        with torch.no_grad():
+            Tfake_B = self.netG_teacher(input_semantics)
+            Sfake_B = self.netG_student(input_semantics)
+        return Tfake_B, Sfake_B
 
     def profile(self, input_semantics):
         raise NotImplementedError('The distiller is only for training!!!')
@@ -203,33 +231,15 @@ class SPADEDistillerModules(nn.Module):
         loss_D_real = LossValue([(1.0 / num_D, self.criterionGAN(p[-1], True, for_discriminator=True)) for p in pred_real])
         return {'loss_D': loss_D_fake + loss_D_real, 'D_fake': loss_D_fake, 'D_real': loss_D_real}
 
-    def discriminate(self, input_semantics, fake_B, real_B):
-        """spade_model_modules.py:136-141: ONE discriminator pass over the 2N batch [sem|fake ; sem|real]."""
-        fake_and_real = ops.DiscInputFn.apply(input_semantics, fake_B, real_B)
-        return self.divide_pred(self.netD(fake_and_real))
-
-    def divide_pred(self, pred):
-        """spade_model_modules.py:143-155.  Intermediate features feed the next layer AND the feature-matching loss."""
-        fake, real = [], []
-        for p in pred:
-            halves = [ops.BatchHalvesFn.apply(t) for t in p]
-            fake.append([h[0] for h in halves])
-            real.append([h[1] for h in halves])
-        return fake, real
-
     # -- checkpoints (same file layout as base_spade_distiller_modules.py:177-214) ---------------------------------------------
     def load_networks(self, verbose=True, teacher_only=False, restore_pretrain=True):
         opt = self.opt
 
         def load(net, path):
-            if verbose:
-                print('Load network at %s' % path)
-            net.load_state_dict(torch.load(path, map_location='cpu'))
+            host.load_state(net, path, verbose)
 
         if getattr(opt, 'restore_pretrained_G_path', None) is not None and restore_pretrain:
             # spade_distiller_modules.py:33-44: a wider pretrained generator seeds the student (host-side, once; cat_amd/weight_transfer.py)
-            import copy
-            from . import networks
             from .weight_transfer import load_pretrained_weight
             popt = copy.deepcopy(opt)
             popt.norm_G, popt.ngf = opt.pretrained_norm_G, opt.pretrained_ngf
@@ -253,14 +263,5 @@ class SPADEDistillerModules(nn.Module):
             for i, netA in enumerate(self.netAs):
                 load(netA, '%s-%d.pth' % (opt.restore_A_path, i))
 
-    def save_networks(self, epoch, save_dir):
-        import os
-        from collections import OrderedDict
-
-        def cpu_sd(net):
-            return OrderedDict((k, v.detach().cpu().contiguous()) for k, v in net.state_dict().items())
-
-        torch.save(cpu_sd(self.netG_student), os.path.join(save_dir, '%s_net_G.pth' % epoch))
-        torch.save(cpu_sd(self.netD), os.path.join(save_dir, '%s_net_D.pth' % epoch))
-        for i, net in enumerate(self.netAs):
-            torch.save(cpu_sd(net), os.path.join(save_dir, '%s_net_A-%d.pth' % (epoch, i)))
+    def _saved_nets(self):
+        return host.distilled_nets(self)

@@ -192,6 +192,14 @@ int cat_ka_bwd(const float* X, int64_t Dx, int N, const float* gout, const void*
  *   kind 4: -mean a           (hinge G / wgangp real) kind 5: mean (a-b)^2 (MSE vs tensor)
  *   kind 6: mean BCE-with-logits(a, target) (vanilla) kind 7: mean a (wgangp fake)
  * Inputs are NHWC with (C, cs); the mean runs over M*C real elements.  out[0] = loss. */
+#define CAT_LOSS_L1 0
+#define CAT_LOSS_LSGAN 1
+#define CAT_LOSS_HINGE_D_REAL 2
+#define CAT_LOSS_HINGE_D_FAKE 3
+#define CAT_LOSS_NEG_MEAN 4
+#define CAT_LOSS_MSE 5
+#define CAT_LOSS_BCE_LOGITS 6
+#define CAT_LOSS_MEAN 7
 size_t cat_loss_ws_bytes(int64_t M);
 int cat_loss_fwd(int kind, const float* a, const float* b, float target, int64_t M, int C, int cs, float* out,
                  void* ws, cat_stream_t stream);

@@ -107,6 +107,16 @@ def test_ctypes_structs_match_the_header():
         assert fields == list(cls._fields_), cname
 
 
+def test_loss_kind_names_match_the_header():
+    """The CAT_LOSS_* numbers of include/cat_hip.h (what the kernels' switch is written in) against cat_amd/_lib.py's LOSS_* (what the host
+    passes): the same eight names with the same values, and CAT_LOSS_MULTI_MAX stays the table capacity, not a kind."""
+    text = open(os.path.join(ROOT, 'include', 'cat_hip.h')).read()
+    header = {n: int(v) for n, v in re.findall(r'^#define CAT_LOSS_(\w+) (\d+)\s*$', text, flags=re.M) if n != 'MULTI_MAX'}
+    mine = {n[len('LOSS_'):]: v for n, v in vars(_lib).items() if n.startswith('LOSS_') and n != 'LOSS_MULTI_MAX'}
+    assert header == mine and sorted(header.values()) == list(range(8))
+    assert header['L1'] == 0 and header['MSE'] == 5 and header['MEAN'] == 7      # the numbers cat_loss_fwd documents
+
+
 def test_qconv_structs_match_their_ctypes_mirrors(tmp_path):
     """sizeof / offsetof of cat_qseg_t, cat_qconv_t, cat_qplan_t as the C compiler lays them out (gcc on include/cat_hip.h) against the
     ctypes mirrors in cat_amd/_lib.py: a drifted field would only show as garbage geometry on the GPU box."""
