@@ -5,8 +5,8 @@
 
 with train-mode (Synchronized)BatchNorm2d in every position, zero ("same") padding, C_in != C_out in general and an optional addend r (the
 block's shortcut).  The per-layer path launches ~45 kernels per unit (12 convs, 9 norms x 3, add_n); most of them HBM-bound passes over
-hidden tensors of 1..13 channels on planes of up to 256 x 512 pixels.  Here a unit is the protocol of cat_amd/fused_unit.py (layout, operand
-preparation and the stages, shared with the fused inception block) without that block's closing pw_bn:
+hidden tensors of 1..13 channels on planes of up to 256 x 512 pixels.  Here a unit is the pipeline of cat_amd/fused_unit.py -- layout, operand
+preparation and the stage sequence, forward and backward, defined once there and shared with the fused inception block:
 
     stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tconv_fwd)
     finalize  scale / shift of all stage-1 norms + their running statistics                               (cat_tnorm_finalize)
@@ -14,11 +14,14 @@ preparation and the stages, shared with the fused inception block) without that 
     finalize
     stage 2   the branch sum: six second convs K-concatenated, norm + ReLU applied while staging, bias and the addend r in the epilogue
 
-5 launches, no normalised tensor is ever written.  The backward pass re-materialises the two hidden activations and runs the shared backward
-stages (branch-wise weight gradients on side streams, norm backward once per stage over the concatenation, the first-conv
-input gradients as one K-concatenated launch).  Taken when the unit runs in training mode on one rank (with several ranks the
-SynchronizedBatchNorm statistics are exchanged per layer: general path), on planes of at least `ops._TCONV_MIN_TILES` 8 x 16 tiles (the
-64 x 128 .. 256 x 512 stages at batch 4); tests/test_spade_gpu.py::test_fused_spade_units_match_general_path pins it to the general path."""
+5 launches, no normalised tensor is ever written.  What this module gives the pipeline: zero padding and batch statistics (the plan's
+defaults), the reducer of a SynchronizedBatchNorm over several ranks as its `sync` (one statistics exchange per stage and direction), the
+folded running statistics as its `folded` (eval mode, no grad: 3 launches), never a dropout ticket, and p.s1d (the second convs' input
+gradients as one launch).  What it keeps: when the path applies, the unit's plan, the stage-2 launch with the addend, the autograd
+Functions and the drivers that perform the exchanges the pipeline asks for -- `_drive` for one unit, `_drive_many` for several
+independent units in lockstep, their k-th exchanges merged into ONE collective (`prepass`: the gamma|beta nets of all SPADE layers).
+Taken on planes of at least `ops._TCONV_MIN_TILES` 8 x 16 tiles (the 64 x 128 .. 256 x 512 stages at batch 4) and, under a multi-rank
+reducer, for every unit the kernels can run; tests/test_spade_gpu.py::test_fused_spade_units_match_general_path pins it to the general path."""
 import ctypes as C
 import os
 
@@ -30,6 +33,7 @@ from . import ops
 from . import optim
 from . import tconv
 from . import fused_unit as U
+from .fused_unit import Alloc      # what a unit generator asks its driver for (tests/test_host.py names it fused_spade.Alloc)
 
 _ENABLED = os.environ.get('CAT_FUSED_SPADE', '1') != '0'      # A/B switch; 'train' / 'frozen' select one of the two forms
 _ONLY = os.environ.get('CAT_FUSED_SPADE', '1') if os.environ.get('CAT_FUSED_SPADE', '1') in ('train', 'frozen') else None
@@ -142,7 +146,6 @@ class _Plan(U.Plan):
         """The second convs' input gradients as ONE launch (cat_tstage1_dgrad: dT is staged once for the 5 x 5 and the 3 x 3 residual branch
         and the N-concatenated 1 x 1 second convs of the depthwise branches) where a kernel exists for the widths."""
         r5, r3 = [b for b in self.res if b['k'] == 5], [b for b in self.res if b['k'] == 3]
-        self.s1d = None
         if _S1_DGRAD and len(r5) == 1 and len(r3) == 1 and self.dws and L.query('cat_tstage1_dgrad_supported', r5[0]['w1'], r3[0]['w1'], self.hcd):
             self.s1d = (r5[0], r3[0])
         return self.s1d is not None
@@ -179,51 +182,6 @@ def plan_for(owner, slot, res_ops, dw_ops, cin, cout, x):
         setattr(owner, slot, p)
         PLAN_GEN += 1
     return p
-
-
-def _slices(pairs):
-    arr = (L.NSlice * len(pairs))()
-    for i, (c0, c, bn) in enumerate(pairs):
-        arr[i].c0, arr[i].c = c0, c
-        arr[i].running_mean = bn.running_mean.data_ptr()
-        arr[i].running_var = bn.running_var.data_ptr()
-        # SynchronizedBatchNorm2d.forward bypasses _BatchNorm.forward: num_batches_tracked is never advanced (batchnorm.py:68-101)
-        arr[i].num_batches = None if isinstance(bn, cnn.SynchronizedBatchNorm2d) else bn.num_batches_tracked.data_ptr()
-    return arr
-
-
-def _finalize_g(p, part, scs, n, h, w, gamma, beta, pairs):
-    """(scale | shift), (mean | rstd) of every norm of a stage.  With a SynchronizedBatchNorm reducer installed (N > 1 ranks) the stage's
-    statistics are exchanged ONCE: this rank's tile table -> [sum x | sum x^2] of the whole concatenation -> one all-reduce -> the
-    reference's multi-replica formula (batchnorm.py:103-140: clamp(var, eps), unbiased running_var); the second tensor then holds
-    (a | b) = (inv_std | -mean * inv_std) for the split-phase backward.
-    A GENERATOR: it yields the tensor to be sum-reduced over the ranks and continues once that has happened -- `_drive` performs the exchange
-    on the spot (one unit), `_drive_many` runs several independent units in lockstep and merges their k-th exchanges into ONE collective
-    (the gamma|beta nets of all SPADE layers of a generator: `prepass`)."""
-    ss = torch.empty((2, 1, scs), device=part.device, dtype=torch.float32)
-    mr = torch.empty((2, 1, scs), device=part.device, dtype=torch.float32)
-    sync = ops.bn_sync()
-    if sync is None:
-        L.call('cat_tnorm_finalize', ops._p(part), scs, 1, n, h, w, ops._p(gamma), ops._p(beta), len(pairs), _slices(pairs), p.eps, p.momentum,
-               ops._p(ss[0]), ops._p(ss[1]), ops._p(mr[0]), ops._p(mr[1]), scs, ops._stream())
-        return ss, mr
-    sums = yield Alloc(2 * scs, part.device)      # a slice of the round's arena under _drive_many: the merged exchange needs no pack / unpack
-    L.call('cat_tnorm_sums', ops._p(part), scs, n, h, w, 8, 16, 1, ops._p(sums), ops._stream())
-    yield sums
-    count = float(n * h * w) * sync.world_size
-    L.call('cat_tnorm_finalize_sums', ops._p(sums), count, scs, ops._p(gamma), ops._p(beta), len(pairs), _slices(pairs), p.eps, p.momentum, 1,
-           ops._p(ss[0]), ops._p(ss[1]), ops._p(mr[0]), ops._p(mr[1]), ops._stream())
-    return ss, mr
-
-
-class Alloc:
-    """A unit generator's request for the buffer of its next statistics exchange (n floats, n % 4 == 0).  `_drive_many` hands every unit of
-    a lockstep round a slice of ONE arena, in unit order, so that the round's exchanges are one contiguous message: the collective runs on
-    the arena itself, without the torch.cat / copy_ kernels a pack + unpack would launch (round-5 verdict, robustness #15)."""
-    __slots__ = ('n', 'device')
-
-    def __init__(self, n, device):
-        self.n, self.device = int(n), device
 
 
 def _drive(gen):
@@ -280,34 +238,28 @@ def _drive_many(gens):
     return results
 
 
-def forward(p, x, addend, save=None):
-    """The unit's forward.  `addend`: NHWC activation [n, Cout, h, w] added in the epilogue (the block's shortcut) or None."""
-    return _drive(forward_g(p, x, addend, save))
+def _branch_sum(p, x, segs, addend):
+    """Stage 2: the K-concatenated branch sum over `segs`, bias and `addend` (NHWC activation [n, Cout, h, w], the block's shortcut, or None)
+    in the epilogue."""
+    n, _, h, w = x.shape
+    y = ops.empty_act(n, p.Cout, h, w, x.device)
+    tconv.run(segs, p.pack2, p.bias2 if p.has_bias2 else None, y, p.Cout, n, h, w, h, w, res=addend)
+    return y
 
 
-def forward_g(p, x, addend, save=None):
-    """forward as a generator over its statistics exchanges (see _finalize_g)."""
+def _train_g(p, x, addend, save=None):
+    """The train-mode unit as a generator over its statistics exchanges (U.finalize_g under the installed reducer, if any)."""
     STATS['train_fwd'] += 1
     p.prepare()
-    n, c, h, w = x.shape
-    dev = x.device
-    tiles = n * ((h + 7) // 8) * ((w + 15) // 16)
-    z1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
-    part1 = torch.empty((tiles, 2, p.hc1), device=dev, dtype=torch.float32)
-    U.stage1(p, x, z1, part1)
-    st1 = yield from _finalize_g(p, part1, p.hc1, n, h, w, p.gamma1, p.beta1, [(b['o1'], b['m'], b['bn1']) for b in p.branches])
-    zd = std = None
-    if p.dws:
-        zd = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
-        partd = torch.empty((tiles, 2, p.hcd), device=dev, dtype=torch.float32)
-        U.dwm_fwd(p, z1, st1[0][0], st1[0][1], zd, partd)
-        std = yield from _finalize_g(p, partd, p.hcd, n, h, w, p.gammad, p.betad, [(b['od'], b['m'], b['bn2']) for b in p.dws])
-    segs = U.stage2_segs(p, z1, st1[0], zd, std[0] if std is not None else None)
-    y = ops.empty_act(n, p.Cout, h, w, dev)
-    tconv.run(segs, p.pack2, p.bias2 if p.has_bias2 else None, y, p.Cout, n, h, w, h, w, res=addend)
+    z1, st1, zd, std, segs = yield from U.forward_g(p, x, sync=ops.bn_sync())
     if save is not None:
         save.update(z1=z1, zd=zd, st1=st1, std=std)
-    return y
+    return _branch_sum(p, x, segs, addend)
+
+
+def forward(p, x, addend, save=None):
+    """The unit's forward.  `addend`: NHWC activation [n, Cout, h, w] added in the epilogue (the block's shortcut) or None."""
+    return _drive(_train_g(p, x, addend, save))
 
 
 def _eval_affine(p):
@@ -342,45 +294,8 @@ def forward_eval(p, x, addend):
     """The unit with eval-mode norms (no grad): stage 1 -> depthwise stage -> branch sum, the norms folded into the consumers' staging."""
     STATS['frozen_fwd'] += 1
     p.prepare()
-    ss1, ssd = _eval_affine(p)
-    n, c, h, w = x.shape
-    dev = x.device
-    z1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
-    U.stage1(p, x, z1, None)
-    zd = None
-    if p.dws:
-        zd = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
-        U.dwm_fwd(p, z1, ss1[0], ss1[1], zd, None)
-    segs = U.stage2_segs(p, z1, ss1, zd, ssd)
-    y = ops.empty_act(n, p.Cout, h, w, dev)
-    tconv.run(segs, p.pack2, p.bias2 if p.has_bias2 else None, y, p.Cout, n, h, w, h, w, res=addend)
-    return y
-
-
-def _norm_bwd_g(p, n, hw, c, cs, x, dy, gamma, beta, mr, dgamma, dbeta, synced=False):
-    dx = torch.empty((n, hw, cs), device=x.device, dtype=torch.float32)
-    if synced:
-        # SynchronizedBatchNorm backward over ranks: local [sum g | sum g * xhat] of the whole stage -> ONE all-reduce -> apply; the parameter
-        # gradients stay local sums (the gradient bucket all-reduce averages them), as in ops.SyncBNFn
-        sync = ops.bn_sync()
-        if sync is None:
-            raise RuntimeError('fused SPADE unit backward: the forward ran under a SynchronizedBatchNorm reducer that is gone')
-        m = n * hw
-        sums = yield Alloc(2 * cs, x.device)
-        ws = ops.workspace(L.query('cat_bn_ws_bytes', m, cs), x.device)
-        st = ops._stream()
-        L.call('cat_bn_stats_bwd', ops._p(x), ops._p(dy), ops._p(gamma), ops._p(beta), ops._p(mr[0]), ops._p(mr[1]), m, c, cs, p.act, p.slope,
-               ops._p(sums), ops._p(ws), st)
-        local = sums.clone()
-        yield sums      # sum-reduced over the ranks by the driver (_drive / _drive_many)
-        L.call('cat_bn_apply_bwd', ops._p(x), ops._p(dy), ops._p(gamma), ops._p(beta), ops._p(mr[0]), ops._p(mr[1]), ops._p(sums),
-               float(m * sync.world_size), ops._p(local), ops._p(dx), ops._p(dgamma), ops._p(dbeta), 0, m, c, cs, p.act, p.slope, st)
-        return dx
-    g = L.NormGeom(n, hw, c, cs, L.NORM_BATCH, p.eps, p.momentum, p.act, p.slope)
-    ws = ops.workspace(L.query('cat_norm_ws_bytes', C.byref(g)), x.device)
-    L.call('cat_norm_bwd', C.byref(g), ops._p(x), ops._p(dy), ops._p(gamma), ops._p(beta), ops._p(mr[0]), ops._p(mr[1]), ops._p(dx), ops._p(dgamma),
-           ops._p(dbeta), 0, ops._p(ws), ops._stream())
-    return dx
+    folded = _eval_affine(p)      # (held here until the branch sum that reads its rows is enqueued)
+    return _branch_sum(p, x, _drive(U.forward_g(p, x, folded=folded))[4], addend)
 
 
 class _UnitFn(torch.autograd.Function):
@@ -390,7 +305,7 @@ class _UnitFn(torch.autograd.Function):
         if addend is not None:
             addend = ops.conform(addend)
         save = {}
-        y = _drive(forward_g(plan, x, addend, save))
+        y = _drive(_train_g(plan, x, addend, save))
         ctx.plan = plan
         ctx.synced = ops.bn_sync() is not None      # statistics over all ranks: (a | b) saved instead of (mean | rstd)
         ctx.has_dw = save['zd'] is not None
@@ -403,10 +318,10 @@ class _UnitFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        return _drive(_backward_g(ctx, dy))
+        return _drive(_grad_g(ctx, dy))
 
 
-def _backward_g(ctx, dy):
+def _grad_g(ctx, dy):
     """A unit's backward as a generator over its statistics exchanges.  `ctx`: anything with plan / synced / has_dw / has_add / saved_tensors /
     needs_input_grad (the autograd context of _UnitFn, or the per-unit record of _PrepassFn)."""
     p = ctx.plan
@@ -417,100 +332,16 @@ def _backward_g(ctx, dy):
     dt = ops.conform(dy)            # no closing norm: the gradient of the branch sum IS dy (and so is the addend's)
     if ops.act_cs(dt) != p.cso:
         raise RuntimeError('fused SPADE unit backward: gradient pixel stride differs from the activation')
+    sync = ops.bn_sync() if ctx.synced else None
+    if ctx.synced and sync is None:
+        raise RuntimeError('fused SPADE unit backward: the forward ran under a SynchronizedBatchNorm reducer that is gone')
     p.prepare(backward=True)
-    n, c, h, w = x.shape
-    dev, hw, m_pix = x.device, h * w, n * h * w
-    grads = {}
-    side = ops.SideJobs(dev)
-
-    def put_side(param, kernel):
-        def job():
-            grads[id(param)] = ops._write_param_grad(param, lambda dst_, acc: kernel(dst_, acc, ops._stream()))
-        side.run(job)
-
-    # ---- re-materialise the hidden activations (inputs of the second convs / of the depthwise convs)
-    a1 = U.rematerialise(p, z1, ss1)
-    da1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
-    ad = dad = None
-    if ctx.has_dw:
-        ad = U.rematerialise(p, zd, ssd)
-        dad = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
-    # ---- second convs: weight gradients from (hidden activation slice, dT); input gradients into slices of dA1 / dAd
-    side.fork()
-    for b in p.branches:
-        res = b['kind'] == 'res'
-        k2, m, w1 = b['k2'], b['m'], b['w1']
-        pad2 = (k2 - 1) // 2
-        src, scs_, o = (a1, p.hc1, b['o1']) if res else (ad, p.hcd, b['od'])
-        dst, dcs = (da1, p.hc1) if res else (dad, p.hcd)
-        xptr = C.c_void_p(src.data_ptr() + 4 * o)
-
-        def kw(dst_, acc, sst, xptr=xptr, m=m, scs_=scs_, k2=k2, pad2=pad2):
-            gw = ops._conv_geom(n, h, w, m, scs_, h, w, p.Cout, p.cso, k2, k2, 1, pad2, L.PAD_ZERO, wcs=ops._grad_wcs(dst_))
-            U.wgrad(gw, xptr, ops._p(dt), dst_, acc, sst)
-        if res or not p.merge2:
-            put_side(b['conv2'].weight, kw)
-        if p.s1d is not None and (b is p.s1d[0] or b is p.s1d[1] or not res):
-            continue            # input gradient: the merged launch below
-        seg = tconv.Segment(None, k2, k2 - 1 - pad2, False, b['d2off'], c4=p.cso, cin=p.Cout, xcs=p.cso, ptr=dt.data_ptr())
-        tconv.run([seg], p.dpack2, None, None, m, n, h, w, h, w, ycs=dcs, ycw=w1, yptr=dst.data_ptr() + 4 * o)
-    if p.s1d is not None:
-        r5, r3 = p.s1d
-        gs = L.Stage1Geom()
-        gs.N, gs.H, gs.W, gs.xcs, gs.cin, gs.reflect, gs.ycs, gs.scs = n, h, w, p.cso, p.Cout, 0, 0, 0
-        packs, dxs, dxcs = (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_int * 3)(p.hc1, p.hc1, p.hcd)
-        for slot, (col0, width, nvalid, pk, dst) in enumerate(((r5['o1'], r5['w1'], r5['m'], p.dpack2.data_ptr() + 4 * r5['d2off'], da1),
-                                                               (r3['o1'], r3['w1'], r3['m'], p.dpack2.data_ptr() + 4 * r3['d2off'], da1),
-                                                               (0, p.hcd, sum(b['m'] for b in p.dws), p.dpack2_dw.data_ptr(), dad))):
-            gs.col0[slot], gs.width[slot], gs.nvalid[slot] = col0, width, nvalid
-            packs[slot], dxs[slot] = pk, dst.data_ptr()
-        L.call('cat_tstage1_dgrad', C.byref(gs), ops._p(dt), packs, dxs, dxcs, ops._stream())
-    if p.merge2:
-        gw2 = ops._conv_geom(n, h, w, p.hcd, p.hcd, h, w, p.Cout, p.cso, 1, 1, 1, 0, L.PAD_ZERO, wcs=p.hcd)
-        side.run(lambda: U.wgrad(gw2, ops._p(ad), ops._p(dt), p.gv['w2'], 0, ops._stream()))
-    if p.has_bias2:
-        U.channel_sum(dt, m_pix, p.Cout, p.cso, p.gv['c2'])
-    # ---- depthwise stage
-    if ctx.has_dw:
-        dzd = yield from _norm_bwd_g(p, n, hw, p.hcd, p.hcd, zd, dad, p.gammad, p.betad, mrd, p.gv['gd'], p.gv['bd'], ctx.synced)
-        if p.has_biasd:
-            U.channel_sum(dzd, m_pix, p.hcd, p.hcd, p.gv['cd'])
-        U.dw_bwd(p, a1, da1, dzd, grads)
-    # ---- stage-1 norms (all branches at once)
-    dz1 = yield from _norm_bwd_g(p, n, hw, p.hc1, p.hc1, z1, da1, p.gamma1, p.beta1, mr1, p.gv['g1'], p.gv['b1'], ctx.synced)
-    if p.has_bias1:
-        U.channel_sum(dz1, m_pix, p.hc1, p.hc1, p.gv['c1'])
-    # ---- first convs: weight gradients from (x, dZ1 slice)
-    side.refork()
-    if p.merge1 is not None:
-        g1 = p.merge1
-        gw1 = ops._conv_geom(n, h, w, c, ops.act_cs(x), h, w, g1['width'], p.hc1, 1, 1, 1, 0, L.PAD_ZERO, wcs=p.csi)
-        side.run(lambda: U.wgrad(gw1, ops._p(x), C.c_void_p(dz1.data_ptr() + 4 * g1['off']), p.gv['w1'], 0, ops._stream()))
-    for b in p.branches:
-        if p.merge1 is not None and b['k'] == 1:
-            continue
-        k, m = b['k'], b['m']
-        pad1 = (k - 1) // 2
-        dyp = C.c_void_p(dz1.data_ptr() + 4 * b['o1'])
-
-        def kw1(dst_, acc, sst, dyp=dyp, m=m, k=k, pad1=pad1):
-            gw = ops._conv_geom(n, h, w, c, ops.act_cs(x), h, w, m, p.hc1, k, k, 1, pad1, L.PAD_ZERO, wcs=ops._grad_wcs(dst_))
-            U.wgrad(gw, ops._p(x), dyp, dst_, acc, sst)
-        put_side(b['conv1'].weight, kw1)
-    # ---- first convs: the input gradients as ONE K-concatenated launch
-    dx = None
-    if ctx.needs_input_grad[0]:
-        segs = U.dgrad1_segs(p, dz1)
-        dx = ops.empty_act(n, c, h, w, dev)
-        tconv.run(segs, p.dpack1, None, dx, c, n, h, w, h, w)
-    side.join()
-    # ---- scatter the concatenated parameter gradients
-    U.scatter_param_grads(p, grads)
+    dx, grads = yield from U.backward_g(p, dt, x, z1, ss1, mr1, zd, ssd, mrd, need_dx=ctx.needs_input_grad[0], sync=sync)
     return (dx, dt if ctx.has_add else None, None) + tuple(grads.get(id(q)) for q in p.params)
 
 
 class _Rec:
-    """Per-unit stand-in for an autograd context inside _PrepassFn.backward (what _backward_g reads)."""
+    """Per-unit stand-in for an autograd context inside _PrepassFn.backward (what _grad_g reads)."""
     __slots__ = ('plan', 'synced', 'has_dw', 'has_add', 'saved_tensors', 'needs_input_grad')
 
 
@@ -525,7 +356,7 @@ class _PrepassFn(torch.autograd.Function):
         n = len(plans)
         xs = [ops.conform(t) for t in args[:n]]
         saves = [dict() for _ in plans]
-        ys = _drive_many([forward_g(p, x, None, sv) for p, x, sv in zip(plans, xs, saves)])
+        ys = _drive_many([_train_g(p, x, None, sv) for p, x, sv in zip(plans, xs, saves)])
         ctx.plans, ctx.nparams = plans, nparams
         ctx.synced = ops.bn_sync() is not None
         ctx.layout, tensors = [], []
@@ -552,7 +383,7 @@ class _PrepassFn(torch.autograd.Function):
         # an output nobody used arrives as None: its unit still has to step through the lockstep exchanges (every rank does the same)
         dys = [dy if dy is not None else torch.zeros(shape[:4], device=saved[0].device, dtype=torch.float32).permute(0, 3, 1, 2)[:, :shape[4]]
                for dy, shape in zip(dys, ctx.out_nhwc)]
-        outs = _drive_many([_backward_g(r, dy) for r, dy in zip(recs, dys)])
+        outs = _drive_many([_grad_g(r, dy) for r, dy in zip(recs, dys)])
         grads = []
         for out in outs:
             grads += list(out[3:])
@@ -580,7 +411,7 @@ def prepass(units):
     plans = tuple(plan_for(u[0], '_cat_fused_gb', u[1], u[2], u[3], u[4], x) for u, x in zip(units, xs))
     STATS['prepass'] = STATS.get('prepass', 0) + 1
     if not torch.is_grad_enabled():
-        return _drive_many([forward_g(p, x, None, None) for p, x in zip(plans, xs)])
+        return _drive_many([_train_g(p, x, None, None) for p, x in zip(plans, xs)])
     params = [q for p in plans for q in p.params]
     return list(_PrepassFn.apply(plans, tuple(len(p.params) for p in plans), *xs, *params))
 

@@ -1,18 +1,34 @@
-"""What the fused inception block (cat_amd/fused_block.py) and the fused six-branch SPADE unit (cat_amd/fused_spade.py) share: one protocol
+"""The fused inception block (cat_amd/fused_block.py) and the fused six-branch SPADE unit (cat_amd/fused_spade.py) are ONE pipeline
 
     stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tconv_fwd)
+    finalize  scale / shift of all stage-1 norms + their running statistics                               (cat_tnorm_finalize)
     dw        all depthwise convs as one launch, norm + activation of stage 1 applied while staging      (cat_dwm_fwd)
+    finalize
     stage 2   the branch sum: the second convs K-concatenated, norm + activation applied while staging   (cat_tconv_fwd)
 
-over one static layout.  `Plan` is that layout -- channel slices, kernel-size groups, persistent operand buffers, the table-driven operand
-preparation (cat_prep_run) and the concatenated parameter-gradient vectors with their scatter targets; the functions below it are the
-stages, forward and backward, each defined once.  The two callers keep what is theirs: how the norms are finalised (the block's closing
-pw_bn, InstanceNorm and reflect padding; the unit's statistics exchanges over ranks), dropout, and the autograd Functions."""
+over one static layout, and both are defined here, once.  `Plan` is the layout -- channel slices, kernel-size groups, persistent operand
+buffers, the table-driven operand preparation (cat_prep_run) and the concatenated parameter-gradient vectors with their scatter targets.
+`forward_g` is the stage sequence up to the stage-2 segment list, `backward_g` the ten steps of the backward pass from the gradient of
+the branch sum to the scattered parameter gradients; the stage functions they call follow the plan.  Five things distinguish the callers,
+each a plan property or an argument, never "which caller":
+
+    p.reflect         reflect padding (block) instead of 'same' zero padding
+    p.instance        per-sample statistics (InstanceNorm) instead of batch statistics; p.affine: the norms have gamma / beta
+    statistics        collected and finalized (train mode), or `folded`: the eval form on cached scale / shift, no statistics, no finalize
+    sync              the finalize (and norm backward) to use: local, or with one statistics exchange over ranks per stage (the pipeline is
+                      a generator over those exchanges; whoever drives it performs them)
+    drop              an optional dropout ticket: the stage-2 operands are then materialised with their masks
+
+plus, in the backward pass, p.s1d (the second convs' input gradients as one cat_tstage1_dgrad launch), p.wgrad_batch (weight-gradient
+partials reduced by one launch when there are no branch streams) and `skip_grad` (a skip connection's share of the input gradient).  The
+callers keep their stage-2 launch and tail (the block's closing pw_bn and residual; the unit's epilogue addend), their plan subclass and
+the autograd Functions."""
 import ctypes as C
 
 import torch
 
 from . import _lib as L
+from . import nn as cnn
 from . import ops
 from . import optim
 from . import tconv
@@ -36,9 +52,16 @@ class Plan:
     res / dws: branch dicts (kind, k, m, conv1, bn1, conv2; dw branches also kd, dconv, bn2) -- they receive their slice offsets here.
     params: the unit's parameters, ordered and de-duplicated (table sources and epoch key).  Subclasses set `what` (error messages) and
     `GAMMA0` (what a norm without gamma reads from the concatenated vectors) and say in `_merges_dw_dgrad` whether the depthwise
-    branches' 1 x 1 second convs get an N-concatenated input-gradient filter stream (`dpack2_dw`)."""
+    branches' 1 x 1 second convs get an N-concatenated input-gradient filter stream (`dpack2_dw`).  What the pipeline reads beyond the
+    layout, with the defaults a subclass overrides: `reflect` / `instance` / `affine` (padding, per-sample statistics, norms with
+    gamma / beta), `s1d` (the two residual branches whose second-conv input gradients join the depthwise ones in ONE cat_tstage1_dgrad
+    launch, or None) and `wgrad_batch` (on one stream the weight-gradient partial sums are reduced by one launch, ops.WgradBatch)."""
     what = 'fused unit'
     GAMMA0 = 0.0
+    reflect = instance = False
+    affine = True
+    s1d = None
+    wgrad_batch = False
 
     def __init__(self, res, dws, cin, cout, dev, params):
         self.dev = dev
@@ -347,9 +370,131 @@ def stage2_segs(p, z1, ss1, zd, ssd, reflect=False, per_sample=False, a1=None, a
             src, ss, o = (z1, ss1, b['o1']) if res else (zd, ssd, b['od'])
             aff = dict(scale=ss[0].data_ptr() + 4 * o, shift=ss[1].data_ptr() + 4 * o, act=p.act, slope=p.slope,
                        sstride=src.shape[-1] if per_sample else 0)
-        segs.append(tconv.Segment(None, k, (k - 1) // 2, reflect and k > 1, b['p2off'], c4=b['w1'], cin=b['m'], xcs=src.shape[-1],
+        # (the segment keeps `src` referenced: the buffer must outlive this function's caller until the launch that reads it is enqueued)
+        segs.append(tconv.Segment(src, k, (k - 1) // 2, reflect and k > 1, b['p2off'], c4=b['w1'], cin=b['m'], xcs=src.shape[-1],
                                   ptr=src.data_ptr() + 4 * o, **aff))
     return segs
+
+
+class Alloc:
+    """A pipeline generator's request for the buffer of its next statistics exchange (n floats, n % 4 == 0).  A driver that runs several
+    units in lockstep hands every unit of a round a slice of ONE arena, in unit order, so that the round's exchanges are one contiguous
+    message: the collective runs on the arena itself, without the torch.cat / copy_ kernels a pack + unpack would launch."""
+    __slots__ = ('n', 'device')
+
+    def __init__(self, n, device):
+        self.n, self.device = int(n), device
+
+
+def slices(pairs):
+    """(c0, c, norm module) per norm of a stage -> the finalize kernels' slice table.  Running-statistic pointers only for a BatchNorm2d in
+    training mode with track_running_stats (never InstanceNorm2d); num_batches None for SynchronizedBatchNorm2d, whose forward bypasses
+    _BatchNorm.forward and never advances num_batches_tracked (sync_batchnorm/batchnorm.py:68-101).  fused_spade.applicable admits a
+    train-mode unit only if every norm is a BatchNorm2d with nm.training and nm.track_running_stats, so for those units the condition
+    always holds and the pointers are the unconditional ones that path used to pass."""
+    arr = (L.NSlice * len(pairs))()
+    for i, (c0, c, bn) in enumerate(pairs):
+        arr[i].c0, arr[i].c = c0, c
+        track = isinstance(bn, cnn.BatchNorm2d) and bn.training and bn.track_running_stats
+        arr[i].running_mean = bn.running_mean.data_ptr() if track else None
+        arr[i].running_var = bn.running_var.data_ptr() if track else None
+        arr[i].num_batches = bn.num_batches_tracked.data_ptr() if track and not isinstance(bn, cnn.SynchronizedBatchNorm2d) else None
+    return arr
+
+
+def finalize_g(p, part, scs, n, h, w, gamma, beta, pairs, *, sync, mstride=None):
+    """-> (ss, mr): ss[0] / ss[1] = scale / shift [G][scs]; mr[0] / mr[1] = mean / rstd [G][mstride] (kept for the backward pass) of every
+    norm of a stage, G = n for per-sample statistics.  `sync`: None, or the reducer of a SynchronizedBatchNorm over N > 1 ranks -- the
+    caller's decision, never read here (an inception block under a data-parallel reducer keeps per-replica statistics).  With it the stage's
+    statistics are exchanged ONCE: this rank's tile table -> [sum x | sum x^2] of the whole concatenation -> one all-reduce -> the
+    reference's multi-replica formula (batchnorm.py:103-140: clamp(var, eps), unbiased running_var); mr then holds
+    (a | b) = (inv_std | -mean * inv_std) for the split-phase backward.
+    A GENERATOR: it yields an `Alloc` for the exchange buffer, then the buffer to be sum-reduced over the ranks, and continues once that
+    has happened; without `sync` it yields nothing."""
+    G = n if p.instance else 1
+    mstride = scs if mstride is None else mstride
+    ss = torch.empty((2, G, scs), device=part.device, dtype=torch.float32)
+    mr = torch.empty((2, G, mstride), device=part.device, dtype=torch.float32)
+    gp, bp = (ops._p(gamma), ops._p(beta)) if p.affine else (None, None)
+    if sync is None:
+        L.call('cat_tnorm_finalize', ops._p(part), scs, G, n, h, w, gp, bp, len(pairs), slices(pairs), p.eps, p.momentum, ops._p(ss[0]), ops._p(ss[1]),
+               ops._p(mr[0]), ops._p(mr[1]), mstride, ops._stream())
+        return ss, mr
+    sums = yield Alloc(2 * scs, part.device)      # a slice of the round's arena under a lockstep driver: the merged exchange needs no pack / unpack
+    L.call('cat_tnorm_sums', ops._p(part), scs, n, h, w, 8, 16, 1, ops._p(sums), ops._stream())
+    yield sums
+    count = float(n * h * w) * sync.world_size
+    L.call('cat_tnorm_finalize_sums', ops._p(sums), count, scs, gp, bp, len(pairs), slices(pairs), p.eps, p.momentum, 1, ops._p(ss[0]), ops._p(ss[1]),
+           ops._p(mr[0]), ops._p(mr[1]), ops._stream())
+    return ss, mr
+
+
+def drop_segs(p, djs, kind):
+    key = ('o1', 'res') if kind == 'res' else ('od', 'dw')
+    return [(b[key[0]], b['m'], b['j']) for b in p.branches if b['kind'] == key[1] and b['j'] in djs]
+
+
+def materialise(p, z1, ss1, zd, ssd, drop, dw_slices):
+    """A1 = act(norm(Z1)) with the res slices dropped (dw slices: written undropped iff dw_slices -- the backward pass's depthwise input
+    gradient needs them, stage 2 does not) and Ad = act(norm(Zd)) dropped; one cat_dropout_apply launch each.  drop = (rate, {j of the
+    branches whose Dropout is active}, ticket); every branch of the plan carries its Dropout index j."""
+    pdrop, djs, ticket = drop
+    n, h, w, _ = z1.shape
+    dev, npix = z1.device, n * h * w
+    sstride_of = lambda scs: scs if p.instance else 0
+    a1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
+    rest = dw_slices or any(b['j'] not in djs for b in p.res)      # (res slices whose Dropout is off are written too)
+    g = ops.dropout_geom(npix, p.hc1, p.hc1, p.hc1, pdrop, drop_segs(p, djs, 'res'), mode=L.DROP_NORM, rest=int(rest), hw=h * w,
+                         sstride=sstride_of(p.hc1), act=p.act, slope=p.slope)
+    if p.res or dw_slices:
+        ops.dropout_apply(g, z1, a1, ticket, ss1[0], ss1[1])
+    ad = None
+    if p.dws:
+        ad = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
+        g = ops.dropout_geom(npix, p.hcd, p.hcd, p.hcd, pdrop, drop_segs(p, djs, 'dw'), mode=L.DROP_NORM, rest=1, hw=h * w, sstride=sstride_of(p.hcd),
+                             act=p.act, slope=p.slope)
+        ops.dropout_apply(g, zd, ad, ticket, ssd[0], ssd[1])
+    return a1, ad
+
+
+def forward_g(p, x, *, sync=None, folded=None, drop=None):
+    """The forward pipeline up to stage 2: stage 1 -> finalize -> depthwise stage -> finalize -> (dropout) -> the stage-2 segment list.
+    -> (z1, st1, zd, std, segs) with st1 / std = (ss, mr) as finalize_g returns them (zd = std = None without depthwise branches); the
+    caller launches stage 2 on `segs` with its own epilogue; the segments keep the buffers they read alive (with dropout: A1 / Ad, which
+    are not returned), their scale / shift rows belong to st1 / std, which the caller holds until stage 2 is enqueued.  A generator over
+    the statistics exchanges of finalize_g(sync=sync).
+    folded = (ss1, ssd): the eval form -- scale / shift [2][hc] given (folded from the running statistics), so no statistics are
+    collected and nothing is finalized (st1 / std = (ss, None)).
+    drop = (rate, {j}, ticket): the stage-2 operands are materialised (normalise + activation + mask) -- res slices of act(norm(Z1)) into
+    A1, all of act(norm(Zd)) into Ad -- and stage 2 stages them as they are."""
+    n, c, h, w = x.shape
+    dev = x.device
+    tiles = n * ((h + 7) // 8) * ((w + 15) // 16)
+    part_of = lambda hc: torch.empty((tiles, 2, hc), device=dev, dtype=torch.float32) if folded is None else None
+    # ---- stage 1: first convs -> Z1 (pre-norm, concatenated) + tile statistics
+    z1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
+    part1 = part_of(p.hc1)
+    stage1(p, x, z1, part1, p.reflect)
+    if folded is None:
+        st1 = yield from finalize_g(p, part1, p.hc1, n, h, w, p.gamma1, p.beta1, [(b['o1'], b['m'], b['bn1']) for b in p.branches], sync=sync)
+    else:
+        st1 = (folded[0], None)
+    # ---- depthwise stage
+    zd = std = None
+    if p.dws:
+        zd = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
+        partd = part_of(p.hcd)
+        dwm_fwd(p, z1, st1[0][0], st1[0][1], zd, partd, p.reflect, p.instance)
+        if folded is None:
+            std = yield from finalize_g(p, partd, p.hcd, n, h, w, p.gammad, p.betad, [(b['od'], b['m'], b['bn2']) for b in p.dws], sync=sync)
+        else:
+            std = (folded[1], None)
+    a1 = ad = None
+    if drop is not None:
+        a1, ad = materialise(p, z1, st1[0], zd, std[0] if std is not None else None, drop, dw_slices=False)
+    # ---- stage 2: the branch sum, K-concatenated, normalise + activation applied while staging
+    segs = stage2_segs(p, z1, st1[0], zd, std[0] if std is not None else None, p.reflect, p.instance, a1, ad)
+    return z1, st1, zd, std, segs
 
 
 # ---------------------------------------------------------------------------------------------------------------- backward stages
@@ -361,6 +506,31 @@ def rematerialise(p, z, ss, per_sample=False):
     L.call('cat_affine_res_fwd', ops._p(z), cs, ops._p(ss[0]), ops._p(ss[1]), cs if per_sample else 0, None, 0, ops._p(a), cs, G, (n // G) * h * w, cs,
            p.act, p.slope, ops._stream())
     return a
+
+
+def norm_bwd_g(p, n, hw, c, cs, x, dy, gamma, beta, mr, act, slope, dgamma, dbeta, accumulate=0, sync=None):
+    """Backward of (a concatenation of) train-mode norms + activation: -> dx, and d gamma / d beta into the given buffers.  `sync` None:
+    one cat_norm_bwd.  `sync` a reducer (the forward saved (a | b) in mr): SynchronizedBatchNorm backward over ranks -- local
+    [sum g | sum g * xhat] of the whole stage -> ONE all-reduce, requested from the driver like finalize_g's -> apply; the parameter
+    gradients stay local sums (the gradient bucket all-reduce averages them), as in ops.SyncBNFn."""
+    dx = torch.empty((n, hw, cs), device=x.device, dtype=torch.float32)
+    if sync is not None:
+        m = n * hw
+        sums = yield Alloc(2 * cs, x.device)
+        ws = ops.workspace(L.query('cat_bn_ws_bytes', m, cs), x.device)
+        st = ops._stream()
+        L.call('cat_bn_stats_bwd', ops._p(x), ops._p(dy), ops._p(gamma), ops._p(beta), ops._p(mr[0]), ops._p(mr[1]), m, c, cs, act, slope, ops._p(sums),
+               ops._p(ws), st)
+        local = sums.clone()
+        yield sums
+        L.call('cat_bn_apply_bwd', ops._p(x), ops._p(dy), ops._p(gamma), ops._p(beta), ops._p(mr[0]), ops._p(mr[1]), ops._p(sums),
+               float(m * sync.world_size), ops._p(local), ops._p(dx), ops._p(dgamma), ops._p(dbeta), accumulate, m, c, cs, act, slope, st)
+        return dx
+    g = L.NormGeom(n, hw, c, cs, L.NORM_INSTANCE if p.instance else L.NORM_BATCH, p.eps, p.momentum, act, slope)
+    ws = ops.workspace(L.query('cat_norm_ws_bytes', C.byref(g)), x.device)
+    L.call('cat_norm_bwd', C.byref(g), ops._p(x), ops._p(dy), ops._p(gamma), ops._p(beta), ops._p(mr[0]), ops._p(mr[1]), ops._p(dx), ops._p(dgamma),
+           ops._p(dbeta), accumulate, ops._p(ws), ops._stream())
+    return dx
 
 
 def channel_sum(src, m_pix, c, cs, dst):
@@ -435,3 +605,144 @@ def scatter_param_grads(p, grads):
         src2 = torch.as_strided(p.gv[v], (rows, cols), (sstr_, 1), o)
         torch.as_strided(gq, (rows, cols), (ops.weight_wcs(gq), 1), gq.storage_offset()).copy_(src2)
         grads[id(q)] = optim.deliver(q, gq)
+
+
+def backward_g(p, dt, x, z1, ss1, mr1, zd, ssd, mrd, *, need_dx, skip_grad=None, drop=None, sync=None):
+    """The backward pipeline: dT (the gradient of the branch sum, pixel stride p.cso) and what the forward saved -> (dx, grads), dx the
+    input gradient (None unless need_dx) and grads {id(parameter): gradient tensor, or None where it was written into the optimizer's
+    buffer}.  A generator over the statistics exchanges of norm_bwd_g(sync=sync).
+    skip_grad: a skip connection's share of dx (an activation like x), added by the last launch.  drop = (rate, {j}, ticket): the
+    forward's masks are re-derived from its ticket.  Weight-gradient launches are independent of the data-gradient chain: side-stream jobs
+    with branch streams on; on one stream they run where they stand or, with p.wgrad_batch, back to back at the end of step 8 with their
+    partial sums reduced by ONE launch (ops.WgradBatch)."""
+    n, c, h, w = x.shape
+    dev, hw, m_pix, xcs = x.device, h * w, n * h * w, ops.act_cs(x)
+    st = ops._stream()
+    grads = {}
+    pad_mode = L.PAD_REFLECT if p.reflect else L.PAD_ZERO
+    aff = lambda v: v if p.affine else None
+    side = ops.SideJobs(dev)      # the temporaries its launches read (a1, ad, dt, dz1) stay referenced by this frame until side.join()
+    batch = ops.WgradBatch(dev, grads) if p.wgrad_batch and not ops.branch_streams_enabled() else None
+
+    def put_wgrad(param, make):      # make(dst) -> (geometry, x pointer, dy pointer)
+        if batch is not None:
+            return batch.add(param, make)
+
+        def job():
+            grads[id(param)] = ops._write_param_grad(param, lambda dst_, acc: wgrad(*make(dst_), dst_, acc, ops._stream()))
+        side.run(job)
+
+    def put_wgrad_into(dst, geom, xp, dyp):      # merged launches: destination = a gradient view of the plan, overwritten
+        if batch is not None:
+            return batch.add_into(dst, 0, geom, xp, dyp)
+        side.run(lambda: wgrad(geom, xp, dyp, dst, 0, ops._stream()))
+
+    # ---- 1. re-materialise the hidden activations (inputs of the second convs / of the depthwise convs); with dropout the forward's
+    # masks are re-derived from its ticket: res slices of A1 and all of Ad dropped, the dw slices of A1 (depthwise inputs) not
+    a1, ad = materialise(p, z1, ss1, zd, ssd, drop, dw_slices=True) if drop is not None else (rematerialise(p, z1, ss1, p.instance), None)
+    da1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
+    dad = None
+    if p.dws:
+        if drop is None:
+            ad = rematerialise(p, zd, ssd, p.instance)
+        dad = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
+    # ---- 2. / 3. second convs: weight gradients from (hidden activation slice, dT); input gradients into slices of dA1 / dAd
+    side.fork()
+    for b in p.branches:
+        res = b['kind'] == 'res'
+        k2, m, w1 = b['k2'], b['m'], b['w1']
+        pad2 = (k2 - 1) // 2
+        src, scs_, o = (a1, p.hc1, b['o1']) if res else (ad, p.hcd, b['od'])
+        dst, dcs = (da1, p.hc1) if res else (dad, p.hcd)
+        xptr = C.c_void_p(src.data_ptr() + 4 * o)
+        mode2 = pad_mode if pad2 > 0 else L.PAD_ZERO
+
+        def kw(dst_, xptr=xptr, m=m, scs_=scs_, k2=k2, pad2=pad2, mode2=mode2):
+            return ops._conv_geom(n, h, w, m, scs_, h, w, p.Cout, p.cso, k2, k2, 1, pad2, mode2, wcs=ops._grad_wcs(dst_)), xptr, ops._p(dt)
+        if res or not p.merge2:
+            put_wgrad(b['conv2'].weight, kw)
+        if (not res and p.dpack2_dw is not None) or (p.s1d is not None and any(b is r for r in p.s1d)):
+            continue            # input gradient: the merged launch below
+        seg_pad = k2 - 1 - (0 if mode2 == L.PAD_REFLECT else pad2)
+        seg = tconv.Segment(None, k2, seg_pad, False, b['d2off'], c4=p.cso, cin=p.Cout, xcs=p.cso, ptr=dt.data_ptr())
+        if mode2 == L.PAD_REFLECT:
+            dxp = torch.empty((n, h + 2 * pad2, w + 2 * pad2, w1), device=dev, dtype=torch.float32)
+            tconv.run([seg], p.dpack2, None, dxp, m, n, h, w, h + 2 * pad2, w + 2 * pad2, ycs=w1, ycw=w1, yptr=dxp.data_ptr())
+            L.call('cat_reflect_pad_bwd2', ops._p(dxp), w1, C.c_void_p(dst.data_ptr() + 4 * o), dcs, None, 0, n, h, w, w1, pad2, st)
+        else:
+            tconv.run([seg], p.dpack2, None, None, m, n, h, w, h, w, ycs=dcs, ycw=w1, yptr=dst.data_ptr() + 4 * o)
+    # ---- 4. merged second-conv input gradients: dT staged once for the 5 x 5 and the 3 x 3 residual branch and the N-concatenated 1 x 1
+    # second convs of the depthwise branches (p.s1d), or those 1 x 1 convs alone as ONE launch over dT into dAd
+    nvalid_dw = sum(b['m'] for b in p.dws)
+    if p.s1d is not None:
+        r5, r3 = p.s1d
+        gs = L.Stage1Geom()
+        gs.N, gs.H, gs.W, gs.xcs, gs.cin, gs.reflect, gs.ycs, gs.scs = n, h, w, p.cso, p.Cout, 0, 0, 0
+        packs, dxs, dxcs = (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_int * 3)(p.hc1, p.hc1, p.hcd)
+        for slot, (col0, width, nvalid, pk, dst) in enumerate(((r5['o1'], r5['w1'], r5['m'], p.dpack2.data_ptr() + 4 * r5['d2off'], da1),
+                                                               (r3['o1'], r3['w1'], r3['m'], p.dpack2.data_ptr() + 4 * r3['d2off'], da1),
+                                                               (0, p.hcd, nvalid_dw, p.dpack2_dw.data_ptr(), dad))):
+            gs.col0[slot], gs.width[slot], gs.nvalid[slot] = col0, width, nvalid
+            packs[slot], dxs[slot] = pk, dst.data_ptr()
+        L.call('cat_tstage1_dgrad', C.byref(gs), ops._p(dt), packs, dxs, dxcs, ops._stream())
+    elif p.dws and p.dpack2_dw is not None:
+        seg = tconv.Segment(None, 1, 0, False, 0, c4=p.cso, cin=p.Cout, xcs=p.cso, ptr=dt.data_ptr())
+        tconv.run([seg], p.dpack2_dw, None, None, p.hcd, n, h, w, h, w, ycs=p.hcd, ycw=p.hcd, yptr=dad.data_ptr(), nvalid=nvalid_dw)
+    if drop is not None:      # gradients of the dropped activations -> of the activations: x keep * s (in place, before the norms)
+        for kind, d_, hc in (('res', da1, p.hc1), ('dw', dad, p.hcd)):
+            segs_k = drop_segs(p, drop[1], kind)
+            if segs_k:
+                ops.dropout_apply(ops.dropout_geom(m_pix, hc, hc, hc, drop[0], segs_k, rest=0), d_, d_, drop[2])
+    # ---- 5. d W2 of all depthwise branches: dT^T x Ad as ONE 1x1 weight-gradient launch over the concatenated hidden buffer; d bias2
+    if p.merge2:
+        put_wgrad_into(p.gv['w2'], ops._conv_geom(n, h, w, p.hcd, p.hcd, h, w, p.Cout, p.cso, 1, 1, 1, 0, L.PAD_ZERO, wcs=p.hcd), ops._p(ad), ops._p(dt))
+    if p.has_bias2:
+        channel_sum(dt, m_pix, p.Cout, p.cso, p.gv['c2'])
+    # ---- 6. depthwise stage
+    if p.dws:
+        dzd = yield from norm_bwd_g(p, n, hw, p.hcd, p.hcd, zd, dad, aff(p.gammad), aff(p.betad), mrd, p.act, p.slope, aff(p.gv['gd']), aff(p.gv['bd']),
+                                    sync=sync)
+        if p.has_biasd:
+            channel_sum(dzd, m_pix, p.hcd, p.hcd, p.gv['cd'])
+        dw_bwd(p, a1, da1, dzd, grads, p.reflect)
+    # ---- 7. stage-1 norms (all branches at once)
+    dz1 = yield from norm_bwd_g(p, n, hw, p.hc1, p.hc1, z1, da1, aff(p.gamma1), aff(p.beta1), mr1, p.act, p.slope, aff(p.gv['g1']), aff(p.gv['b1']),
+                                sync=sync)
+    if p.has_bias1:
+        channel_sum(dz1, m_pix, p.hc1, p.hc1, p.gv['c1'])
+    # ---- 8. first convs: weight gradients from (x, dZ1 slice)
+    side.refork()
+    if p.merge1 is not None:
+        g1 = p.merge1
+        put_wgrad_into(p.gv['w1'], ops._conv_geom(n, h, w, c, xcs, h, w, g1['width'], p.hc1, 1, 1, 1, 0, L.PAD_ZERO, wcs=p.csi), ops._p(x),
+                       C.c_void_p(dz1.data_ptr() + 4 * g1['off']))
+    for b in p.branches:
+        if p.merge1 is not None and b['k'] == 1:
+            continue
+        k, m = b['k'], b['m']
+        pad1 = (k - 1) // 2
+        mode1 = pad_mode if pad1 > 0 else L.PAD_ZERO
+        dyp = C.c_void_p(dz1.data_ptr() + 4 * b['o1'])
+
+        def kw1(dst_, dyp=dyp, m=m, k=k, pad1=pad1, mode1=mode1):
+            return ops._conv_geom(n, h, w, c, xcs, h, w, m, p.hc1, k, k, 1, pad1, mode1, wcs=ops._grad_wcs(dst_)), ops._p(x), dyp
+        put_wgrad(b['conv1'].weight, kw1)
+    if batch is not None:
+        batch.flush()
+    # ---- 9. first convs: the input gradients as ONE K-concatenated launch (+ the skip connection's share)
+    dx = None
+    if need_dx:
+        M = max((b['k'] - 1) // 2 for b in p.branches) if p.reflect else 0
+        segs = dgrad1_segs(p, dz1, M)
+        dx = ops.empty_act(n, c, h, w, dev)
+        if M:
+            dxp = torch.empty((n, h + 2 * M, w + 2 * M, p.csi), device=dev, dtype=torch.float32)
+            tconv.run(segs, p.dpack1, None, dxp, c, n, h, w, h + 2 * M, w + 2 * M, ycs=p.csi, ycw=p.csi, yptr=dxp.data_ptr())
+            L.call('cat_reflect_pad_bwd2', ops._p(dxp), p.csi, ops._p(dx), ops.act_cs(dx), ops._p(skip_grad),
+                   ops.act_cs(skip_grad) if skip_grad is not None else 0, n, h, w, p.csi, M, st)
+        else:
+            tconv.run(segs, p.dpack1, None, dx, c, n, h, w, h, w, res=skip_grad)
+    side.join()
+    # ---- 10. scatter the concatenated parameter gradients
+    scatter_param_grads(p, grads)
+    return dx, grads

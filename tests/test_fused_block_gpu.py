@@ -251,3 +251,23 @@ def test_fused_block_backward_with_mixed_parameter_ownership():
             assert q.grad.data_ptr() == view.data_ptr(), k
         assert float(q.grad.abs().max()) > 0.0, k
         assert torch.equal(q.grad, ref[k].grad), k
+
+
+def test_stage2_segments_keep_the_buffers_they_read():
+    """The pipeline returns the stage-2 segment list and the caller launches stage 2 later, after allocating its output: every segment must
+    hold the tensor its raw pointer addresses (with dropout these are A1 / Ad, which nothing else references), otherwise the caching
+    allocator may hand that memory to the output of the very launch that reads it."""
+    from cat_amd import _lib, fused_block, fused_unit, ops, rng
+    _lib.load()
+    dev = torch.device('cuda:0')
+    blk = _block('batch', dev, 40, (7, 6, 9), (16, 5, 0), 'reflect')
+    x = ops.to_nhwc(detfill.normal((8, 40, 32, 48), 5).to(dev))
+    p = fused_block.plan_for(blk, x)
+    p.prepare()
+    for drop in (None, (0.5, frozenset(range(5)), rng.draw(dev))):
+        z1, st1, zd, std, segs = fused_block._run(fused_unit.forward_g(p, x, drop=drop))
+        torch.cuda.synchronize()
+        assert len(segs) == len(p.branches)
+        for s in segs:
+            assert s.src is not None and s.src.data_ptr() <= s.ptr < s.src.data_ptr() + 4 * s.src.numel()
+            assert (s.src is z1 or s.src is zd) == (drop is None)
