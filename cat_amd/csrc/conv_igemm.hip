@@ -1574,20 +1574,22 @@ __global__ __launch_bounds__(256) void wgrad_reduce_many_kernel(const RedMany m)
 
 // ------------------------------------------------------------------------------------------------ host side
 // The tiles of the generic forward / dgrad kernels by GEMM width n (Cout / Cin): ROW(n <=, MT, MT when M is small, NT, WM, WN).
-// ONE table for the dispatch, default_bm and split_plan, so a tile rule cannot change in one of them only.
+// ONE table for the dispatch, the profiler names, default_bm and split_plan, so a tile rule cannot change in one of them only.
 // Small M = few output pixels (e.g. the student's 64x64 trunk at batch 16 = 256 tiles of 256 rows): halve the M tile so that every CU
-// holds 2+ workgroups and the per-chunk load / LDS / barrier latencies of one overlap the MFMA stream of another.
+// holds 2+ workgroups and the per-chunk load / LDS / barrier latencies of one overlap the MFMA stream of another.  Measured: that helps the
+// 16- and 32-wide rows (256-row default) and not the 48..96-wide ones, so only those two rows have a second tile; in every other row both
+// columns name the same tile and nothing more is compiled.
 // (N = 130 .. 192 -- the frozen teacher's 176-wide fused GEMM, SPADE's 170-wide heads -- would fill two 96-wide tiles better than two
 // 128-wide ones, 8 % instead of 31 % padding at 176; not taken: the 176-wide layer is the frozen teacher's merged 1 x 1, served by the
 // direct-to-LDS 128 x 128 tile ahead of this dispatch.)
 #define CONV_TILES(ROW, ...)         \
   ROW(16, 4, 2, 1, 4, 1, __VA_ARGS__) \
   ROW(32, 4, 2, 2, 4, 1, __VA_ARGS__) \
-  ROW(48, 2, 1, 3, 4, 1, __VA_ARGS__) \
-  ROW(64, 2, 1, 4, 4, 1, __VA_ARGS__) \
-  ROW(96, 2, 1, 6, 4, 1, __VA_ARGS__) \
+  ROW(48, 2, 2, 3, 4, 1, __VA_ARGS__) \
+  ROW(64, 2, 2, 4, 4, 1, __VA_ARGS__) \
+  ROW(96, 2, 2, 6, 4, 1, __VA_ARGS__) \
   ROW(INT_MAX, 4, 4, 4, 2, 2, __VA_ARGS__)
-// ... and of conv_wgrad_kernel by Cout: ROW(Cout <=, MT, NT, WM, WN), for the launch and wgrad_plan
+// ... and of conv_wgrad_kernel by Cout: ROW(Cout <=, MT, NT, WM, WN), for the launch, the profiler names and wgrad_split
 #define WGRAD_TILES(ROW, ...)         \
   ROW(16, 1, 4, 1, 4, __VA_ARGS__)    \
   ROW(32, 2, 4, 1, 4, __VA_ARGS__)    \
@@ -1618,6 +1620,12 @@ static TileShape wgrad_tile(int cout) {
   return TileShape{};
 }
 
+// the profiler family of a launch through DISPATCH_TILE_N(n, smallm, ...) / WGRAD_TILES: the kernel's prefix + the tile's MT x NT x WM x WN
+#define CONV_TILE_NAME(NMAX, MT, MTS, NT, WM, WN, n, smallm, PFX) \
+  (n) <= NMAX ? ((smallm) ? PFX #MTS "x" #NT "x" #WM "x" #WN : PFX #MT "x" #NT "x" #WM "x" #WN) :
+#define TILE_NAME(PFX, n, smallm) (CONV_TILES(CONV_TILE_NAME, n, smallm, PFX) "")
+#define WGRAD_TILE_NAME(NMAX, MT, NT, WM, WN, cout) (cout) <= NMAX ? "conv_wgrad_" #MT "x" #NT "x" #WM "x" #WN :
+
 // out[pix][c] = act(sum_z part[z][pix][c] + bias[c]) for c < C; zeros for C <= c < cw
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias,
                                                             float* __restrict__ out, int64_t P, int C, int cw, int cs, int ksplit, int act,
@@ -1640,10 +1648,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 
 static int default_bm(int n) { return conv_tile(n, false).bm; }
-static bool use_small_m(int M, int n) {
-  if (n > 32) return false;   // measured: helps the 16/32-wide tiles (256-row default), not the 48..96-wide ones
-  return cdiv(M, default_bm(n)) < 768;
-}
+// take the small-M column of CONV_TILES?  (Which rows have a tile of their own there is the table's business.)
+static bool use_small_m(int M, int n) { return cdiv(M, default_bm(n)) < 768; }
 
 // Split-K plan: when the (M, N) tile grid of the kernel the dispatcher would pick is far below the 256 CUs (the 4x8 .. 32x64
 // pixel layers of the SPADE generators: M = 128 .. 8192 pixels against K = 25 * 1024), K is cut into slices of >= 4 chunks.
@@ -1689,8 +1695,16 @@ static void zero_lanes_past_c4(float* out, int64_t P, int C, int cw, int cs, hip
   zero_lanes_kernel<<<(int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)), 256, 0, s>>>(out, P, cs, c4, cw);
 }
 
+// dynamic LDS of the double-buffered 128 x 128 x 32 tiles
+constexpr size_t kLds128 = (size_t)2 * (128 + 128) * 32 * sizeof(float);
 // the direct-to-LDS kernels address a tensor with 32-bit byte offsets
 static bool fits_2gb(int64_t floats) { return floats * 4 < (int64_t)2147483647; }
+
+// weight floats per (cout, tap): 0 in the geometry = dense
+static int weight_cs(const cat_conv_t* g) { return g->wcs > 0 ? g->wcs : g->Cin; }
+
+// 2 x the layer's multiply-adds: what every pass (forward, input gradient, weight gradient) reports to the profiler
+static double conv_flops(const cat_conv_t* g) { return 2.0 * (double)g->N * g->Ho * g->Wo * g->Cout * g->kh * g->kw * g->Cin; }
 
 int fill_common(IgemmArgs& a, const cat_conv_t* g, int pad_w = -1, int dil = 1) {
   const int padw = pad_w >= 0 ? pad_w : g->pad;
@@ -1706,7 +1720,7 @@ int fill_common(IgemmArgs& a, const cat_conv_t* g, int pad_w = -1, int dil = 1) 
   a.Ho = g->Ho; a.Wo = g->Wo; a.Cout = g->Cout; a.ycs = g->ycs;
   a.kh = g->kh; a.kw = g->kw; a.stride = g->stride; a.pad = g->pad; a.padw = padw; a.reflect = g->pad_mode == CAT_PAD_REFLECT;
   a.act = g->act; a.slope = g->slope;
-  a.wcs = g->wcs > 0 ? g->wcs : g->Cin;
+  a.wcs = weight_cs(g);
   CAT_REQUIRE(a.wcs >= g->Cin, "conv: wcs < Cin");
   a.wvec = (a.wcs % 4) == 0;
   a.M = g->N * g->Ho * g->Wo;
@@ -1721,27 +1735,25 @@ int walk_extent(int c4) {
   return (c16 - c4) * 8 <= c16 ? c16 : c4;
 }
 
-struct WgradPlan { int nsplit, mchunk, tiles; };
-WgradPlan wgrad_plan(const cat_conv_t* g) {
+// pixel split of conv_wgrad_kernel: nsplit slices of mchunk pixels, partial sums per slice
+struct WgradSplit { int nsplit, mchunk; };
+WgradSplit wgrad_split(const cat_conv_t* g) {
   const int Cout = g->Cout, K = g->kh * g->kw * ((g->Cin + 3) & ~3);
   const TileShape t = wgrad_tile(Cout);
-  WgradPlan pl;
-  pl.tiles = cdiv(Cout, t.bm) * cdiv(K, t.bn);
+  const int tiles = cdiv(Cout, t.bm) * cdiv(K, t.bn);
   const int M = g->N * g->Ho * g->Wo;
-  const char* tenv = getenv("CAT_WGRAD_BLOCKS");   // workgroups the pixel split aims for (tuning knob, read per call)
-  const int target = tenv ? atoi(tenv) : 1024;
-  int ns = cdiv(target > 0 ? target : 1024, pl.tiles);
-  const char* cenv = getenv("CAT_WGRAD_MINCHUNK");   // fewest pixels per slice (tuning knob)
-  const int minchunk = cenv && atoi(cenv) >= 16 ? atoi(cenv) : 256;
+  // tuning knobs, read per call: the workgroups the pixel split aims for, the fewest pixels per slice, the most slices
+  const auto knob = [](const char* name, int least, int dflt) { const char* v = getenv(name); return v && atoi(v) >= least ? atoi(v) : dflt; };
+  int ns = cdiv(knob("CAT_WGRAD_BLOCKS", 1, 1024), tiles);
+  const int minchunk = knob("CAT_WGRAD_MINCHUNK", 16, 256), maxsplit = knob("CAT_WGRAD_MAXSPLIT", 1, 256);
   int maxs = M / minchunk > 0 ? M / minchunk : 1;
-  const char* senv = getenv("CAT_WGRAD_MAXSPLIT");
-  const int maxsplit = senv && atoi(senv) >= 1 ? atoi(senv) : 256;
   if (maxs > maxsplit) maxs = maxsplit;
   if (ns > maxs) ns = maxs;
   if (ns < 1) ns = 1;
-  pl.mchunk = cat::round_up(cdiv(M, ns), 16);
-  pl.nsplit = cdiv(M, pl.mchunk);
-  return pl;
+  WgradSplit sp;
+  sp.mchunk = cat::round_up(cdiv(M, ns), 16);
+  sp.nsplit = cdiv(M, sp.mchunk);
+  return sp;
 }
 
 // CAT_SCHED scheduling experiments of the 128 x 128 tile: instantiated by the diagnostic build only
@@ -1753,38 +1765,237 @@ void launch_fwd_sched(int sched, int grid, const IgemmArgs& a, hipStream_t s) {
   }
 }
 
+// a kernel that needs more than 64 KB of dynamic LDS: opted in once per instantiation and device, then launched
+template <auto KERNEL, class... Extra>
+static void launch_big_lds(dim3 grid, size_t lds, hipStream_t s, const IgemmArgs& a, Extra... extra) {
+  static cat::LdsOptIn optin;
+  cat::lds_optin(optin, (const void*)KERNEL, (int)lds);
+  KERNEL<<<grid, 256, lds, s>>>(a, extra...);
+}
+
+// ---- One plan per pass.  plan_fwd / plan_dgrad / plan_wgrad map a geometry and what the caller supplies to the kernel family, its tile and
+// split, the derived extents, the workspace bytes and the profiler family.  The workspace queries, cat_conv2d_dgrad_t_applicable and the
+// launches below all read the SAME plan, so a workspace cannot be sized for one kernel while another launches into it.  The applicability
+// predicates, the tile rules and the A/B switches (CAT_FWD_DIRECT, CAT_DGRAD_DIRECT, CAT_DGRAD_T, CAT_WGRAD_DIRECT, CAT_WGRAD_*) are
+// consulted by the plans only.  Plain struct, no allocation: the eager SPADE step is bound by host issue time.
+// Small: conv_smallco.hip (Cout <= 3, dgrad Cin <= 6); Direct32: the direct-to-LDS 128 x 128 tiles conv_{fwd,dgrad,wgrad}32d_kernel;
+// Tile32: conv_fwd32_kernel over CONV_TILES / conv_dgrad32_kernel; Tile16: conv_{fwd,dgrad}_kernel over CONV_TILES / conv_wgrad_kernel over
+// WGRAD_TILES; LdsTile: conv_twgrad.hip; PixelStream: conv_pwgrad.hip
+enum class Kernel { Small, Direct32, Tile32, Tile16, LdsTile, PixelStream };
+struct ConvPlan {
+  Kernel kernel;
+  const char* name;   // profiler family
+  int split;          // slices reduced from the workspace (1 = none): fwd / dgrad of K, wgrad of the pixels (Direct32: of the output rows)
+  int chunk;          // length of a slice: fwd / dgrad K chunks, wgrad Tile16 pixels, wgrad Direct32 output rows
+  bool smallm;        // fwd / dgrad over CONV_TILES: the small-M column of the row
+  bool direct;        // wgrad: the kernel writes dw itself (the one slice of Direct32 / Tile16) -- no workspace, no reduce
+  bool t_ok;          // dgrad Direct32: the transposed-filter variant is on offer (cat_conv2d_dgrad_t)
+  int cval, c4, K;    // IgemmArgs' channel and K extents
+  int Hin, Win, pad_eff, mmax;   // dgrad: the plane written (reflect: the padded one, pad_eff = 0), pixels of the largest stride-parity class
+  size_t ws_bytes;
+};
+static ConvPlan pick(ConvPlan p, Kernel kernel, const char* name, int split = 1, int chunk = 0) {
+  p.kernel = kernel; p.name = name; p.split = split; p.chunk = chunk;
+  return p;
+}
+
+// BK = 32 forward kernels: per-tap K extent a multiple of 16 (walk_extent allows <= 12.5 % zero padding), float4-readable filter rows
+static bool fwd_bk32_ok(const cat_conv_t* g, int c4) {
+  static const bool dbg_on = cat::kDiag && getenv("CAT_DBG");   // the per-phase clocks are in conv_fwd_kernel
+  return (weight_cs(g) % 4) == 0 && (c4 & 15) == 0 && !dbg_on;
+}
+
+// has_ws: the caller passes a workspace (only then may K be split); plain: cat_conv2d_fwd / _ws, not the rect or ex entry points
+static ConvPlan plan_fwd(const cat_conv_t* g, bool has_ws, bool plain) {
+  ConvPlan p{};
+  const int M = g->N * g->Ho * g->Wo, n = g->Cout;
+  p.cval = (g->Cin + 3) & ~3;
+  p.c4 = walk_extent(p.cval);
+  p.K = g->kh * g->kw * p.c4;
+  static const int fwd_direct = getenv("CAT_FWD_DIRECT") ? atoi(getenv("CAT_FWD_DIRECT")) : 1;
+  if (plain && cat::smallco_applicable(g)) {
+    p = pick(p, Kernel::Small, "conv_fwd_smallco", has_ws ? cat::smallco_fwd_ksplit(g) : 1);
+  } else {
+    const bool bk32 = fwd_bk32_ok(g, p.c4);
+    const SplitPlan sp = bk32 && has_ws ? split_plan(M, n, (p.K + 31) >> 5) : SplitPlan{1, 0};
+    p.smallm = use_small_m(M, n);
+    // direct-to-LDS variant of the 128 x 128 tile: Cin % 32 == 0 (a chunk never straddles taps), no K split, 32-bit byte offsets
+    if (fwd_direct && bk32 && sp.ksplit == 1 && n > 96 && (g->Cin & 31) == 0 && p.c4 == g->Cin && weight_cs(g) >= g->Cin &&
+        fits_2gb((int64_t)g->N * g->H * g->W * g->xcs) && fits_2gb((int64_t)n * g->kh * g->kw * weight_cs(g)))
+      p = pick(p, Kernel::Direct32, "conv_fwd32d_4x4x2x2");
+    else if (bk32)
+      p = pick(p, Kernel::Tile32, sp.ksplit > 1 ? TILE_NAME("conv_fwd32sk_", n, p.smallm) : TILE_NAME("conv_fwd32_", n, p.smallm), sp.ksplit, sp.kchunks);
+    else
+      p = pick(p, Kernel::Tile16, TILE_NAME("conv_fwd_", n, p.smallm));
+  }
+  p.ws_bytes = p.split > 1 ? (size_t)p.split * M * g->ycs * sizeof(float) : 0;
+  return p;
+}
+
+// does the direct-to-LDS dgrad tile apply (and with it the transposed-filter variant)?
+static bool dgrad32d_ok(const cat_conv_t* g) {
+  static const int on = getenv("CAT_DGRAD_DIRECT") ? atoi(getenv("CAT_DGRAD_DIRECT")) : 1;
+  const int wcs = weight_cs(g);
+  return on && g->Cin > 96 && (wcs & 3) == 0 && g->Cout % 32 == 0 && g->Cin % 4 == 0 &&
+         fits_2gb((int64_t)g->N * g->Ho * g->Wo * g->ycs) && fits_2gb((int64_t)g->Cout * g->kh * g->kw * wcs);
+}
+
+// has_ws: the caller passes a workspace of dxcs floats per pixel and slice (only then may K be split); has_wt: it passes the transposed
+// filter; has_bias: it passes a bias (with g->act the fused epilogue, which the Cin <= 6 kernel does not have)
+static ConvPlan plan_dgrad(const cat_conv_t* g, int dxcs, bool has_ws, bool has_wt, bool has_bias) {
+  ConvPlan p{};
+  const bool refl = g->pad_mode == CAT_PAD_REFLECT;
+  const int st = g->stride < 1 ? 1 : g->stride, n = g->Cin;   // (the two queries do not validate the geometry)
+  p.Hin = refl ? g->H + 2 * g->pad : g->H;
+  p.Win = refl ? g->W + 2 * g->pad : g->W;
+  p.pad_eff = refl ? 0 : g->pad;
+  p.mmax = g->N * cdiv(p.Hin, st) * cdiv(p.Win, st);
+  p.cval = (g->Cout + 3) & ~3;
+  p.c4 = walk_extent(p.cval);
+  static const int t_on = getenv("CAT_DGRAD_T") ? atoi(getenv("CAT_DGRAD_T")) : 1;
+  // K is split at stride 1 only: one parity class, mmax = every pixel of the plane
+  const SplitPlan sp = has_ws && st == 1 && g->N > 0 ? split_plan(p.mmax, n, (g->kh * g->kw * p.c4 + 15) >> 4) : SplitPlan{1, 0};
+  p.smallm = use_small_m(p.mmax, n);
+  if (sp.ksplit > 1)
+    p = pick(p, Kernel::Tile16, TILE_NAME("conv_dgradsk_", n, p.smallm), sp.ksplit, sp.kchunks);
+  else if (!has_bias && g->act == CAT_ACT_NONE && cat::smallci_dgrad_applicable(g))
+    p = pick(p, Kernel::Small, "conv_dgrad_smallci");
+  else if (dgrad32d_ok(g) && p.c4 == g->Cout)   // BK = 32, direct to LDS (the discriminator's and the teacher's wide layers)
+    p = pick(p, Kernel::Direct32, has_wt ? "conv_dgrad32dt_4x4x2x2" : "conv_dgrad32d_4x4x2x2");
+  else if (n > 96 && (weight_cs(g) % 4) == 0 && g->Cout % 16 == 0 && n % 4 == 0)
+    p = pick(p, Kernel::Tile32, "conv_dgrad32_4x4x2x2");
+  else
+    p = pick(p, Kernel::Tile16, TILE_NAME("conv_dgrad_", n, p.smallm));
+  p.t_ok = t_on && p.kernel == Kernel::Direct32;
+  p.ws_bytes = p.split > 1 ? (size_t)p.split * g->N * p.Hin * p.Win * dxcs * sizeof(float) : 0;
+  return p;
+}
+
+// direct-to-LDS wgrad (conv_wgrad32d_kernel): wide zero-padded layers whose 128-column K blocks lie inside one tap; returns the number
+// of output-row slices (0 = not applicable)
+static int wgrad32d_nsplit(const cat_conv_t* g, int* rows_per) {
+  static const int on = getenv("CAT_WGRAD_DIRECT") ? atoi(getenv("CAT_WGRAD_DIRECT")) : 1;
+  // (output rows that end in a partial 32-pixel segment are served: the segment's tail lanes are parked out of range)
+  if (!on || g->Cout <= 96 || (g->Cin & 127) || g->pad_mode != CAT_PAD_ZERO || !fits_2gb((int64_t)g->N * g->H * g->W * g->xcs) ||
+      !fits_2gb((int64_t)g->N * g->Ho * g->Wo * g->ycs) || weight_cs(g) < g->Cin)
+    return 0;
+  const int tiles = cdiv(g->Cout, 128) * (g->kh * g->kw * g->Cin / 128);
+  const int R = g->N * g->Ho;
+  // workgroups aimed at: ONE resident round (256 CUs x 2).  Round 6, conv_bench on the three PatchGAN layers: 512 -> 2067 / 555 / 554 us, 1024 (two
+  // rounds, twice the partial-sum traffic) 2155 / 562 / 563, 768 / 1536 / 2048 slower still; with 512 tiles (conv4) the launch writes dw directly
+  int ns = cdiv(512, tiles);
+  if (ns > R) ns = R;
+  if (ns < 1) ns = 1;
+  *rows_per = cdiv(R, ns);
+  return cdiv(R, *rows_per);
+}
+
+// The order of the weight-gradient paths is written here and nowhere else.  Two predicates lean on it: the wide direct tile does not ask
+// again whether the Cout <= 3 kernels apply (they come first), and pwgrad_applicable (conv_pwgrad.hip) keeps its own copy of the wide direct
+// tile's "Cout > 96 && Cin % 128 == 0", so that under CAT_WGRAD_DIRECT=0 those layers fall to the generic tile and not to it.
+static ConvPlan plan_wgrad(const cat_conv_t* g) {
+  ConvPlan p{};
+  p.c4 = (g->Cin + 3) & ~3;
+  p.K = g->kh * g->kw * p.c4;
+  int rows_per = 0;
+  if (cat::smallco_applicable(g)) {
+    p = pick(p, Kernel::Small, "conv_wgrad_smallco", cat::smallco_wgrad_nblk(g));
+  } else if (cat::twgrad_applicable(g)) {
+    p = pick(p, Kernel::LdsTile, "conv_twgrad", cat::twgrad_nblk(g));
+  } else if (cat::pwgrad_applicable(g)) {
+    p = pick(p, Kernel::PixelStream, "conv_pwgrad", cat::pwgrad_nblk(g));
+  } else if (const int nsd = wgrad32d_nsplit(g, &rows_per)) {
+    p = pick(p, Kernel::Direct32, "conv_wgrad32d_4x4x2x2", nsd, rows_per);
+  } else {
+    const WgradSplit sp = wgrad_split(g);
+    p = pick(p, Kernel::Tile16, WGRAD_TILES(WGRAD_TILE_NAME, g->Cout) "", sp.nsplit, sp.mchunk);
+  }
+  p.direct = p.split == 1 && (p.kernel == Kernel::Direct32 || p.kernel == Kernel::Tile16);
+  p.ws_bytes = (size_t)p.split * g->Cout * p.K * sizeof(float);
+  return p;
+}
+
 }  // namespace
 
 extern "C" {
 
-static bool fwd_bk32_ok(const IgemmArgs& a) {
-  static const bool dbg_on = cat::kDiag && getenv("CAT_DBG");
-  return a.wvec && (a.c4 & 15) == 0 && !dbg_on;
-}
-
-static int fwd_setup(IgemmArgs& a, const cat_conv_t* g, int pad_w = -1, int dil = 1) {
-  if (int e = fill_common(a, g, pad_w, dil)) return e;
-  a.cval = (g->Cin + 3) & ~3;
-  a.c4 = walk_extent(a.cval);
-  a.K = g->kh * g->kw * a.c4;
-  return 0;
-}
-
 size_t cat_conv2d_fwd_ws_bytes(const cat_conv_t* g) {
   IgemmArgs a{};
-  if (fwd_setup(a, g)) return 0;
-  if (cat::smallco_applicable(g)) {
-    const int ks = cat::smallco_fwd_ksplit(g);
-    return ks > 1 ? (size_t)ks * a.M * g->ycs * sizeof(float) : 0;
-  }
-  if (!fwd_bk32_ok(a)) return 0;
-  const SplitPlan sp = split_plan(a.M, a.Cout, (a.K + 31) >> 5);
-  return sp.ksplit > 1 ? (size_t)sp.ksplit * a.M * g->ycs * sizeof(float) : 0;
+  if (fill_common(a, g)) return 0;
+  return plan_fwd(g, true, true).ws_bytes;
 }
 
 struct FwdEx { int dil; const float* res; int rcs; };   // cat_conv2d_fwd_ex: dilation + residual epilogue (the EX kernel instantiations)
 static int conv_fwd_impl(const cat_conv_t* g, const float* x, const float* w, const float* bias, float* y, void* ws, cat_stream_t stream,
-                         int pad_w = -1, const FwdEx* ex = nullptr);
+                         int pad_w = -1, const FwdEx* ex = nullptr) {
+  IgemmArgs a{};
+  if (int e = fill_common(a, g, pad_w, ex ? ex->dil : 1)) return e;
+  const bool rect = pad_w >= 0 && pad_w != g->pad;
+  const ConvPlan pl = plan_fwd(g, ws != nullptr, !rect && !ex);
+  a.cval = pl.cval; a.c4 = pl.c4; a.K = pl.K;
+  a.ksplit = pl.split; a.kchunks = pl.chunk; a.part = (float*)ws;
+  if (ex) { a.res = ex->res; a.rcs = ex->rcs; }
+  a.a = x; a.b = w; a.bias = bias; a.out = y;
+  a.cw = g->ycw > g->Cout ? g->ycw : g->Cout;
+  CAT_REQUIRE(a.cw <= g->ycs, "conv fwd: ycw > ycs");
+  hipStream_t s = (hipStream_t)stream;
+  zero_lanes_past_c4(y, a.M, a.Cout, a.cw, a.ycs, s);
+  // diagnostic build only (common.h kDiag): scheduling experiments, an LDS pad that caps workgroups per CU, per-phase shader clocks
+  static const int sched = (cat::kDiag && getenv("CAT_SCHED")) ? atoi(getenv("CAT_SCHED")) : 0;
+  static const int lds_pad = (cat::kDiag && getenv("CAT_LDS_PAD")) ? atoi(getenv("CAT_LDS_PAD")) : 0;
+  static const bool dbg_on = cat::kDiag && getenv("CAT_DBG");
+  static long long* dbg_buf = nullptr;
+  if (dbg_on && pl.kernel == Kernel::Tile16) {
+    if (!dbg_buf) (void)hipMalloc(&dbg_buf, 64);
+    (void)hipMemsetAsync(dbg_buf, 0, 64, s);
+    a.dbg = dbg_buf;
+  }
+#define LAUNCH(MT, NT, WM, WN)                                                             \
+  {                                                                                        \
+    const int grid = cdiv(a.M, WM * MT * 16) * cdiv(a.Cout, WN * NT * 16);                 \
+    /* the EX launches take neither the CAT_SCHED variants nor the CAT_LDS_PAD occupancy cap: those diagnostics cover the plain kernels only */ \
+    if (ex && !a.wvec) conv_fwd_kernel<MT, NT, WM, WN, false, 0, true><<<grid, 256, 0, s>>>(a); \
+    else if (ex) conv_fwd_kernel<MT, NT, WM, WN, true, 0, true><<<grid, 256, 0, s>>>(a);    \
+    else if (!a.wvec) conv_fwd_kernel<MT, NT, WM, WN, false, 0><<<grid, 256, 0, s>>>(a);    \
+    else if (WN == 2 && sched) launch_fwd_sched<cat::kDiag>(sched, grid, a, s);             \
+    else conv_fwd_kernel<MT, NT, WM, WN, true, 0><<<grid, 256, lds_pad, s>>>(a);            \
+  }
+#define LAUNCH32(MT, NT, WM, WN)                                                                      \
+  {                                                                                                   \
+    const dim3 grid(cdiv(a.M, WM * MT * 16) * cdiv(a.Cout, WN * NT * 16), pl.split);                   \
+    const size_t lds = (size_t)2 * (WM * MT * 16 + WN * NT * 16) * 32 * sizeof(float);                \
+    if (ex) launch_big_lds<conv_fwd32_kernel<MT, NT, WM, WN, true>>(grid, lds, s, a);                  \
+    else launch_big_lds<conv_fwd32_kernel<MT, NT, WM, WN>>(grid, lds, s, a);                           \
+  }
+  {
+    cat::ProfScope prof(pl.name, conv_flops(g), 0.0, stream);
+    const int grid128 = cdiv(a.M, 128) * cdiv(a.Cout, 128);
+    switch (pl.kernel) {
+      case Kernel::Small:
+        if (int e = cat::smallco_fwd(g, x, w, bias, y, (float*)ws, pl.split, s)) return e;
+        break;
+      case Kernel::Direct32:
+        if (ex) launch_big_lds<conv_fwd32d_kernel<true>>(grid128, kLds128, s, a);
+        else launch_big_lds<conv_fwd32d_kernel<false>>(grid128, kLds128, s, a);
+        break;
+      case Kernel::Tile32: DISPATCH_TILE_N(a.Cout, pl.smallm, LAUNCH32) break;
+      default: DISPATCH_TILE_N(a.Cout, pl.smallm, LAUNCH) break;
+    }
+    if (pl.split > 1) launch_splitk_reduce((const float*)ws, bias, y, a.M, a.Cout, a.cw, a.ycs, pl.split, a.act, a.slope, s);
+  }
+#undef LAUNCH32
+#undef LAUNCH
+  if (a.dbg) {
+    long long h[8];
+    (void)hipMemcpyAsync(h, dbg_buf, 64, hipMemcpyDeviceToHost, s);
+    (void)hipStreamSynchronize(s);
+    fprintf(stderr, "[cat dbg raw] %lld %lld %lld %lld %lld err=%s\n", h[0], h[1], h[2], h[3], h[4], hipGetErrorString(hipGetLastError()));
+    if (h[4] > 0)
+      fprintf(stderr, "[cat dbg] chunks=%lld  per chunk: gload %lld  ds_read+mfma %lld  wait+ds_write %lld  barrier %lld  (shader clocks)\n", h[4],
+              h[0] / h[4], h[1] / h[4], h[2] / h[4], h[3] / h[4]);
+  }
+  return cat::check_launch("conv2d_fwd");
+}
 
 int cat_conv2d_fwd(const cat_conv_t* g, const float* x, const float* w, const float* bias, float* y, cat_stream_t stream) {
   return conv_fwd_impl(g, x, w, bias, y, nullptr, stream);
@@ -1817,127 +2028,55 @@ int cat_conv2d_fwd_ex(const cat_conv_t* g, int dilation, const float* x, const f
   return conv_fwd_impl(g, x, w, bias, y, nullptr, stream, -1, &ex);
 }
 
-static int conv_fwd_impl(const cat_conv_t* g, const float* x, const float* w, const float* bias, float* y, void* ws, cat_stream_t stream,
-                         int pad_w, const FwdEx* ex) {
-  IgemmArgs a{};
-  if (int e = fwd_setup(a, g, pad_w, ex ? ex->dil : 1)) return e;
-  if (ex) { a.res = ex->res; a.rcs = ex->rcs; }
-  const bool rect = pad_w >= 0 && pad_w != g->pad;
-  a.a = x; a.b = w; a.bias = bias; a.out = y;
-  a.cw = g->ycw > g->Cout ? g->ycw : g->Cout;
-  CAT_REQUIRE(a.cw <= g->ycs, "conv fwd: ycw > ycs");
-  hipStream_t s = (hipStream_t)stream;
-  zero_lanes_past_c4(y, a.M, a.Cout, a.cw, a.ycs, s);
-  if (!rect && !ex && cat::smallco_applicable(g)) {
-    cat::ProfScope prof("conv_fwd_smallco", 2.0 * (double)g->N * g->Ho * g->Wo * g->Cout * g->kh * g->kw * g->Cin, 0.0, stream);
-    const int ks = ws ? cat::smallco_fwd_ksplit(g) : 1;
-    if (int e = cat::smallco_fwd(g, x, w, bias, y, (float*)ws, ks, s)) return e;
-    if (ks > 1) {
-      launch_splitk_reduce((const float*)ws, bias, y, a.M, a.Cout, a.cw, a.ycs, ks, a.act, a.slope, s);
-      return cat::check_launch("conv2d_fwd_smallco_reduce");
-    }
-    return 0;
-  }
-  const double prof_flops = 2.0 * (double)g->N * g->Ho * g->Wo * g->Cout * g->kh * g->kw * g->Cin;
-  // diagnostic build only (common.h kDiag): scheduling experiments, an LDS pad that caps workgroups per CU, per-phase shader clocks
-  static const int sched = (cat::kDiag && getenv("CAT_SCHED")) ? atoi(getenv("CAT_SCHED")) : 0;
-  static const int lds_pad = (cat::kDiag && getenv("CAT_LDS_PAD")) ? atoi(getenv("CAT_LDS_PAD")) : 0;
-  static const bool dbg_on = cat::kDiag && getenv("CAT_DBG");
-  static long long* dbg_buf = nullptr;
-  if (dbg_on) {
-    if (!dbg_buf) (void)hipMalloc(&dbg_buf, 64);
-    (void)hipMemsetAsync(dbg_buf, 0, 64, s);
-    a.dbg = dbg_buf;
-  }
-#define LAUNCH(MT, NT, WM, WN)                                                             \
-  {                                                                                        \
-    cat::ProfScope prof("conv_fwd_" #MT "x" #NT "x" #WM "x" #WN, prof_flops, 0.0, stream); \
-    const int grid = cdiv(a.M, WM * MT * 16) * cdiv(a.Cout, WN * NT * 16);                 \
-    /* the EX launches take neither the CAT_SCHED variants nor the CAT_LDS_PAD occupancy cap: those diagnostics cover the plain kernels only */ \
-    if (ex && !a.wvec) conv_fwd_kernel<MT, NT, WM, WN, false, 0, true><<<grid, 256, 0, s>>>(a); \
-    else if (ex) conv_fwd_kernel<MT, NT, WM, WN, true, 0, true><<<grid, 256, 0, s>>>(a);    \
-    else if (!a.wvec) conv_fwd_kernel<MT, NT, WM, WN, false, 0><<<grid, 256, 0, s>>>(a);    \
-    else if (WN == 2 && sched) launch_fwd_sched<cat::kDiag>(sched, grid, a, s);             \
-    else conv_fwd_kernel<MT, NT, WM, WN, true, 0><<<grid, 256, lds_pad, s>>>(a);            \
-  }
-  // BK = 32 path: per-tap K extent a multiple of 32 (allowing <= 12.5 % zero padding) and float4-readable filter rows
-  const bool bk32 = fwd_bk32_ok(a);   // a.c4 = walk_extent(cval): multiple of 16 when padding <= 12.5 %
-  a.ksplit = 1;
-  if (bk32 && ws) {
-    const SplitPlan sp = split_plan(a.M, a.Cout, (a.K + 31) >> 5);
-    a.ksplit = sp.ksplit;
-    a.kchunks = sp.kchunks;
-    a.part = (float*)ws;
-  }
-#define LAUNCH32(MT, NT, WM, WN)                                                                      \
-  {                                                                                                   \
-    cat::ProfScope prof(a.ksplit > 1 ? "conv_fwd32sk_" #MT "x" #NT "x" #WM "x" #WN : "conv_fwd32_" #MT "x" #NT "x" #WM "x" #WN, prof_flops, 0.0, \
-                        stream);                                                                      \
-    const dim3 grid(cdiv(a.M, WM * MT * 16) * cdiv(a.Cout, WN * NT * 16), a.ksplit);                   \
-    const size_t lds = (size_t)2 * (WM * MT * 16 + WN * NT * 16) * 32 * sizeof(float);                \
-    static cat::LdsOptIn optin, optin_ex;                                                             \
-    if (ex) {                                                                                         \
-      cat::lds_optin(optin_ex, (const void*)conv_fwd32_kernel<MT, NT, WM, WN, true>, (int)lds);       \
-      conv_fwd32_kernel<MT, NT, WM, WN, true><<<grid, 256, lds, s>>>(a);                               \
-    } else {                                                                                          \
-      cat::lds_optin(optin, (const void*)conv_fwd32_kernel<MT, NT, WM, WN>, (int)lds);                \
-      conv_fwd32_kernel<MT, NT, WM, WN><<<grid, 256, lds, s>>>(a);                                     \
-    }                                                                                                 \
-    if (a.ksplit > 1) launch_splitk_reduce(a.part, a.bias, a.out, a.M, a.Cout, a.cw, a.ycs, a.ksplit, a.act, a.slope, s);   \
-  }
-  // direct-to-LDS variant of the 128 x 128 tile: Cin % 32 == 0 (a chunk never straddles taps), no K split, 32-bit byte offsets
-  static const int fwd_direct = getenv("CAT_FWD_DIRECT") ? atoi(getenv("CAT_FWD_DIRECT")) : 1;
-  if (fwd_direct && bk32 && a.ksplit == 1 && a.Cout > 96 && (g->Cin & 31) == 0 && a.c4 == g->Cin && a.wcs >= g->Cin &&
-      fits_2gb((int64_t)g->N * g->H * g->W * g->xcs) && fits_2gb((int64_t)g->Cout * g->kh * g->kw * a.wcs)) {
-    cat::ProfScope prof("conv_fwd32d_4x4x2x2", prof_flops, 0.0, stream);
-    const int grid = cdiv(a.M, 128) * cdiv(a.Cout, 128);
-    const size_t lds = (size_t)2 * (128 + 128) * 32 * sizeof(float);
-    static cat::LdsOptIn optin, optin_ex;
-    if (ex) {
-      cat::lds_optin(optin_ex, (const void*)conv_fwd32d_kernel<true>, (int)lds);
-      conv_fwd32d_kernel<true><<<grid, 256, lds, s>>>(a);
-    } else {
-      cat::lds_optin(optin, (const void*)conv_fwd32d_kernel<false>, (int)lds);
-      conv_fwd32d_kernel<false><<<grid, 256, lds, s>>>(a);
-    }
-    return cat::check_launch("conv2d_fwd");
-  }
-  const bool smallm = use_small_m(a.M, a.Cout);
-  if (bk32) DISPATCH_TILE_N(a.Cout, smallm, LAUNCH32)
-  else DISPATCH_TILE_N(a.Cout, smallm, LAUNCH)
-#undef LAUNCH32
-  if (a.dbg) {
-    long long h[8];
-    (void)hipMemcpyAsync(h, dbg_buf, 64, hipMemcpyDeviceToHost, s);
-    (void)hipStreamSynchronize(s);
-    fprintf(stderr, "[cat dbg raw] %lld %lld %lld %lld %lld err=%s\n", h[0], h[1], h[2], h[3], h[4], hipGetErrorString(hipGetLastError()));
-    if (h[4] > 0)
-      fprintf(stderr, "[cat dbg] chunks=%lld  per chunk: gload %lld  ds_read+mfma %lld  wait+ds_write %lld  barrier %lld  (shader clocks)\n", h[4],
-              h[0] / h[4], h[1] / h[4], h[2] / h[4], h[3] / h[4]);
-  }
-#undef LAUNCH
-  return cat::check_launch("conv2d_fwd");
-}
+size_t cat_conv2d_dgrad_ws_bytes(const cat_conv_t* g, int dxcs) { return plan_dgrad(g, dxcs, true, false, false).ws_bytes; }
 
-static SplitPlan dgrad_split(const cat_conv_t* g) {
-  if (g->stride != 1) return SplitPlan{1, 0};
-  const bool refl = g->pad_mode == CAT_PAD_REFLECT;
-  const int Hin = refl ? g->H + 2 * g->pad : g->H, Win = refl ? g->W + 2 * g->pad : g->W;
-  const int c4 = walk_extent((g->Cout + 3) & ~3);
-  return split_plan(g->N * Hin * Win, g->Cin, (g->kh * g->kw * c4 + 15) >> 4);
-}
+// the transposed-filter tile is offered where a caller holding a workspace would still get the direct-to-LDS tile (no K split)
+int cat_conv2d_dgrad_t_applicable(const cat_conv_t* g) { return plan_dgrad(g, 0, true, true, false).t_ok ? 1 : 0; }
 
-size_t cat_conv2d_dgrad_ws_bytes(const cat_conv_t* g, int dxcs) {
-  if (g->N <= 0 || g->stride != 1) return 0;
-  const SplitPlan sp = dgrad_split(g);
-  if (sp.ksplit <= 1) return 0;
-  const bool refl = g->pad_mode == CAT_PAD_REFLECT;
-  const int Hin = refl ? g->H + 2 * g->pad : g->H, Win = refl ? g->W + 2 * g->pad : g->W;
-  return (size_t)sp.ksplit * g->N * Hin * Win * dxcs * sizeof(float);
+int cat_conv2d_weight_transpose(const cat_conv_t* g, const float* w, float* wt, cat_stream_t stream) {
+  const int wcs = weight_cs(g);
+  CAT_REQUIRE(g->Cin > 0 && g->Cout > 0 && wcs >= g->Cin, "weight transpose: bad geometry");
+  const dim3 grid(cdiv(g->Cin, 32), cdiv(g->Cout, 32), g->kh * g->kw);
+  weight_transpose_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(w, wt, g->Cout, g->Cin, g->kh * g->kw, wcs);
+  return cat::check_launch("weight_transpose");
 }
 
 static int conv_dgrad_impl(const cat_conv_t* g, const float* dy, const float* w, const float* wt, const float* bias, float* dx, int dxcs, int dxcw,
-                           void* ws, cat_stream_t stream);
+                           void* ws, cat_stream_t stream) {
+  IgemmArgs a{};
+  if (int e = fill_common(a, g)) return e;
+  const ConvPlan pl = plan_dgrad(g, dxcs, ws != nullptr, wt != nullptr, bias != nullptr);
+  a.a = dy; a.b = w; a.bt = wt; a.bias = bias; a.out = dx;
+  a.cval = pl.cval; a.c4 = pl.c4;
+  a.Hin = pl.Hin; a.Win = pl.Win; a.pad_eff = pl.pad_eff;
+  a.ksplit = pl.split; a.kchunks = pl.chunk; a.part = (float*)ws;
+  a.cw = dxcw > g->Cin ? dxcw : g->Cin;
+  a.ocs = dxcs;
+  CAT_REQUIRE(dxcs >= a.cw, "conv dgrad: dxcw > dxcs");
+  const int st = g->stride;
+  const int64_t P = (int64_t)g->N * pl.Hin * pl.Win;
+  hipStream_t s = (hipStream_t)stream;
+  zero_lanes_past_c4(dx, P, a.Cin, a.cw, a.ocs, s);
+  cat::ProfScope prof(pl.name, conv_flops(g), 0.0, stream);
+  const dim3 grid128(cdiv(pl.mmax, 128) * cdiv(a.Cin, 128), st * st);
+#define LAUNCH(MT, NT, WM, WN)                                                               \
+  {                                                                                          \
+    dim3 grid(cdiv(pl.mmax, WM * MT * 16) * cdiv(a.Cin, WN * NT * 16), st * st, pl.split);   \
+    conv_dgrad_kernel<MT, NT, WM, WN><<<grid, 256, 0, s>>>(a);                                \
+  }
+  switch (pl.kernel) {
+    case Kernel::Small: return cat::smallci_dgrad(g, dy, w, dx, dxcs, a.cw, s);
+    case Kernel::Direct32:
+      if (wt) launch_big_lds<conv_dgrad32d_kernel<true>>(grid128, kLds128, s, a);
+      else launch_big_lds<conv_dgrad32d_kernel<false>>(grid128, kLds128, s, a);
+      break;
+    case Kernel::Tile32: launch_big_lds<conv_dgrad32_kernel<4, 4, 2, 2>>(grid128, kLds128, s, a); break;
+    default: DISPATCH_TILE_N(a.Cin, pl.smallm, LAUNCH) break;
+  }
+#undef LAUNCH
+  if (pl.split > 1) launch_splitk_reduce((const float*)ws, bias, dx, P, a.Cin, a.cw, a.ocs, pl.split, a.act, a.slope, s);
+  return cat::check_launch("conv2d_dgrad");
+}
 
 int cat_conv2d_dgrad(const cat_conv_t* g, const float* dy, const float* w, const float* bias, float* dx, int dxcs, int dxcw,
                      cat_stream_t stream) {
@@ -1949,210 +2088,62 @@ int cat_conv2d_dgrad_ws(const cat_conv_t* g, const float* dy, const float* w, co
   return conv_dgrad_impl(g, dy, w, nullptr, bias, dx, dxcs, dxcw, ws, stream);
 }
 
-// does the direct-to-LDS dgrad tile apply (and with it the transposed-filter variant)?
-static bool dgrad32d_ok(const cat_conv_t* g) {
-  static const int on = getenv("CAT_DGRAD_DIRECT") ? atoi(getenv("CAT_DGRAD_DIRECT")) : 1;
-  const int wcs = g->wcs > 0 ? g->wcs : g->Cin;
-  return on && g->Cin > 96 && (wcs & 3) == 0 && g->Cout % 32 == 0 && g->Cin % 4 == 0 &&
-         fits_2gb((int64_t)g->N * g->Ho * g->Wo * g->ycs) && fits_2gb((int64_t)g->Cout * g->kh * g->kw * wcs);
-}
-
-int cat_conv2d_dgrad_t_applicable(const cat_conv_t* g) {
-  static const int on = getenv("CAT_DGRAD_T") ? atoi(getenv("CAT_DGRAD_T")) : 1;
-  return on && dgrad32d_ok(g) && g->stride >= 1 && dgrad_split(g).ksplit <= 1 ? 1 : 0;
-}
-
-int cat_conv2d_weight_transpose(const cat_conv_t* g, const float* w, float* wt, cat_stream_t stream) {
-  const int wcs = g->wcs > 0 ? g->wcs : g->Cin;
-  CAT_REQUIRE(g->Cin > 0 && g->Cout > 0 && wcs >= g->Cin, "weight transpose: bad geometry");
-  const dim3 grid(cdiv(g->Cin, 32), cdiv(g->Cout, 32), g->kh * g->kw);
-  weight_transpose_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(w, wt, g->Cout, g->Cin, g->kh * g->kw, wcs);
-  return cat::check_launch("weight_transpose");
-}
-
 int cat_conv2d_dgrad_t(const cat_conv_t* g, const float* dy, const float* w, const float* wt, const float* bias, float* dx, int dxcs, int dxcw,
                        cat_stream_t stream) {
   return conv_dgrad_impl(g, dy, w, wt, bias, dx, dxcs, dxcw, nullptr, stream);
 }
 
-static int conv_dgrad_impl(const cat_conv_t* g, const float* dy, const float* w, const float* wt, const float* bias, float* dx, int dxcs, int dxcw,
-                           void* ws, cat_stream_t stream) {
-  IgemmArgs a{};
-  if (int e = fill_common(a, g)) return e;
-  a.a = dy; a.b = w; a.bt = wt; a.bias = bias; a.out = dx;
-  a.cval = (g->Cout + 3) & ~3;
-  a.c4 = walk_extent(a.cval);
-  a.cw = dxcw > g->Cin ? dxcw : g->Cin;
-  a.ocs = dxcs;
-  CAT_REQUIRE(dxcs >= a.cw, "conv dgrad: dxcw > dxcs");
-  if (a.reflect) { a.Hin = g->H + 2 * g->pad; a.Win = g->W + 2 * g->pad; a.pad_eff = 0; }
-  else { a.Hin = g->H; a.Win = g->W; a.pad_eff = g->pad; }
-  const int st = g->stride;
-  const int mmax = g->N * cdiv(a.Hin, st) * cdiv(a.Win, st);
-  hipStream_t s = (hipStream_t)stream;
-  zero_lanes_past_c4(dx, (int64_t)g->N * a.Hin * a.Win, a.Cin, a.cw, a.ocs, s);
-  const double prof_flops = 2.0 * (double)g->N * g->Ho * g->Wo * g->Cout * g->kh * g->kw * g->Cin;
-  a.ksplit = 1;
-  if (ws) {
-    const SplitPlan sp = dgrad_split(g);
-    a.ksplit = sp.ksplit;
-    a.kchunks = sp.kchunks;
-    a.part = (float*)ws;
-  }
-#define LAUNCH(MT, NT, WM, WN)                                                             \
-  {                                                                                        \
-    cat::ProfScope prof(a.ksplit > 1 ? "conv_dgradsk_" #MT "x" #NT "x" #WM "x" #WN : "conv_dgrad_" #MT "x" #NT "x" #WM "x" #WN, prof_flops, 0.0, \
-                        stream);                                                           \
-    dim3 grid(cdiv(mmax, WM * MT * 16) * cdiv(a.Cin, WN * NT * 16), st * st, a.ksplit);    \
-    conv_dgrad_kernel<MT, NT, WM, WN><<<grid, 256, 0, s>>>(a);                              \
-    if (a.ksplit > 1)                                                                      \
-      launch_splitk_reduce(a.part, a.bias, a.out, (int64_t)g->N * a.Hin * a.Win, a.Cin, a.cw, a.ocs, a.ksplit, a.act, a.slope, s); \
-  }
-  if (a.ksplit == 1 && !bias && a.act == CAT_ACT_NONE && cat::smallci_dgrad_applicable(g)) {
-    cat::ProfScope prof("conv_dgrad_smallci", prof_flops, 0.0, stream);
-    return cat::smallci_dgrad(g, dy, w, dx, dxcs, a.cw, s);
-  }
-  // BK = 32 variant of the 128 x 128 tile (the discriminator's and the teacher's wide layers)
-  if (a.ksplit == 1 && dgrad32d_ok(g) && a.c4 == g->Cout) {
-    cat::ProfScope prof(wt ? "conv_dgrad32dt_4x4x2x2" : "conv_dgrad32d_4x4x2x2", prof_flops, 0.0, stream);
-    const dim3 grid(cdiv(mmax, 128) * cdiv(a.Cin, 128), st * st);
-    const size_t lds = (size_t)2 * (128 + 128) * 32 * sizeof(float);
-    static cat::LdsOptIn optin_d, optin_dt;
-    cat::lds_optin(optin_d, (const void*)conv_dgrad32d_kernel<false>, (int)lds);
-    cat::lds_optin(optin_dt, (const void*)conv_dgrad32d_kernel<true>, (int)lds);
-    if (wt) conv_dgrad32d_kernel<true><<<grid, 256, lds, s>>>(a);
-    else conv_dgrad32d_kernel<false><<<grid, 256, lds, s>>>(a);
-    return cat::check_launch("conv2d_dgrad");
-  }
-  if (a.ksplit == 1 && a.Cin > 96 && a.wvec && g->Cout % 16 == 0 && g->Cin % 4 == 0) {
-    cat::ProfScope prof("conv_dgrad32_4x4x2x2", prof_flops, 0.0, stream);
-    const dim3 grid(cdiv(mmax, 128) * cdiv(a.Cin, 128), st * st);
-    const size_t lds = (size_t)2 * (128 + 128) * 32 * sizeof(float);
-    static cat::LdsOptIn optin;
-    cat::lds_optin(optin, (const void*)conv_dgrad32_kernel<4, 4, 2, 2>, (int)lds);
-    conv_dgrad32_kernel<4, 4, 2, 2><<<grid, 256, lds, s>>>(a);
-    return cat::check_launch("conv2d_dgrad");
-  }
-  DISPATCH_TILE_N(a.Cin, use_small_m(mmax, a.Cin), LAUNCH)
-#undef LAUNCH
-  return cat::check_launch("conv2d_dgrad");
-}
+size_t cat_conv2d_wgrad_ws_bytes(const cat_conv_t* g) { return plan_wgrad(g).ws_bytes; }
 
-// direct-to-LDS wgrad (conv_wgrad32d_kernel): wide zero-padded layers whose 128-column K blocks lie inside one tap; returns the number
-// of output-row slices (0 = not applicable)
-static int wgrad32d_nsplit(const cat_conv_t* g, int* rows_per) {
-  static const int on = getenv("CAT_WGRAD_DIRECT") ? atoi(getenv("CAT_WGRAD_DIRECT")) : 1;
-  const int wcs = g->wcs > 0 ? g->wcs : g->Cin;
-  // (output rows that end in a partial 32-pixel segment are served: the segment's tail lanes are parked out of range)
-  if (!on || g->Cout <= 96 || (g->Cin & 127) || g->pad_mode != CAT_PAD_ZERO || cat::smallco_applicable(g) ||
-      !fits_2gb((int64_t)g->N * g->H * g->W * g->xcs) || !fits_2gb((int64_t)g->N * g->Ho * g->Wo * g->ycs) || wcs < g->Cin)
-    return 0;
-  const int tiles = cdiv(g->Cout, 128) * (g->kh * g->kw * g->Cin / 128);
-  const int R = g->N * g->Ho;
-  // workgroups aimed at: ONE resident round (256 CUs x 2).  Round 6, conv_bench on the three PatchGAN layers: 512 -> 2067 / 555 / 554 us, 1024 (two
-  // rounds, twice the partial-sum traffic) 2155 / 562 / 563, 768 / 1536 / 2048 slower still; with 512 tiles (conv4) the launch writes dw directly
-  int ns = cdiv(512, tiles);
-  if (ns > R) ns = R;
-  if (ns < 1) ns = 1;
-  const int rp = cdiv(R, ns);
-  if (rows_per) *rows_per = rp;
-  return cdiv(R, rp);
-}
+static int wgrad_reduce_blocks(const RedItem& r) { return (int)(((int64_t)r.Cout * r.taps * (r.c4 / 4) + 15) / 16); }
 
-size_t cat_conv2d_wgrad_ws_bytes(const cat_conv_t* g) {
-  if (const int nsd = wgrad32d_nsplit(g, nullptr)) return (size_t)nsd * g->Cout * g->kh * g->kw * ((g->Cin + 3) & ~3) * sizeof(float);
-  const WgradPlan pl = wgrad_plan(g);
-  const size_t K = (size_t)g->kh * g->kw * ((g->Cin + 3) & ~3);
-  if (cat::smallco_applicable(g)) return (size_t)cat::smallco_wgrad_nblk(g) * g->Cout * K * sizeof(float);
-  if (cat::twgrad_applicable(g)) return (size_t)cat::twgrad_nblk(g) * g->Cout * K * sizeof(float);
-  if (cat::pwgrad_applicable(g)) return (size_t)cat::pwgrad_nblk(g) * g->Cout * K * sizeof(float);
-  return (size_t)pl.nsplit * g->Cout * K * sizeof(float);
-}
-
-// one weight gradient; `defer` != nullptr: the partial sums stay in ws and *defer describes the reduction still owed (nsplit = 0: none, dw is
-// final) -- cat_conv2d_wgrad_batch reduces several of them with one launch
-static int reduce_or_defer(const RedItem& it, RedItem* defer, hipStream_t s) {
-  if (defer) {
-    *defer = it;
-    return 0;
-  }
-  const int64_t total = (int64_t)it.Cout * it.taps * (it.c4 / 4);
-  wgrad_reduce_kernel<<<(int)((total + 15) / 16), 256, 0, s>>>(it.ws, it.dw, it.nsplit, it.Cout, it.taps, it.wlim, it.wcs, it.c4, it.K, it.accumulate);
-  return cat::check_launch("conv2d_wgrad_reduce");
-}
-
+// One weight gradient.  `defer` != nullptr: the partial sums stay in ws, defer->red describes the reduction still owed (nsplit = 0: none, dw is
+// final) and defer->ws_bytes what the plan asked of ws -- cat_conv2d_wgrad_batch reduces several of them with one launch.
+struct WgradDeferred { RedItem red; size_t ws_bytes; };
 static int wgrad_impl(const cat_conv_t* g, const float* x, const float* dy, float* dw, int accumulate, void* ws, cat_stream_t stream,
-                      RedItem* defer) {
-  if (defer) defer->nsplit = 0;
+                      WgradDeferred* defer) {
+  if (defer) defer->red.nsplit = 0;
   IgemmArgs a{};
   if (int e = fill_common(a, g)) return e;
-  const WgradPlan pl = wgrad_plan(g);
   CAT_REQUIRE((int64_t)g->N * g->H * g->W * g->xcs < (int64_t)4294967295LL, "conv wgrad: activation larger than 2^32 elements");
+  const ConvPlan pl = plan_wgrad(g);
+  if (defer) defer->ws_bytes = pl.ws_bytes;
+  CAT_REQUIRE(pl.direct || ws != nullptr, "conv wgrad: workspace required");
   a.a = x; a.b = dy;
-  a.c4 = (g->Cin + 3) & ~3;
+  a.c4 = pl.c4;
   a.cval = a.wcs >= a.c4 ? a.c4 : g->Cin;   // channels written per tap
-  a.K = g->kh * g->kw * a.c4;
-  a.nsplit = pl.nsplit; a.mchunk = pl.mchunk;
-  a.direct = pl.nsplit == 1 ? 1 : 0;
+  a.K = pl.K;
+  a.nsplit = pl.split; a.mchunk = pl.chunk;
+  a.direct = pl.direct ? 1 : 0;
   a.accumulate = accumulate;
-  a.out = a.direct ? dw : (float*)ws;
+  a.out = pl.direct ? dw : (float*)ws;
   hipStream_t s = (hipStream_t)stream;
-  if (cat::smallco_applicable(g)) {
-    CAT_REQUIRE(ws != nullptr, "conv wgrad: workspace required");
-    const double fl = 2.0 * (double)g->N * g->Ho * g->Wo * g->Cout * g->kh * g->kw * g->Cin;
-    cat::ProfScope prof("conv_wgrad_smallco", fl, 0.0, stream);
-    if (int e = cat::smallco_wgrad(g, x, dy, (float*)ws, s)) return e;
-    return reduce_or_defer(RedItem{(const float*)ws, dw, cat::smallco_wgrad_nblk(g), a.Cout, a.kh * a.kw, a.cval, a.wcs, a.c4, a.K, accumulate}, defer, s);
+  cat::ProfScope prof(pl.name, conv_flops(g), 0.0, stream);
+#define WGRAD_TILE_LAUNCH(NMAX, MT, NT, WM, WN, ...)                                                                              \
+  if (a.Cout <= NMAX)                                                                                                             \
+    conv_wgrad_kernel<MT, NT, WM, WN><<<dim3(cdiv(a.Cout, WM * MT * 16) * cdiv(a.K, WN * NT * 16), pl.split), 256, 0, s>>>(a);     \
+  else
+  int e = 0;
+  switch (pl.kernel) {
+    case Kernel::Small: e = cat::smallco_wgrad(g, x, dy, (float*)ws, s); break;
+    case Kernel::LdsTile: e = cat::twgrad(g, x, dy, (float*)ws, s); break;
+    case Kernel::PixelStream: e = cat::pwgrad(g, x, dy, (float*)ws, s); break;
+    case Kernel::Direct32:
+      launch_big_lds<conv_wgrad32d_kernel>(dim3(cdiv(a.Cout, 128) * (a.K / 128), pl.split), (size_t)2 * 2 * 32 * 128 * sizeof(float), s, a,
+                                           pl.chunk, cdiv(g->Wo, 32));
+      e = cat::check_launch("conv2d_wgrad");
+      break;
+    default:
+      WGRAD_TILES(WGRAD_TILE_LAUNCH, ) {}
+      e = cat::check_launch("conv2d_wgrad");
+      break;
   }
-  const double prof_flops = 2.0 * (double)g->N * g->Ho * g->Wo * g->Cout * g->kh * g->kw * g->Cin;
-  if (cat::twgrad_applicable(g)) {
-    CAT_REQUIRE(ws != nullptr, "conv wgrad: workspace required");
-    cat::ProfScope prof("conv_twgrad", prof_flops, 0.0, stream);
-    if (int e = cat::twgrad(g, x, dy, (float*)ws, s)) return e;
-    return reduce_or_defer(RedItem{(const float*)ws, dw, cat::twgrad_nblk(g), a.Cout, a.kh * a.kw, a.cval, a.wcs, a.c4, a.K, accumulate}, defer, s);
-  }
-  if (cat::pwgrad_applicable(g)) {
-    CAT_REQUIRE(ws != nullptr, "conv wgrad: workspace required");
-    cat::ProfScope prof("conv_pwgrad", prof_flops, 0.0, stream);
-    if (int e = cat::pwgrad(g, x, dy, (float*)ws, s)) return e;
-    return reduce_or_defer(RedItem{(const float*)ws, dw, cat::pwgrad_nblk(g), a.Cout, 1, a.cval, a.wcs, a.c4, a.K, accumulate}, defer, s);
-  }
-  int rows_per = 0;
-  if (const int nsd = wgrad32d_nsplit(g, &rows_per)) {
-    CAT_REQUIRE(nsd == 1 || ws != nullptr, "conv wgrad: workspace required");
-    a.nsplit = nsd;
-    a.direct = nsd == 1 ? 1 : 0;
-    a.out = a.direct ? dw : (float*)ws;
-    {
-      cat::ProfScope prof("conv_wgrad32d_4x4x2x2", prof_flops, 0.0, stream);
-      const dim3 grid(cdiv(a.Cout, 128) * (a.K / 128), nsd);
-      const size_t lds = (size_t)2 * 2 * 32 * 128 * sizeof(float);
-      static cat::LdsOptIn optin_w;
-      cat::lds_optin(optin_w, (const void*)conv_wgrad32d_kernel, (int)lds);
-      conv_wgrad32d_kernel<<<grid, 256, lds, s>>>(a, rows_per, cdiv(g->Wo, 32));
-    }
-    if (int e = cat::check_launch("conv2d_wgrad")) return e;
-    if (!a.direct) {
-      return reduce_or_defer(RedItem{(const float*)ws, dw, nsd, a.Cout, a.kh * a.kw, a.cval, a.wcs, a.c4, a.K, accumulate}, defer, s);
-    }
-    return 0;
-  }
-  CAT_REQUIRE(a.direct || ws != nullptr, "conv wgrad: workspace required");
-#define LAUNCH(MT, NT, WM, WN)                                                                         \
-  {                                                                                                    \
-    cat::ProfScope prof("conv_wgrad_" #MT "x" #NT "x" #WM "x" #WN, prof_flops, 0.0, stream); \
-    dim3 grid(cdiv(a.Cout, WM * MT * 16) * cdiv(a.K, WN * NT * 16), pl.nsplit);                        \
-    conv_wgrad_kernel<MT, NT, WM, WN><<<grid, 256, 0, s>>>(a);                                          \
-  }
-#define WGRAD_TILE_LAUNCH(NMAX, MT, NT, WM, WN, ...) if (a.Cout <= NMAX) LAUNCH(MT, NT, WM, WN) else
-  WGRAD_TILES(WGRAD_TILE_LAUNCH, ) {}
 #undef WGRAD_TILE_LAUNCH
-#undef LAUNCH
-  if (int e = cat::check_launch("conv2d_wgrad")) return e;
-  if (!a.direct) {
-    return reduce_or_defer(RedItem{(const float*)ws, dw, pl.nsplit, a.Cout, a.kh * a.kw, a.cval, a.wcs, a.c4, a.K, accumulate}, defer, s);
-  }
-  return 0;
+  if (e || pl.direct) return e;
+  const RedItem red{(const float*)ws, dw, pl.split, a.Cout, a.kh * a.kw, a.cval, a.wcs, a.c4, a.K, accumulate};
+  if (defer) defer->red = red;
+  else wgrad_reduce_kernel<<<wgrad_reduce_blocks(red), 256, 0, s>>>(red.ws, red.dw, red.nsplit, red.Cout, red.taps, red.wlim, red.wcs, red.c4, red.K, red.accumulate);
+  return cat::check_launch("conv2d_wgrad_reduce");
 }
 
 int cat_conv2d_wgrad(const cat_conv_t* g, const float* x, const float* dy, float* dw, int accumulate, void* ws,
@@ -2160,9 +2151,12 @@ int cat_conv2d_wgrad(const cat_conv_t* g, const float* x, const float* dy, float
   return wgrad_impl(g, x, dy, dw, accumulate, ws, stream, nullptr);
 }
 
+// every item's part of the batch workspace starts on a 256-byte boundary
+static size_t wgrad_batch_slot(size_t ws_bytes) { return (ws_bytes + 255) & ~(size_t)255; }
+
 size_t cat_conv2d_wgrad_batch_ws_bytes(const cat_wgrad_item_t* items, int n) {
   size_t total = 0;
-  for (int i = 0; i < n; ++i) total += (cat_conv2d_wgrad_ws_bytes(&items[i].g) + 255) & ~(size_t)255;
+  for (int i = 0; i < n; ++i) total += wgrad_batch_slot(plan_wgrad(&items[i].g).ws_bytes);
   return total;
 }
 
@@ -2173,14 +2167,13 @@ int cat_conv2d_wgrad_batch(const cat_wgrad_item_t* items, int n, void* ws, cat_s
   size_t off = 0;
   int blocks = 0;
   for (int i = 0; i < n; ++i) {
-    RedItem it{};
-    if (int e = wgrad_impl(&items[i].g, items[i].x, items[i].dy, items[i].dw, items[i].accumulate, (char*)ws + off, stream, &it)) return e;
-    off += (cat_conv2d_wgrad_ws_bytes(&items[i].g) + 255) & ~(size_t)255;
-    if (it.nsplit > 0) {
-      many.it[many.n] = it;
+    WgradDeferred d{};
+    if (int e = wgrad_impl(&items[i].g, items[i].x, items[i].dy, items[i].dw, items[i].accumulate, (char*)ws + off, stream, &d)) return e;
+    off += wgrad_batch_slot(d.ws_bytes);
+    if (d.red.nsplit > 0) {
+      many.it[many.n] = d.red;
       many.start[many.n] = blocks;
-      const int64_t total = (int64_t)it.Cout * it.taps * (it.c4 / 4);
-      blocks += (int)((total + 15) / 16);
+      blocks += wgrad_reduce_blocks(d.red);
       ++many.n;
     }
   }

@@ -3,7 +3,7 @@ layout -- ops.padded_weight_like storage, wcs = round_up(Cin, 4) -- against floa
 kernel test checks: channel-slice output writes (ycw / dxcw below the pixel stride) and accumulate = 1 of the weight gradient.
 
 A (host): the ROW(...) lines of CONV_TILES / WGRAD_TILES are parsed from the source text; the profiler family names the dispatch can emit
-          must equal the keys of VARIANT_CASES plus the capped UNREACHABLE table, so a new tile row without a parity case fails without a GPU.
+          must equal the keys of VARIANT_CASES exactly, so a new tile row without a parity case fails without a GPU.
 B (GPU):  one Conv2dFn forward + backward per case with the profiler on and NaNs in the cached workspace; the family the case stands for must
           have been recorded exactly once (a moved dispatch fails the case instead of silently testing another kernel), then y / dx / dw / db
           parity at TOL.
@@ -133,23 +133,8 @@ WGRAD_FORMS = {
 TW_CASES = {1: (42, 7, 5, 1, 2, 1, 0, 2, 64, 64), 2: (3, 35, 5, 1, 2, 1, 0, 2, 64, 64), 3: (42, 7, 3, 1, 1, 0, 0, 2, 64, 64), 4: (3, 35, 3, 1, 1, 0, 0, 2, 64, 64), 5: (42, 17, 3, 1, 1, 0, 0, 2, 64, 64), 6: (20, 35, 3, 1, 1, 0, 0, 2, 64, 64)}
 PW_CASES = {'cout_le_64': (8, 8, 1, 1, 0, 0, 0, 3, 256, 256), 'cout_gt_64': (3, 77, 1, 1, 0, 0, 0, 2, 64, 64)}
 
-# Instantiations the dispatch compiles but cannot reach (dead code, left in place): name -> why.
-_NO_SMALL_M = 'small-M tile of a row wider than 32: use_small_m() returns false for n > 32, so the MTS branch is never taken'
-_NO_SPLIT = 'a K split needs fewer than 128 tiles, the full-M tile of a 16 / 32-wide row at least 768 M tiles'
-UNREACHABLE = {
-    'conv_fwd_1x3x4x1': _NO_SMALL_M, 'conv_fwd_1x4x4x1': _NO_SMALL_M, 'conv_fwd_1x6x4x1': _NO_SMALL_M,
-    'conv_fwd32_1x3x4x1': _NO_SMALL_M, 'conv_fwd32_1x4x4x1': _NO_SMALL_M, 'conv_fwd32_1x6x4x1': _NO_SMALL_M,
-    'conv_fwd32sk_1x3x4x1': _NO_SMALL_M, 'conv_fwd32sk_1x4x4x1': _NO_SMALL_M, 'conv_fwd32sk_1x6x4x1': _NO_SMALL_M,
-    'conv_dgrad_1x3x4x1': _NO_SMALL_M, 'conv_dgrad_1x4x4x1': _NO_SMALL_M, 'conv_dgrad_1x6x4x1': _NO_SMALL_M,
-    'conv_dgradsk_1x3x4x1': _NO_SMALL_M, 'conv_dgradsk_1x4x4x1': _NO_SMALL_M, 'conv_dgradsk_1x6x4x1': _NO_SMALL_M,
-    'conv_fwd32sk_4x1x4x1': _NO_SPLIT, 'conv_fwd32sk_4x2x4x1': _NO_SPLIT, 'conv_dgradsk_4x1x4x1': _NO_SPLIT, 'conv_dgradsk_4x2x4x1': _NO_SPLIT,
-}
-# the cap: nothing else may ever be declared unreachable
-UNREACHABLE_ALLOWED = frozenset(p + t for p in ('conv_fwd_', 'conv_fwd32_', 'conv_fwd32sk_', 'conv_dgrad_', 'conv_dgradsk_')
-                                for t in ('1x3x4x1', '1x4x4x1', '1x6x4x1')) | \
-    frozenset(('conv_fwd32sk_4x1x4x1', 'conv_fwd32sk_4x2x4x1', 'conv_dgradsk_4x1x4x1', 'conv_dgradsk_4x2x4x1'))
-
 CONV_PREFIXES = ('conv_fwd_', 'conv_fwd32_', 'conv_fwd32sk_', 'conv_dgrad_', 'conv_dgradsk_')
+SPLIT_PREFIXES = ('conv_fwd32sk_', 'conv_dgradsk_')
 FIXED_NAMES = ('conv_fwd32d_4x4x2x2', 'conv_dgrad32_4x4x2x2', 'conv_dgrad32d_4x4x2x2', 'conv_dgrad32dt_4x4x2x2', 'conv_wgrad32d_4x4x2x2',
                'conv_fwd_smallco', 'conv_wgrad_smallco', 'conv_dgrad_smallci', 'conv_twgrad', 'conv_pwgrad')
 
@@ -177,8 +162,11 @@ def _rows(text, macro):
 def _derived_names(text):
     conv, wgrad = set(), set()
     for nmax, mt, mts, nt, wm, wn in _rows(text, 'CONV_TILES'):
-        for m in (mt, mts):      # both branches of CONV_TILE_LAUNCH are instantiated for every row
-            conv |= {'%s%dx%dx%dx%d' % (p, m, nt, wm, wn) for p in CONV_PREFIXES}
+        conv |= {'%s%dx%dx%dx%d' % (p, mts, nt, wm, wn) for p in CONV_PREFIXES}
+        if mts != mt:
+            # A row with a small-M tile of its own (the 16 / 32-wide rows) also launches its full-M tile, but never split: a K split needs
+            # fewer than 128 tiles, and use_small_m() leaves the small-M tile only at 768 or more M tiles of the full-M size.
+            conv |= {'%s%dx%dx%dx%d' % (p, mt, nt, wm, wn) for p in CONV_PREFIXES if p not in SPLIT_PREFIXES}
     for nmax, mt, nt, wm, wn in _rows(text, 'WGRAD_TILES'):
         wgrad.add('conv_wgrad_%dx%dx%dx%d' % (mt, nt, wm, wn))
     return conv, wgrad
@@ -207,13 +195,11 @@ def test_variant_table_covers_the_tile_tables():
     text = open(IGEMM_SRC).read()
     conv, wgrad = _derived_names(text)
     derived = conv | wgrad | set(FIXED_NAMES)
-    assert set(UNREACHABLE) <= UNREACHABLE_ALLOWED, sorted(set(UNREACHABLE) - UNREACHABLE_ALLOWED)
-    assert not set(UNREACHABLE) & set(VARIANT_CASES)
-    have = set(VARIANT_CASES) | set(UNREACHABLE)
+    have = set(VARIANT_CASES)
     assert derived == have, (sorted(derived - have), sorted(have - derived))
     assert all(len(v) >= 1 for v in VARIANT_CASES.values())
     # every generic tile also has a case with Cin % 4 != 0 on an odd plane (the edges where the masks matter)
-    for name in sorted((conv | wgrad) - set(UNREACHABLE)):
+    for name in sorted(conv | wgrad):
         assert any(_ragged(c) for c in VARIANT_CASES[name]), name
     # both forms of every weight-gradient tile, the six LDS-tile instantiations, both accumulator widths of the pixel-streaming kernel
     assert set(WGRAD_FORMS) == wgrad | {'conv_wgrad32d_4x4x2x2'}
