@@ -166,16 +166,24 @@ class BaseInceptionDistiller(host.StepHost):
         -> (segments, slices) or None.  `segments`: the PatchGAN's layer list split in front of its two widest convolutions (pix2pix D:
         [conv1 .. bn2 act | conv3 bn3 act | conv4 bn4 act conv5]); `slices`: per segment the (lo, hi) float range its parameters occupy in
         optimizer_D's flat gradient buffer.  The last segment (the 512 -> 1024 conv: 8.4 M of 11 M parameters) is differentiated first."""
+        flat = self.optimizer_D._ensure_flat() if hasattr(self.optimizer_D, '_ensure_flat') else None
+        # the slices are float ranges of optimizer_D's flat gradient buffer and stages 0 / 1 differentiate with torch.autograd.grad, which
+        # drops what a node returns for a parameter: the cut is valid only while EVERY discriminator parameter's gradient sink is its span
+        # of that very buffer.  An optimizer rebuilt over the same parameters (a second FusedAdam re-flattens and re-adopts them) or a
+        # re-flattened optimizer_D changes the key; a parameter whose sink lies elsewhere makes the plan None (plain backward_D)
+        f0 = flat[0] if flat is not None and len(flat) == 1 else None
+        mods = getattr(self.netD, 'model', None)
+        # (the staged forward calls the layers of netD.model itself: a hook on netD, on netD.model or on a layer would be bypassed)
+        hooked = any(m._forward_hooks or m._forward_pre_hooks for m in [self.netD] + ([mods] + list(mods) if isinstance(mods, cnn.FusedSequential) else []))
+        key = (id(self.netD), id(self.optimizer_D), id(f0), None if f0 is None else tuple(f0['offs']), hooked,
+               tuple(q._cat_grad_view.data_ptr() if getattr(q, '_cat_grad_view', None) is not None else None for q in self.netD.parameters()))
         cached = self.__dict__.get('_d_stage_plan')
-        if cached is not None and cached[0] is self.netD:
-            return cached[1]
+        if cached is not None and cached[0] == key:
+            return cached[2]
         plan = None
         from ..discriminators import NLayerDiscriminator
-        from .. import nn as cnn
-        mods = getattr(self.netD, 'model', None)
-        flat = self.optimizer_D._ensure_flat() if hasattr(self.optimizer_D, '_ensure_flat') else None
         if isinstance(self.netD, NLayerDiscriminator) and isinstance(mods, cnn.FusedSequential) and flat is not None and len(flat) == 1 and \
-                flat[0] is not None and not any(m._forward_hooks or m._forward_pre_hooks for m in mods):
+                flat[0] is not None and not hooked:
             convs = [i for i, m in enumerate(mods) if isinstance(m, cnn.Conv2d)]
             if len(convs) >= 4:
                 order = sorted(convs[1:], key=lambda i: -mods[i].weight.numel())[:2]      # the two widest convs that are not the first layer
@@ -191,9 +199,11 @@ class BaseInceptionDistiller(host.StepHost):
                     slices.append((lo, hi))
                     pos = hi
                 dparams = list(self.netD.parameters())
-                if ok and pos == f['n'] and len(dparams) == len(f['params']) and all(a is b for a, b in zip(dparams, f['params'])):
+                sunk = all(getattr(q, '_cat_grad_view', None) is not None and q._cat_grad_view.data_ptr() == f['g'].data_ptr() + 4 * o
+                           for q, o in zip(f['params'], f['offs']))
+                if ok and sunk and pos == f['n'] and len(dparams) == len(f['params']) and all(a is b for a, b in zip(dparams, f['params'])):
                     plan = (segments, slices)
-        self.__dict__['_d_stage_plan'] = (self.netD, plan)
+        self.__dict__['_d_stage_plan'] = (key, (self.netD, self.optimizer_D, f0), plan)      # (the objects: their ids stay unique)
         return plan
 
     def backward_D_stages(self):

@@ -396,6 +396,8 @@ def slices(pairs):
     for i, (c0, c, bn) in enumerate(pairs):
         arr[i].c0, arr[i].c = c0, c
         track = isinstance(bn, cnn.BatchNorm2d) and bn.training and bn.track_running_stats
+        if track:      # the finalize kernel this table goes to updates them in place: the folds derived from them re-fold (optim.weights_key)
+            optim.note_stats_written(bn.running_mean, bn.running_var)
         arr[i].running_mean = bn.running_mean.data_ptr() if track else None
         arr[i].running_var = bn.running_var.data_ptr() if track else None
         arr[i].num_batches = bn.num_batches_tracked.data_ptr() if track and not isinstance(bn, cnn.SynchronizedBatchNorm2d) else None

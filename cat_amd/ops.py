@@ -725,6 +725,7 @@ class NormActFn(torch.autograd.Function):
                    (n // groups) * h * w, cs, act, slope, _stream())
         else:
             ws = workspace(L.query('cat_norm_ws_bytes', C.byref(g)), x.device)
+            optim.note_stats_written(running_mean, running_var)
             L.call('cat_norm_fwd', C.byref(g), _p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), _p(running_mean), _p(running_var),
                    _p(num_batches), _p(ws), _stream())
         ctx.geom = (n, h * w, c, cs, mode, eps, momentum, act, slope)
@@ -767,6 +768,7 @@ def norm_from_tiles(tiles, n, c, groups, gamma, beta, running_mean, running_var,
     sl = (L.NSlice * 1)()
     sl[0].c0, sl[0].c = 0, c
     if running_mean is not None:
+        optim.note_stats_written(running_mean, running_var)
         sl[0].running_mean, sl[0].running_var = running_mean.data_ptr(), running_var.data_ptr()
         if num_batches is not None:
             sl[0].num_batches = num_batches.data_ptr()
@@ -1140,6 +1142,7 @@ def _bn_forward_stats(x, rm, rv, eps, momentum, gamma, beta, want_affine):
     stats = torch.empty((4 + (2 if want_affine else 0), cs), device=dev, dtype=torch.float32)
     mean, rstd, a, b = stats[0], stats[1], stats[2], stats[3]
     scale, shift = (stats[4], stats[5]) if want_affine else (None, None)
+    optim.note_stats_written(rm, rv)
     L.call('cat_bn_finalize', _p(sums), float(count), c, cs, eps, 1 if sync is not None else 0, momentum, _p(gamma), _p(beta), _p(mean),
            _p(rstd), _p(rm), _p(rv), _p(a), _p(b), _p(scale), _p(shift), st)
     return a, b, scale, shift, count, sync

@@ -40,9 +40,37 @@ def epoch_of(tensors):
     return _WEIGHTS_EPOCH if any(owned(t) for t in tensors if t is not None) else -1
 
 
+# BatchNorm running statistics are a third kind of change: the norm kernels of a train-mode forward write them through raw pointers, with
+# no optimizer step anywhere near (a forward-only pass, a net without an optimizer, an evaluation between two steps), so neither
+# `_version` nor the weights epoch sees it.  Every wrapper that hands a running-statistics pointer to a kernel calls note_stats_written()
+# on those buffers; the count lives on the buffer itself and only weights_key() -- the key of the conv+BN / block / unit FOLDS, the only
+# operands derived from statistics -- reads it.  Filter packs and transposed filters key on epoch_of() alone: a train-mode norm forward
+# between two uses of a discriminator never refreshes a weight pack.  Host-only: no launch.
+# PRECONDITION: the count is a Python attribute, so a captured-graph REPLAY of a train-mode norm does not advance it.  The folds of a
+# replayed net stay fresh only because the norm's weight and bias are FusedAdam-owned and note_graph_replay advances the epoch in their
+# key; every graphed step here is of that kind.  Replaying train-mode norms whose parameters no FusedAdam owns (a BatchNorm without an
+# optimizer inside a captured step) would leave their eval folds stale: whoever adds such a replay must call note_stats_written on
+# those buffers after it.
+def note_stats_written(*buffers):
+    """A kernel is about to update these running-statistics buffers (None entries allowed) in place."""
+    for t in buffers:
+        if t is not None:
+            t._cat_stat_writes = getattr(t, '_cat_stat_writes', 0) + 1
+
+
+def stat_writes(t):
+    return getattr(t, '_cat_stat_writes', 0)
+
+
+def _tensor_key(t):
+    writes = stat_writes(t)
+    return (t.data_ptr(), t._version, writes) if writes else (t.data_ptr(), t._version)
+
+
 def weights_key(tensors):
-    """Cache key of an operand derived from `tensors` (None entries allowed): changes when any of them moved or changed value."""
-    return (tuple((t.data_ptr(), t._version) if t is not None else None for t in tensors), epoch_of(tensors))
+    """Cache key of an operand derived from `tensors` (None entries allowed): changes when any of them moved or changed value -- by an
+    ordinary in-place update (version), an optimizer step on an owned tensor (epoch), or a norm kernel's statistics update (stat_writes)."""
+    return (tuple(_tensor_key(t) if t is not None else None for t in tensors), epoch_of(tensors))
 
 
 def _adopt(p, view):

@@ -689,3 +689,96 @@ def test_layer_cache_follows_weight_and_tile_rule(dev, kind):
         _note('layer_cache', ratio, (kind, rule))
         assert ratio <= 1.0, (kind, rule, ratio)
     assert cells == [16, 8, 8, 16]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('column', ['adam_step', 'storage_move', 'data_swap'])
+def test_layer_streams_follow_optimizer_steps_and_storage_moves(dev, column):
+    """qconv.Layer's packed stream under the ways a TRAINED weight changes (test_layer_cache_follows_weight_and_tile_rule covers copy_): an
+    eager FusedAdam.step after a real backward (raw pointers, no version bump: the optimizer epoch is the key), the storage move of
+    FusedAdam's first zero_grad AFTER the layer has run (then a step), and `weight.data = new_tensor`.  The smallest stem16 case.  After the
+    change the same Layer must give (a) bit for bit what a Layer that never ran gives on a copy of the new weight, (b) the fp64 result for
+    the new weight within this file's element bar, (c) which the fp64 result for the old weight misses by > 100 bars (upper quartile over the elements); (d) one more
+    run re-packs nothing."""
+    from cat_amd import _lib as L
+    from cat_amd import ops, qconv
+    from cat_amd.optim import FusedAdam
+    case = FEATURE_CASES['stem16'][0]
+    la = _case_launch(case)
+    sg = la.segs[0]
+    pad, mode = -sg.oy, (L.PAD_REFLECT if sg.reflect else L.PAD_ZERO)
+    w0 = ops.padded_weight_like(sg.w.shape, dev)
+    w0.copy_(sg.w)
+    weight, bias = torch.nn.Parameter(w0), torch.nn.Parameter(la.bias.to(dev))
+    layer = qconv.Layer('conv', weight, stride=la.stride, pad=pad, reflect=bool(sg.reflect))
+    xd = ops.to_nhwc(sg.x.to(dev))
+    gy = ops.to_nhwc(detfill.normal((la.n, la.nn, la.ho, la.wo), 98).to(dev))
+    packs = []
+    real_call = L.call
+
+    def counting(name, *args):
+        if name == 'cat_qconv_pack':
+            packs.append(name)
+        return real_call(name, *args)
+
+    def run(lay, b):
+        out = ops.empty_act(la.n, la.nn, la.ho, la.wo, dev)
+        with _tile_rule(la.rule):
+            lay.run(xd, b.detach(), out, act=la.act, slope=la.slope)
+            torch.cuda.synchronize()
+        return out.cpu().double()
+
+    def step(opt):
+        """one training step of the layer the way nn._conv_norm_q drives it: forward on the quad-granule kernel, the general backward"""
+        opt.zero_grad()
+        with _tile_rule(la.rule):
+            y = ops.Conv2dFn.apply(xd, weight, bias, la.stride, pad, mode, L.ACT_NONE, 0.0, {'layer': layer, 'stats': False})
+            y.backward(gy)
+        opt.step()
+
+    def want(wt, b):
+        return _reference(Launch([Sg(sg.x, wt, sg.oy, sg.ox, sg.reflect)], la.ho, la.wo, la.rule, stride=la.stride, bias=b, act=la.act, slope=la.slope))
+
+    make = lambda: FusedAdam([weight, bias], lr=0.5, betas=(0.5, 0.999))
+    if column == 'adam_step':
+        opt = make()
+        opt.zero_grad()
+        y0 = run(layer, bias)
+        step(opt)
+    elif column == 'storage_move':
+        y0 = run(layer, bias)                       # the first use is BEFORE the optimizer re-houses the weight
+        ptr = weight.data_ptr()
+        opt = make()
+        opt.zero_grad()
+        assert weight.data_ptr() != ptr and weight._cat_grad_view is not None
+        step(opt)
+    else:
+        y0 = run(layer, bias)
+        new = ops.padded_weight_like(sg.w.shape, dev)
+        new.copy_(detfill.normal(tuple(sg.w.shape), 99, float(sg.w.std())))
+        version = weight._version
+        weight.data = new
+        assert weight._version == version
+    torch.cuda.synchronize()
+    w1, b1 = weight.detach().cpu().clone().contiguous(), bias.detach().cpu().clone()
+    _, r0, bar0 = want(sg.w, la.bias)
+    assert float(((y0 - r0).abs() / bar0).max()) <= 1.0
+    L.call = counting
+    try:
+        warm = run(layer, bias)
+        assert len(packs) == 1                                                   # re-packed once
+        _, r1, bar = want(w1, b1)
+        ratio = float(((warm - r1).abs() / bar).max())
+        sep = float(torch.quantile(((r0 - r1).abs() / bar).reshape(-1), 0.75))
+        _note('layer_cache', ratio, (column,))
+        print('qconv.Layer %s: warm vs fp64(W1) %.3g of the bar; (c) upper-quartile separation %.3g bars' % (column, ratio, sep))
+        assert ratio <= 1.0, (column, ratio)                                      # (b)
+        assert sep > 100.0, (column, sep)                                         # (c)
+        stream = layer._pk[1]
+        assert torch.equal(run(layer, bias), warm) and layer._pk[1] is stream and len(packs) == 1      # (d)
+    finally:
+        L.call = real_call
+    wc = ops.padded_weight_like(sg.w.shape, dev)
+    wc.copy_(w1)
+    cold = qconv.Layer('conv', wc, stride=la.stride, pad=pad, reflect=bool(sg.reflect))
+    assert torch.equal(run(cold, b1.to(dev)), warm)                               # (a)
