@@ -24,22 +24,17 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from . import derived
 from . import nn as cnn
 from . import ops
 from . import optim
 
 
+FROZEN = derived.slot('_cat_frozen')      # R5: the block's plan, keyed on every parameter and buffer of the block
 _STAGE1W = True      # stage 1 of the block as one launch (cat_tstage1w_fwd); A/B closed in round 6: teacher forward 11.51 -> 11.15 ms
 
 
-def _affine(bn):
-    scale = torch.rsqrt(bn.running_var + bn.eps)
-    if bn.weight is not None:
-        scale = scale * bn.weight
-    shift = -bn.running_mean * scale
-    if bn.bias is not None:
-        shift = shift + bn.bias
-    return scale, shift
+_affine = cnn.bn_affine
 
 
 def _foldable(bn):
@@ -61,23 +56,13 @@ def applicable(block, x):
     return len(block.dw_ops) + sum(1 for op in block.res_ops if op[1][0].kernel_size[0] == 1) >= 2
 
 
-def _tensors(block):
-    out = []
-    for m in block.modules():
-        for t in list(m._parameters.values()) + list(m._buffers.values()):
-            if t is not None:
-                out.append(t)
-    return out
-
-
 def _plan(block):
-    tensors = _tensors(block)
     # weights owned by a FusedAdam change under torch's feet (raw-pointer kernels): such blocks -- a BatchNorm student run in eval mode by
     # evaluate_model between training steps -- re-fold after every optimizer step; the frozen teacher (no optimizer) folds once
-    key = optim.weights_key(tensors)
-    cached = getattr(block, '_cat_frozen', None)
-    if cached is not None and cached['key'] == key:
-        return cached
+    return derived.lookup(block, FROZEN, optim.weights_key(list(block.parameters()) + list(block.buffers())), lambda prev: _build_plan(block))
+
+
+def _build_plan(block):
     dev = block.pw_bn.running_mean.device
     cin = block.input_dim
     s_pw, t_pw = _affine(block.pw_bn)
@@ -154,10 +139,8 @@ def _plan(block):
             and L.query('cat_tstage1w_supported', by_k[5]['m'], by_k[3]['m'], hc)):
         s1w = dict(packs=None, ws=[by_k[5]['wf'], by_k[3]['wf'], w_a],      # packed filter streams: built at the first launch
                    biases=[by_k[5]['bf'], by_k[3]['bf'], b_a.contiguous()], m=[by_k[5]['m'], by_k[3]['m'], hc])
-    plan = dict(key=key, s1w=s1w, tail_pack=None, tail_offs=None, hc=hc, dwm=dwm, w_a=w_a, b_a=b_a.contiguous(), w_f=w_f, b_f=b_f.contiguous(), dws=dws, wides=wides, act=act, slope=slope,
+    return dict(s1w=s1w, tail_pack=None, tail_offs=None, hc=hc, dwm=dwm, w_a=w_a, b_a=b_a.contiguous(), w_f=w_f, b_f=b_f.contiguous(), dws=dws, wides=wides, act=act, slope=slope,
                 pad_mode=pad_mode, copies=[(o, sz) for (kind, _), (o, m, sz) in zip(slots, offs) if kind == 'res'])
-    block._cat_frozen = plan
-    return plan
 
 
 def block_forward(block, x):

@@ -120,13 +120,13 @@ class _Plan(U.Plan):
 
 
 def plan_for(block, x):
-    p = getattr(block, '_cat_fused_plan', None)
+    p = getattr(block, U.PLAN, None)
     # the plan holds Parameter OBJECTS (gradient targets are keyed by identity): a parameter replaced by one of the same shape
     # (module.weight = nn.Parameter(...), weight transfer) invalidates it like a shape change does
     if p is None or p.dev != x.device or p.shapes != tuple(tuple(q.shape) for q in block.parameters()) or \
             p.ids != tuple(id(q) for q in block.parameters()):
         p = _Plan(block, x.device)
-        block._cat_fused_plan = p
+        setattr(block, U.PLAN, p)
     return p
 
 

@@ -28,6 +28,7 @@ import os
 import torch
 
 from . import _lib as L
+from . import derived
 from . import nn as cnn
 from . import ops
 from . import optim
@@ -163,13 +164,15 @@ def units_of(generator):
     """Plans of every fused unit (main six-branch units and gamma|beta nets) built so far under `generator`, in module order."""
     out = []
     for m in generator.modules():
-        for slot in ('_cat_fused_main', '_cat_fused_gb'):
+        for slot in (MAIN, GB):
             p = m.__dict__.get(slot)
             if p is not None:
                 out.append(p)
     return out
 
 
+MAIN, GB = derived.slot('_cat_fused_main'), derived.slot('_cat_fused_gb')      # R7: a block's main unit / a SPADE layer's gamma|beta net (the slot holds the plan)
+EVAL_SS = derived.slot('eval_ss')      # R6: the eval scale / shift rows, on a unit's plan
 PLAN_GEN = 0      # bumped whenever a unit plan is (re)built: generators regroup their units' operand preparation when it moves
 
 
@@ -270,10 +273,10 @@ def _eval_affine(p):
         tensors += [b['bn1'].weight, b['bn1'].bias, b['bn1'].running_mean, b['bn1'].running_var]
     for b in p.dws:
         tensors += [b['bn2'].weight, b['bn2'].bias, b['bn2'].running_mean, b['bn2'].running_var]
-    key = optim.weights_key(tensors)
-    cached = getattr(p, 'eval_ss', None)
-    if cached is not None and cached[0] == key:
-        return cached[1], cached[2]
+    return derived.lookup(p, EVAL_SS, optim.weights_key(tensors), lambda prev: _fold_norms(p))
+
+
+def _fold_norms(p):
     dev = p.dev
     ss1 = torch.zeros((2, max(p.hc1, 4)), device=dev, dtype=torch.float32)
     ssd = torch.zeros((2, max(p.hcd, 4)), device=dev, dtype=torch.float32)
@@ -286,7 +289,6 @@ def _eval_affine(p):
         fold(b['bn1'], ss1, b['o1'], b['m'])
     for b in p.dws:
         fold(b['bn2'], ssd, b['od'], b['m'])
-    p.eval_ss = (key, ss1, ssd)
     return ss1, ssd
 
 
@@ -408,7 +410,7 @@ def prepass(units):
     xs = [ops.conform(u[5]) for u in units]
     if any(x.requires_grad for x in xs) or not all(applicable(u[1], u[2], x, True) for u, x in zip(units, xs)):
         return None
-    plans = tuple(plan_for(u[0], '_cat_fused_gb', u[1], u[2], u[3], u[4], x) for u, x in zip(units, xs))
+    plans = tuple(plan_for(u[0], GB, u[1], u[2], u[3], u[4], x) for u, x in zip(units, xs))
     STATS['prepass'] = STATS.get('prepass', 0) + 1
     if not torch.is_grad_enabled():
         return _drive_many([_train_g(p, x, None, None) for p, x in zip(plans, xs)])

@@ -28,10 +28,13 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from . import derived
 from . import nn as cnn
 from . import ops
 from . import optim
 from . import tconv
+
+PLAN = derived.slot('_cat_fused_plan')      # R7: a fused block's plan (the slot holds the Plan itself, which keeps its own keys)
 
 
 def cs4(c):
@@ -266,7 +269,7 @@ class Plan:
 def prepare_many(blocks, backward=False):
     """prepare_plans over the plans of the fused blocks of a generator.  Blocks without a plan yet (first forward) are left to their own
     prepare()."""
-    plans = [getattr(b, '_cat_fused_plan', None) for b in blocks]
+    plans = [getattr(b, PLAN, None) for b in blocks]
     prepare_plans([p for p in plans if p is not None], blocks, backward)
 
 

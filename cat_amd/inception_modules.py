@@ -379,7 +379,7 @@ class InceptionSPADE(nn.Module):
             gb = pre
         elif fused_spade._UNITS in ('all', 'gb') and fused_spade.applicable(self.res_ops, self.dw_ops, seg, self.training):
             # all first convs / norms / depthwise convs / the 2C-channel branch sum of the gamma|beta net as 5 launches (cat_amd/fused_spade.py)
-            gb = fused_spade.apply(self, '_cat_fused_gb', self.res_ops, self.dw_ops, self.input_dim, 2 * self.output_dim, seg)
+            gb = fused_spade.apply(self, fused_spade.GB, self.res_ops, self.dw_ops, self.input_dim, 2 * self.output_dim, seg)
         else:
             gb = _run_branches(branch_ops, seg)
         if instance:      # norm_G = 'spadeinstance...' (reference :414-415): per-image statistics in train and eval mode alike
@@ -509,7 +509,7 @@ class SPADEInvertedResidualChannels(nn.Module):
         tmp = self.active(tmp, applied=True)
         from . import fused_spade
         if fused_spade._UNITS in ('all', 'main') and fused_spade.applicable(self.res_ops, self.dw_ops, tmp, self.training):
-            return fused_spade.apply(self, '_cat_fused_main', self.res_ops, self.dw_ops, self.input_dim, self.output_dim, tmp,
+            return fused_spade.apply(self, fused_spade.MAIN, self.res_ops, self.dw_ops, self.input_dim, self.output_dim, tmp,
                                      addend=self._shortcut(x_short))
         return _run_branches(branch_ops, tmp, extra=(self._shortcut(x_short),))
 

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib as L
+from .. import nn as cnn
 from .. import ops
 
 BN_EPS = 1e-5
@@ -27,24 +28,7 @@ BN_EPS = 1e-5
 def _folded(conv, bn):
     """(filters in the kernels' padded channels-last storage with the BatchNorm scale folded in, wcs, bias) of a conv + eval BatchNorm pair,
     or of a bare conv (bn None); cached on the conv holder, refreshed when a tensor changes."""
-    ts = [conv.weight] + ([conv.bias] if conv.bias is not None else []) + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-    key = tuple((t.data_ptr(), t._version) for t in ts)
-    cache = conv.__dict__.get('_cat_fold')
-    if cache is None or cache[0] != key:
-        with torch.no_grad():
-            w = ops.padded_weight_like(conv.weight.shape, conv.weight.device)
-            if bn is not None:
-                scale = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
-                w.copy_(conv.weight * scale.view(-1, 1, 1, 1))
-                bias = bn.bias - bn.running_mean * scale
-                if conv.bias is not None:
-                    bias = bias + conv.bias * scale
-                bias = bias.contiguous()
-            else:
-                w.copy_(conv.weight)
-                bias = conv.bias.detach().contiguous() if conv.bias is not None else None
-        cache = conv.__dict__['_cat_fold'] = (key, w, ops.weight_wcs(w), bias)
-    return cache[1:]
+    return cnn.folded_metric_conv(conv, conv, bn)
 
 
 def conv_bn_act(x, conv, bn, act, res=None):

@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib as L
+from .. import nn as cnn
 from .. import ops
 
 POOL_MAX, POOL_AVG_EXCL = 0, 1
@@ -35,18 +36,8 @@ class BasicConv2d(nn.Module):
         self.out_channels = out_channels
 
     def _folded(self):
-        """(filters in the kernels' padded channels-last storage with the BatchNorm scale folded in, bias): refreshed when a tensor changes."""
-        ts = (self.conv.weight, self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var)
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        cache = self.__dict__.get('_cat_fold')
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                scale = self.bn.weight * torch.rsqrt(self.bn.running_var + self.bn.eps)
-                w = ops.padded_weight_like(self.conv.weight.shape, self.conv.weight.device)
-                w.copy_(self.conv.weight * scale.view(-1, 1, 1, 1))
-                bias = (self.bn.bias - self.bn.running_mean * scale).contiguous()
-            cache = self.__dict__['_cat_fold'] = (key, w, ops.weight_wcs(w), bias)
-        return cache[1:]
+        """(filters in the kernels' padded channels-last storage with the BatchNorm scale folded in, wcs, bias): refreshed when a tensor changes."""
+        return cnn.folded_metric_conv(self, self.conv, self.bn)
 
     def forward(self, x, out=None, c0=0):
         """x: NHWC activation.  out / c0: write channels [c0, c0 + Cout) of this wider activation instead of a fresh tensor."""

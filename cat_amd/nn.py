@@ -13,9 +13,13 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from . import derived
 from . import ops
 from . import optim
 from . import rng
+
+FOLD = derived.slot('_cat_fold')      # R4: (w, bias) of a conv + eval-BatchNorm fold, on the conv; R9: (w, wcs, bias) on a metric network's holder
+Q = derived.slot('_cat_q')            # the quad-granule layer of a conv (its plans per input shape, its filter stream R8); replaced, never keyed
 
 
 class Padded:
@@ -139,35 +143,53 @@ def _rehouse_(w):
     w.data = new
 
 
+def bn_affine(bn):
+    """(scale, shift) of an eval-mode BatchNorm: the per-channel affine map its running statistics make of it."""
+    scale = torch.rsqrt(bn.running_var + bn.eps)
+    if bn.weight is not None:
+        scale = scale * bn.weight
+    shift = -bn.running_mean * scale
+    if bn.bias is not None:
+        shift = shift + bn.bias
+    return scale, shift
+
+
+def fold_conv_bn(conv, bn, out_dim, padded=False):
+    """(w, bias) of conv -> eval BatchNorm as one conv: the norm's scale folded into the filters along weight dim `out_dim`, its shift into the
+    bias.  bn None: the bare conv (bias None if it has none).  w is a fresh tensor in the kernels' padded channels-last storage when the
+    weight has more than one input channel -- always with `padded`, the metric networks' rule -- else contiguous."""
+    with torch.no_grad():
+        w, bias = conv.weight.detach(), None if conv.bias is None else conv.bias.detach()
+        if bn is not None:
+            scale, shift = bn_affine(bn)
+            shape = [1, 1, 1, 1]
+            shape[out_dim] = -1
+            w = w * scale.view(shape)
+            bias = shift if bias is None else bias * scale + shift
+        if padded or (w.dim() == 4 and w.shape[1] > 1):
+            wf = ops.padded_weight_like(w.shape, w.device)
+            wf.copy_(w)
+        else:
+            wf = w.contiguous()
+        return wf, None if bias is None else bias.contiguous()
+
+
 def _folded_eval_bn(conv, bn, out_dim):
     """Frozen-teacher fast path: conv -> BatchNorm2d(eval, running stats) is an affine map per output channel, so it is folded
     into the conv's weight / bias once (cached until any of the tensors involved changes) and the norm kernel disappears.
     One-time setup arithmetic, not part of the per-step kernel stream."""
-    tensors = [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
     # optimizer-owned weights are updated through raw pointers (no version bump): such layers re-fold after every optimizer step
-    key = optim.weights_key(tensors)
-    cache = getattr(conv, '_cat_fold', None)
-    if cache is not None and cache[0] == key:
-        return cache[1], cache[2]
-    with torch.no_grad():
-        scale = torch.rsqrt(bn.running_var + bn.eps)
-        if bn.weight is not None:
-            scale = scale * bn.weight
-        shift = -bn.running_mean * scale
-        if bn.bias is not None:
-            shift = shift + bn.bias
-        shape = [1, 1, 1, 1]
-        shape[out_dim] = -1
-        w = conv.weight.detach()
-        if w.dim() == 4 and w.shape[1] > 1:
-            wf = ops.padded_weight_like(w.shape, w.device)
-            wf.copy_(w * scale.view(shape))
-        else:
-            wf = (w * scale.view(shape)).contiguous()
-        bf = shift if conv.bias is None else conv.bias.detach() * scale + shift
-        bf = bf.contiguous()
-    conv._cat_fold = (key, wf, bf)
-    return wf, bf
+    key = optim.weights_key([conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var])
+    return derived.lookup(conv, FOLD, key, lambda prev: fold_conv_bn(conv, bn, out_dim))
+
+
+def folded_metric_conv(holder, conv, bn):
+    """(w, wcs, bias) of a metric network's conv [+ eval BatchNorm] pair (R9), always in padded channels-last storage; cached on `holder`."""
+    def make(prev):
+        w, bias = fold_conv_bn(conv, bn, 0, padded=True)
+        return w, ops.weight_wcs(w), bias
+    tensors = [conv.weight, conv.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+    return derived.lookup(holder, FOLD, optim.weights_key(tensors), make)
 
 
 def _bn_folds(bn):
@@ -393,9 +415,9 @@ def _edge_conv(m, nxt, x):
 def _q_layer(conv, pad, mode):
     from . import qconv
     _to_channels_last_(conv)
-    layer = getattr(conv, '_cat_q', None)
+    layer = getattr(conv, Q, None)
     if layer is None or layer.weight is not conv.weight or layer.pad != pad or layer.reflect != (mode == L.PAD_REFLECT):
-        layer = conv._cat_q = qconv.Layer('conv', conv.weight, stride=conv.stride[0], pad=pad, reflect=mode == L.PAD_REFLECT)
+        layer = conv.__dict__[Q] = qconv.Layer('conv', conv.weight, stride=conv.stride[0], pad=pad, reflect=mode == L.PAD_REFLECT)
     return layer
 
 

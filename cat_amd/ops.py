@@ -10,7 +10,7 @@ import warnings
 
 import torch
 
-from . import _lib as L, optim
+from . import _lib as L, derived, optim
 from ._lib import ConvGeom, NormGeom
 
 STATS = {'conform_copies': 0}   # non-native layout fix-ups; must stay 0 on the distillation hot path
@@ -345,6 +345,7 @@ def _nchw(t):
 # ---------------------------------------------------------------------------------------------- convolutions
 _TCONV = os.environ.get('CAT_TCONV', '1') != '0'      # LDS-tile kernels with packed filters for stride-1 3x3 / 5x5 layers (A/B switch)
 _TCONV_MIN_TILES = int(os.environ.get('CAT_TCONV_MIN_TILES', '96'))
+PK, WT, WTP = derived.slot('_cat_pk'), derived.slot('_cat_wt'), derived.slot('_cat_wtp')      # R1 ({mode: Entry}), R2, R3: filter packs, on the weight
 
 
 def set_tconv_min_tiles(n):
@@ -375,21 +376,16 @@ def packed_filter(weight, wcl, mode):
     owner = weight if weight is not None else wcl
     if owner is not wcl and owner.data_ptr() != wcl.data_ptr():      # a re-laid-out temporary (foreign layout): nothing to key a cache on
         return tconv.pack(wcl, mode)
-    key = (wcl.data_ptr(), wcl._version, optim.epoch_of([owner]))
-    cache = getattr(owner, '_cat_pk', None)
-    if cache is None:
-        cache = owner._cat_pk = {}
-    ent = cache.get(mode)
-    if ent is not None and ent[0] == key:
-        return ent[1]
-    if ent is None or ent[1].device != wcl.device:
-        o, i, kh, kw = wcl.shape
-        nn, ck = (o, i) if mode == tconv.FWD else (i, o)
-        ent = [None, torch.empty(tconv.pack_floats(kh, tconv.cs4(ck), nn), device=wcl.device, dtype=torch.float32)]
-        cache[mode] = ent
-    tconv.pack_into(ent[1], wcl, mode)
-    ent[0] = key
-    return ent[1]
+
+    def make(prev):
+        buf = prev.value if prev is not None and prev.value.device == wcl.device else None
+        if buf is None:
+            o, i, kh, kw = wcl.shape
+            nn, ck = (o, i) if mode == tconv.FWD else (i, o)
+            buf = torch.empty(tconv.pack_floats(kh, tconv.cs4(ck), nn), device=wcl.device, dtype=torch.float32)
+        tconv.pack_into(buf, wcl, mode)
+        return buf
+    return derived.lookup(owner, PK, optim.pack_key(wcl, owner), make, sub=mode)
 
 
 def _conv_fwd(g, x, w, bias, y, st):
@@ -405,16 +401,14 @@ def transposed_filter(weight, wcl, g):
     """[Cin][kh][kw][Cout] copy of a conv weight for cat_conv2d_dgrad_t, cached on the tensor and refreshed when the weight changed (same
     keying as packed_filter: version counter, or the optimizer epoch for FusedAdam-owned parameters)."""
     owner = weight if weight is not None else wcl
-    key = (wcl.data_ptr(), wcl._version, optim.epoch_of([owner]))
-    ent = getattr(owner, '_cat_wt', None)
-    if ent is not None and ent[0] == key:
-        return ent[1]
-    o, i, kh, kw = wcl.shape
-    buf = ent[1] if (ent is not None and ent[1].numel() == o * i * kh * kw and ent[1].device == wcl.device) else \
-        torch.empty(o * i * kh * kw, device=wcl.device, dtype=torch.float32)
-    L.call('cat_conv2d_weight_transpose', C.byref(g), _p(wcl), _p(buf), _stream())
-    owner._cat_wt = (key, buf)
-    return buf
+
+    def make(prev):
+        o, i, kh, kw = wcl.shape
+        buf = prev.value if (prev is not None and prev.value.numel() == o * i * kh * kw and prev.value.device == wcl.device) else \
+            torch.empty(o * i * kh * kw, device=wcl.device, dtype=torch.float32)
+        L.call('cat_conv2d_weight_transpose', C.byref(g), _p(wcl), _p(buf), _stream())
+        return buf
+    return derived.lookup(owner, WT, optim.pack_key(wcl, owner), make)
 
 
 # ---------------------------------------------------------------------------------------------- opt-in split-bf16 backward tiles
@@ -441,13 +435,7 @@ def split_transposed_filter(weight, wcl, g):
     """bf16 planes of the [Cin][kh][kw][Cout] filter copy, cached like transposed_filter"""
     wt = transposed_filter(weight, wcl, g)
     owner = weight if weight is not None else wcl
-    key = owner._cat_wt[0]
-    ent = getattr(owner, '_cat_wtp', None)
-    if ent is not None and ent[0] == key:
-        return ent[1]
-    planes = split_planes(wt)
-    owner._cat_wtp = (key, planes)
-    return planes
+    return derived.lookup(owner, WTP, derived.peek(owner, WT).key, lambda prev: split_planes(wt))
 
 
 def _conv_dgrad(g, dy, w, bias, dx, dxcs, dxcw, st, weight=None):

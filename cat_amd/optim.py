@@ -15,7 +15,7 @@ import torch
 from . import _lib as L
 
 # The kernels update parameters (and BatchNorm running statistics) through raw pointers, so torch's `_version` counters never move.
-# Caches derived from trainable weights (cat_amd/frozen.py folds an eval-mode block's weights once) key on this epoch instead:
+# Caches derived from trainable weights (cat_amd/derived.py; e.g. cat_amd/frozen.py folds an eval-mode block's weights once) key on this epoch instead:
 # it advances with every optimizer step, eager or replayed.
 _WEIGHTS_EPOCH = 0
 
@@ -44,7 +44,7 @@ def epoch_of(tensors):
 # no optimizer step anywhere near (a forward-only pass, a net without an optimizer, an evaluation between two steps), so neither
 # `_version` nor the weights epoch sees it.  Every wrapper that hands a running-statistics pointer to a kernel calls note_stats_written()
 # on those buffers; the count lives on the buffer itself and only weights_key() -- the key of the conv+BN / block / unit FOLDS, the only
-# operands derived from statistics -- reads it.  Filter packs and transposed filters key on epoch_of() alone: a train-mode norm forward
+# operands derived from statistics -- reads it.  Filter packs and transposed filters key on pack_key(), whose tensors carry none: a train-mode norm forward
 # between two uses of a discriminator never refreshes a weight pack.  Host-only: no launch.
 # PRECONDITION: the count is a Python attribute, so a captured-graph REPLAY of a train-mode norm does not advance it.  The folds of a
 # replayed net stay fresh only because the norm's weight and bias are FusedAdam-owned and note_graph_replay advances the epoch in their
@@ -71,6 +71,12 @@ def weights_key(tensors):
     """Cache key of an operand derived from `tensors` (None entries allowed): changes when any of them moved or changed value -- by an
     ordinary in-place update (version), an optimizer step on an owned tensor (epoch), or a norm kernel's statistics update (stat_writes)."""
     return (tuple(_tensor_key(t) if t is not None else None for t in tensors), epoch_of(tensors))
+
+
+def pack_key(wcl, owner):
+    """Cache key of a filter pack: pointer and version of the kernel-layout tensor `wcl` the pack is read from, the epoch of the Parameter
+    `owner` it is a view of (ownership is registered on the Parameter).  Weights carry no statistics count, so none is part of it."""
+    return (weights_key([wcl])[0], epoch_of([owner]))
 
 
 def _adopt(p, view):

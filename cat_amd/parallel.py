@@ -19,6 +19,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import derived
+
 
 def init_distributed(backend=None):
     """Initialise torch.distributed from the torchrun environment (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_*).
@@ -182,15 +184,8 @@ class DataParallelReducer:
                     stage = d.contiguous()
                     dist.broadcast(stage, src=src, group=self.group)
                     d.copy_(stage)
-                t.__dict__.pop('_cat_pk', None)        # packed-filter cache of the LDS-tile convs
-                t.__dict__.pop('_cat_wt', None)        # transposed-filter cache of the wide dgrad tiles
-                t.__dict__.pop('_cat_wtp', None)       # ... and its split-bf16 planes (CAT_MFMA=bf16x3), keyed by the same (ptr, version, epoch)
-            # the broadcast wrote through .data (no version bump): drop every cache derived from the old values
-            for sub in m.modules():
-                for attr in ('_cat_frozen', '_cat_fold', '_cat_fused_plan', '_cat_fused_gb', '_cat_fused_main', '_cat_q'):
-                    sub.__dict__.pop(attr, None)
-        from . import optim
-        optim._bump_weights_epoch()
+        # the broadcast wrote through .data (no version bump): drop every cache derived from the old values
+        derived.drop_derived(modules)
 
     def all_reduce_sum_(self, t):
         """In-place sum over ranks, ordered with the CURRENT stream (SynchronizedBatchNorm's [sum x | sum x^2] exchange,

@@ -9,7 +9,9 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from . import derived
 from . import ops
+from . import optim
 
 
 def cs4(c):
@@ -78,6 +80,7 @@ def pack_conv(g, seg, dst, wcl, wcs, nn, ntaps):
 # sub-pixel classes of ConvTranspose2d(k 3, stride 2, padding 1, output_padding 1): output row 2a + py reads input rows a (+1) with
 # filter rows ky:  py = 0 -> (dy 0, ky 1);  py = 1 -> (dy 0, ky 2), (dy 1, ky 0).  Same along x.
 _CT_K = {0: [1], 1: [2, 0]}
+PK = derived.slot('_pk')      # R8: a Layer's packed filter stream
 
 
 def ct_class_taps(py, px):
@@ -100,7 +103,6 @@ class Layer:
     def __init__(self, kind, weight, stride=1, pad=0, reflect=False):
         self.kind, self.weight, self.stride, self.pad, self.reflect = kind, weight, stride, pad, reflect
         self._plans = {}
-        self._pk = None      # (key, tensor, plan signature)
 
     @staticmethod
     def supported(kind, weight, stride, pad, out_pad=0):
@@ -142,7 +144,6 @@ class Layer:
 
     def run(self, x, bias, y, act=L.ACT_NONE, slope=0.0, pre=None, stats=None, scs=0):
         """Returns the plan (tile geometry of the statistics table).  y: NHWC output activation."""
-        from . import optim
         n, c, h, w = x.shape
         nn, ho, wo = self.out_shape(x)
         segs = self._segments(x, pre)
@@ -157,16 +158,17 @@ class Layer:
         # packed stream: keyed like ops.packed_filter (version counter, or the optimizer epoch for FusedAdam-owned parameters)
         wcl, wcs = ops.weight_cl(self.weight)
         sig = (plan.cs, plan.nq, plan.nsplit, int(plan.pack_floats), plan.th)
-        wkey = (wcl.data_ptr(), wcl._version, optim.epoch_of([self.weight]), sig, key)
-        if self._pk is None or self._pk[0] != wkey:
-            same_layout = self._pk is not None and self._pk[0][3:] == wkey[3:] and self._pk[1].device == x.device
+        wkey = (optim.pack_key(wcl, self.weight), sig, key)
+
+        def make(prev):
+            same_layout = prev is not None and prev.key[1:] == wkey[1:] and prev.value.device == x.device
             # a new weight version re-packs in place; another geometry gets a fresh zeroed stream (its spare table rows / filter step must read 0)
-            buf = self._pk[1] if same_layout else torch.zeros(int(plan.pack_floats), device=x.device, dtype=torch.float32)
+            buf = prev.value if same_layout else torch.zeros(int(plan.pack_floats), device=x.device, dtype=torch.float32)
             if ct:
                 pack_conv_transpose(g, buf, wcl, wcs, nn)
             else:
                 k = self.weight.shape[2]
                 pack_conv(g, 0, buf, wcl, wcs, nn, k * k)
-            self._pk = (wkey, buf)
-        launch(g, self._pk[1], bias, y.data_ptr())
+            return buf
+        launch(g, derived.lookup(self, PK, wkey, make), bias, y.data_ptr())
         return plan

@@ -233,9 +233,10 @@ class ConvRow(Row):
         return Padded(nn.Identity(), nn.Conv2d(self.cin, self.cout, self.k, stride=self.stride, padding=self.pad, bias=self.bias))
 
     def derived(self, net):
+        from cat_amd import derived, ops
         w = net.conv.weight
-        out = [ent[1] for ent in getattr(w, '_cat_pk', {}).values()]
-        out += [getattr(w, a)[1] for a in ('_cat_wt', '_cat_wtp') if getattr(w, a, None) is not None]
+        out = [ent.value for ent in (derived.peek(w, ops.PK) or {}).values()]
+        out += [derived.peek(w, a).value for a in (ops.WT, ops.WTP) if derived.peek(w, a) is not None]
         return out
 
 
@@ -274,7 +275,8 @@ class FoldRow(Row):
             return list(cnn._folded_eval_bn(net[0], net[1], 0))
 
     def fold_keys(self, net):
-        return [net[0]._cat_fold[0]]
+        from cat_amd import derived, nn as cnn
+        return [derived.peek(net[0], cnn.FOLD).key]
 
 
 class TorchBlock(nn.Module):
@@ -367,7 +369,8 @@ class FrozenRow(BlockRow):
         return [p['w_a'], p['w_f'], p['b_f'], p['dwm']['frame'], p['tail_pack']] + list(p['s1w']['packs'])
 
     def fold_keys(self, net):
-        return [net.blocks[0]._cat_frozen['key']]
+        from cat_amd import derived, frozen
+        return [derived.peek(net.blocks[0], frozen.FROZEN).key]
 
 
 class FusedRow(BlockRow):
@@ -444,7 +447,8 @@ class SpadeRow(Row):
         return [t for p in plans for t in fused_spade._eval_affine(p)]
 
     def fold_keys(self, net):
-        return [p.eval_ss[0] for p in (net._cat_fused_main, net.spade._cat_fused_gb)]
+        from cat_amd import derived, fused_spade
+        return [derived.peek(p, fused_spade.EVAL_SS).key for p in (net._cat_fused_main, net.spade._cat_fused_gb)]
 
 
 R1Z = ConvRow('R1 packed_filter zero pad', 12, 20, 3, 1, 1, (1, 8, 16), uses=('cat_tconv_fwd',), derives=('cat_tconv_pack',), seed=110)

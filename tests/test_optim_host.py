@@ -147,10 +147,10 @@ def test_statistics_counter_is_not_part_of_the_weight_pack_key():
     """The counter lives on the statistics buffers and only weights_key reads it: epoch_of -- the whole optimizer part of the filter-pack /
     transposed-filter / qconv-stream keys -- does not move when a norm layer of the same net runs in train mode."""
     w, rv = _param(), torch.ones(3)
-    pack_key = (w.data_ptr(), w._version, optim.epoch_of([w]))
+    pack_key = optim.pack_key(w, w)
     fold_key = optim.weights_key([w, rv])
     assert optim.stat_writes(rv) == 0 and fold_key[0][1] == (rv.data_ptr(), rv._version)
     optim.note_stats_written(rv, None)
     assert optim.stat_writes(rv) == 1 and optim.stat_writes(w) == 0
-    assert (w.data_ptr(), w._version, optim.epoch_of([w])) == pack_key
+    assert optim.pack_key(w, w) == pack_key == (((w.data_ptr(), w._version),), optim.epoch_of([w]))
     assert optim.weights_key([w, rv]) != fold_key and optim.weights_key([w]) == (fold_key[0][:1], fold_key[1])

@@ -774,8 +774,9 @@ def test_layer_streams_follow_optimizer_steps_and_storage_moves(dev, column):
         print('qconv.Layer %s: warm vs fp64(W1) %.3g of the bar; (c) upper-quartile separation %.3g bars' % (column, ratio, sep))
         assert ratio <= 1.0, (column, ratio)                                      # (b)
         assert sep > 100.0, (column, sep)                                         # (c)
-        stream = layer._pk[1]
-        assert torch.equal(run(layer, bias), warm) and layer._pk[1] is stream and len(packs) == 1      # (d)
+        from cat_amd import derived
+        stream = derived.peek(layer, qconv.PK).value
+        assert torch.equal(run(layer, bias), warm) and derived.peek(layer, qconv.PK).value is stream and len(packs) == 1      # (d)
     finally:
         L.call = real_call
     wc = ops.padded_weight_like(sg.w.shape, dev)
