@@ -103,7 +103,11 @@ __device__ __forceinline__ float act_grad_from_out(float y, int act, float slope
 // nothing else, which is what makes cat_loss_multi_* bit-identical to cat_loss_fwd/bwd term by term.  CAT_LOSS_MSE is the default arm.
 __device__ __forceinline__ float loss_term(int kind, float a, float b, float t) {
   switch (kind) {
-    case CAT_LOSS_L1: return fabsf(a - b);
+    case CAT_LOSS_L1: {      // t = beta of nn.SmoothL1Loss: d^2 / (2 beta) inside |d| < beta, |d| - beta / 2 outside; both arms computed, one select.
+      // beta 0 is plain L1, bit for bit: |d| < 0 never holds and |d| - 0 is |d| (rbeta is uniform and loop-invariant, and keeps the unused arm finite)
+      const float d = a - b, ad = fabsf(d), rbeta = t > 0.f ? 1.f / t : 0.f;
+      return ad < t ? 0.5f * d * d * rbeta : ad - 0.5f * t;
+    }
     case CAT_LOSS_LSGAN: return (a - t) * (a - t);
     case CAT_LOSS_HINGE_D_REAL: return -fminf(a - 1.f, 0.f);
     case CAT_LOSS_HINGE_D_FAKE: return -fminf(-a - 1.f, 0.f);
@@ -115,7 +119,10 @@ __device__ __forceinline__ float loss_term(int kind, float a, float b, float t) 
 }
 __device__ __forceinline__ float loss_grad(int kind, float a, float b, float t) {
   switch (kind) {
-    case CAT_LOSS_L1: return a > b ? 1.f : (a < b ? -1.f : 0.f);
+    case CAT_LOSS_L1: {      // d / beta inside |d| < beta, sign(d) outside (beta 0: sign(d) everywhere, 0 at d = 0)
+      const float d = a - b, rbeta = t > 0.f ? 1.f / t : 0.f;
+      return fabsf(d) < t ? d * rbeta : (a > b ? 1.f : (a < b ? -1.f : 0.f));
+    }
     case CAT_LOSS_LSGAN: return 2.f * (a - t);
     case CAT_LOSS_HINGE_D_REAL: return a - 1.f < 0.f ? -1.f : 0.f;   // torch.min(x-1, 0): ties send the gradient to ... see tests (measure zero)
     case CAT_LOSS_HINGE_D_FAKE: return -a - 1.f < 0.f ? 1.f : 0.f;

@@ -65,12 +65,7 @@ class BaseInceptionDistiller(host.StepHost):
 
         self.netG_teacher.eval()
         self.criterionGAN = closs.GANLoss(opt.gan_mode)
-        if opt.recon_loss_type == 'l1':
-            self.criterionRecon = closs.L1Loss()
-        elif opt.recon_loss_type == 'l2':
-            self.criterionRecon = closs.MSELoss()
-        else:
-            raise NotImplementedError('Unknown reconstruction loss type [%s]!' % opt.recon_loss_type)
+        self.criterionRecon = closs.recon_criterion(opt.recon_loss_type)
 
         self.mapping_layers = ['down_sampling.9'] + ['features.%d' % i for i in range(2, 11, 3)]
         self.netAs = []

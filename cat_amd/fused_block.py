@@ -65,8 +65,12 @@ def applicable(block, x):
         return False
     norms = [op[1][1] for op in block.res_ops] + [op[0][1] for op in block.dw_ops] + [op[2][1] for op in block.dw_ops] + [block.pw_bn]
     kind = type(norms[0])
-    if kind not in (cnn.BatchNorm2d, cnn.InstanceNorm2d) or any(type(m) is not kind for m in norms):
+    if kind not in (cnn.BatchNorm2d, cnn.InstanceNorm2d, cnn.SynchronizedBatchNorm2d) or any(type(m) is not kind for m in norms):
         return False
+    if kind is cnn.SynchronizedBatchNorm2d:      # --norm syncbatch: replica-local layers are BatchNorm2d that never count batches (fused_unit.slices)
+        if any(not m.replica_local for m in norms):
+            return False
+        kind = cnn.BatchNorm2d
     if kind is cnn.BatchNorm2d and any(m.momentum is None or not m.track_running_stats for m in norms):
         return False
     if kind is cnn.InstanceNorm2d and any(m.track_running_stats for m in norms):

@@ -1,4 +1,4 @@
-"""Losses of the distillation step: GANLoss (reference models/modules/loss.py:8-99: hinge, lsgan, vanilla, wgangp), the L1 / MSE
+"""Losses of the distillation step: GANLoss (reference models/modules/loss.py:8-99: hinge, lsgan, vanilla, wgangp), the L1 / MSE / smooth-L1
 reconstruction criteria and KA (utils/common.py:38-46).  Each evaluates to a 0-d device tensor produced (and
 differentiated) by the reduction kernels of libcat_hip.so."""
 from torch import nn
@@ -49,6 +49,35 @@ class L1Loss(nn.Module):
 class MSELoss(nn.Module):
     def forward(self, input, target):
         return ops.LossFn.apply(input, target, L.LOSS_MSE, 0.0)
+
+
+class SmoothL1Loss(nn.Module):
+    """torch.nn.SmoothL1Loss(beta=1.0), mean reduction (--recon_loss_type smooth_l1 builds it with the default): the L1 kind of cat_loss_fwd
+    with beta as its `target` (include/cat_hip.h; beta 0 is L1Loss)."""
+
+    def __init__(self, beta=1.0):
+        super().__init__()
+        if beta < 0:
+            raise ValueError('SmoothL1Loss: beta must be >= 0')
+        self.beta = float(beta)
+
+    def forward(self, input, target):
+        return ops.LossFn.apply(input, target, L.LOSS_L1, self.beta)
+
+
+def recon_criterion(recon_loss_type):
+    """--recon_loss_type of the inception distillers and of Pix2PixModel (base_inception_distiller.py:171-180, pix2pix_model.py:102-109)."""
+    if recon_loss_type == 'l1':
+        return L1Loss()
+    if recon_loss_type == 'l2':
+        return MSELoss()
+    if recon_loss_type == 'smooth_l1':
+        return SmoothL1Loss()
+    if recon_loss_type == 'vgg':
+        # the reference calls VGGLoss(self.device) (distillers/base_inception_distiller.py:178) on a constructor that takes no argument:
+        # it raises TypeError there, so there is no behaviour to match
+        raise NotImplementedError('recon_loss_type vgg: the reference itself fails at VGGLoss(self.device) (TypeError); nothing to match')
+    raise NotImplementedError('Unknown reconstruction loss type [%s]!' % recon_loss_type)
 
 
 def KA(X, Y):

@@ -1,5 +1,5 @@
 """Pix2PixModel: the teacher-training step of `train.py --model pix2pix` (reference models/pix2pix_model.py:19-207) on the gfx950
-kernels -- generator forward, PatchGAN D step (0.5 * (fake + real)), G step (GAN + lambda_recon * L1 / L2), two Adam updates.
+kernels -- generator forward, PatchGAN D step (0.5 * (fake + real)), G step (GAN + lambda_recon * L1 / L2 / smooth-L1), two Adam updates.
 Same op set as the distillation step; LossValue / seeded backward keep torch arithmetic off the path."""
 from .. import loss as closs
 from .. import networks, ops
@@ -39,12 +39,7 @@ class Pix2PixModel(BaseModel):
         self.netD = networks.define_D(opt.input_nc + opt.output_nc, opt.ndf, opt.netD, opt.n_layers_D, opt.norm, opt.init_type,
                                       opt.init_gain, self._dev_ids, opt=opt)
         self.criterionGAN = closs.GANLoss(opt.gan_mode)
-        if opt.recon_loss_type == 'l1':
-            self.criterionRecon = closs.L1Loss()
-        elif opt.recon_loss_type == 'l2':
-            self.criterionRecon = closs.MSELoss()
-        else:
-            raise NotImplementedError('Unknown reconstruction loss type [%s]!' % opt.recon_loss_type)
+        self.criterionRecon = closs.recon_criterion(opt.recon_loss_type)
         self.optimizer_G = FusedAdam(self.netG.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999))
         self.optimizer_D = FusedAdam(self.netD.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999))
         self.optimizers = [self.optimizer_G, self.optimizer_D]

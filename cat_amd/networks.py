@@ -2,6 +2,7 @@
 init_net), :167-266 (define_G / define_D).  One process drives one GPU, so `gpu_ids` only selects the device
 (data parallelism is cat_amd.parallel, not nn.DataParallel)."""
 import functools
+import warnings
 
 import torch
 from torch.nn import init
@@ -15,6 +16,12 @@ def get_norm_layer(norm_type='instance', affine=True, track_running_stats=True):
         return functools.partial(cnn.BatchNorm2d, affine=affine, track_running_stats=track_running_stats)
     if norm_type == 'instance':
         return functools.partial(cnn.InstanceNorm2d, affine=affine, track_running_stats=track_running_stats)
+    if norm_type == 'syncbatch':      # reference networks.py:48-56
+        if not track_running_stats:
+            warnings.warn('track_running_stats=False is not supported by the SynchronizedBatchNorm.')
+        # the inception family runs under plain nn.DataParallel (networks.py:157-161), where the class takes its F.batch_norm arm on any number
+        # of GPUs (sync_batchnorm/batchnorm.py:68-72): per-replica statistics, num_batches_tracked never advanced, no exchange
+        return functools.partial(cnn.SynchronizedBatchNorm2d, affine=affine, track_running_stats=track_running_stats, replica_local=True)
     if norm_type == 'none':
         return lambda x: cnn.Identity()
     raise NotImplementedError('normalization layer [%s] is not found' % norm_type)

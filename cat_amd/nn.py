@@ -370,11 +370,16 @@ def _hooked(*mods):
     return any(m is not None and (m._forward_hooks or m._forward_pre_hooks) for m in mods)
 
 
+def _exchanges(norm):
+    """SynchronizedBatchNorm2d that may all-reduce its statistics (the SPADE path's); a replica-local one is a BatchNorm2d that never counts batches."""
+    return isinstance(norm, SynchronizedBatchNorm2d) and not norm.replica_local
+
+
 def _edge_conv(m, nxt, x):
     """conv `m` followed by norm `nxt` takes the quad-granule path (csrc/conv_q.hip: cat_qconv_fwd with statistics): dense Conv2d with few
     channels on both sides on a large plane -- the image stem and the first stride-2 conv of a pruned student (3 -> 25 7x7, 25 -> 40 3x3 / 2:
     measured 175 + 105 us against 223 + 108 us for the im2col kernels + 30 us of separate statistics passes, profiles/r04_qconv_layers.txt)"""
-    if not _QCONV or not isinstance(m, Conv2d) or not isinstance(nxt, _NORMS) or isinstance(nxt, SynchronizedBatchNorm2d):
+    if not _QCONV or not isinstance(m, Conv2d) or not isinstance(nxt, _NORMS) or _exchanges(nxt):
         return False
     if _hooked(m):      # the edge path never calls m.forward: a forward (pre-)hook registered on the conv would silently stop firing
         return False
@@ -432,6 +437,8 @@ def _conv_norm_q(conv, norm, act_mod, x, lazy):
     nmode = L.NORM_INSTANCE if inst else L.NORM_BATCH
     track = (not inst) and norm.training and norm.track_running_stats
     rm, rv, nbt = (norm.running_mean, norm.running_var, norm.num_batches_tracked) if track else (None, None, None)
+    if isinstance(norm, SynchronizedBatchNorm2d):      # its forward bypasses _BatchNorm.forward: the counter stays where it is
+        nbt = None
     eps, mom = float(norm.eps), float(norm.momentum if norm.momentum is not None else 0.0)
     q = {'layer': layer, 'stats': True}
     if isinstance(x, ops.Normed) or lazy:      # no-grad forward
@@ -456,7 +463,16 @@ class SynchronizedBatchNorm2d(BatchNorm2d):
     """models/modules/sync_batchnorm/batchnorm.py:SynchronizedBatchNorm2d.  Training mode: statistics over the samples of ALL
     ranks (one RCCL all-reduce of [sum x | sum x^2] per layer, installed with ops.set_bn_sync); with one rank it is
     F.batch_norm, exactly as the reference falls back (:69-72).  `num_batches_tracked` is never advanced (the reference's
-    forward bypasses _BatchNorm.forward)."""
+    forward bypasses _BatchNorm.forward).
+
+    `replica_local=True` is the class as `--norm syncbatch` builds it in the inception family (networks.get_norm_layer): the reference wraps
+    those networks in plain nn.DataParallel (models/networks.py:157-161), never in DataParallelWithCallback, so `_is_parallel` stays False and
+    every replica takes the F.batch_norm arm on its own samples.  Such a layer never reads the installed reducer, and the fused block and the
+    edge-conv path admit it like a BatchNorm2d (its num_batches_tracked stays 0).  The default is the SPADE path's exchange."""
+
+    def __init__(self, *args, replica_local=False, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.replica_local = bool(replica_local)
 
     def forward(self, x, fuse_act=None, applied=False):
         if applied:
@@ -464,7 +480,7 @@ class SynchronizedBatchNorm2d(BatchNorm2d):
         if isinstance(x, Padded):
             raise NotImplementedError('padding in front of a norm layer')
         if self.training or not self.track_running_stats:
-            if ops.bn_sync() is None:     # one rank: F.batch_norm (batchnorm.py:69-72) = the fused stats/finalize/apply launch
+            if self.replica_local or ops.bn_sync() is None:     # one rank: F.batch_norm (batchnorm.py:69-72) = the fused stats/finalize/apply launch
                 return self._run(x, L.NORM_BATCH, True, fuse_act, count_batches=False)
             act, slope = _act_code(fuse_act)
             track = self.training and self.track_running_stats

@@ -1001,7 +1001,7 @@ class KAFn(torch.autograd.Function):
 
 
 class LossFn(torch.autograd.Function):
-    """mean-reduced scalar losses (L1 / MSE / lsgan / hinge); see cat_loss_fwd in include/cat_hip.h."""
+    """mean-reduced scalar losses (L1 / MSE / smooth-L1 / lsgan / hinge); see cat_loss_fwd in include/cat_hip.h."""
 
     @staticmethod
     def forward(ctx, a, b, kind, target):

@@ -164,11 +164,13 @@ def model_profiling(model, height, width, batch=1, channel=3, **unused):
 
 # ---------------------------------------------------------------------------------------------- shrink
 def _norm_cls(opt):
-    return {'instance': cnn.InstanceNorm2d, 'batch': cnn.BatchNorm2d}[opt.norm]
+    return {'instance': cnn.InstanceNorm2d, 'batch': cnn.BatchNorm2d, 'syncbatch': cnn.SynchronizedBatchNorm2d}[opt.norm]
 
 
 def _new_norm(opt, channels):
-    return _norm_cls(opt)(channels, affine=opt.norm_affine, track_running_stats=opt.norm_track_running_stats)
+    cls = _norm_cls(opt)
+    local = {'replica_local': True} if cls is cnn.SynchronizedBatchNorm2d else {}      # as networks.get_norm_layer builds the teacher's
+    return cls(channels, affine=opt.norm_affine, track_running_stats=opt.norm_track_running_stats, **local)
 
 
 def _clone_conv(old, cin, cout, transposed=False):

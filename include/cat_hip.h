@@ -191,6 +191,8 @@ int cat_ka_bwd(const float* X, int64_t Dx, int N, const float* gout, const void*
  *   kind 2: -mean min(a-1,0)  (hinge D real)        kind 3: -mean min(-a-1,0) (hinge D fake)
  *   kind 4: -mean a           (hinge G / wgangp real) kind 5: mean (a-b)^2 (MSE vs tensor)
  *   kind 6: mean BCE-with-logits(a, target) (vanilla) kind 7: mean a (wgangp fake)
+ * Kind 0 reads `target` as the beta of nn.SmoothL1Loss (target >= 0): with d = a-b the element is d^2 / (2 beta) where |d| < beta and
+ * |d| - beta / 2 elsewhere.  target 0 is plain L1, bit for bit; target 1 is nn.SmoothL1Loss() with its defaults.
  * Inputs are NHWC with (C, cs); the mean runs over M*C real elements.  out[0] = loss. */
 #define CAT_LOSS_L1 0
 #define CAT_LOSS_LSGAN 1
