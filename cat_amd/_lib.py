@@ -125,12 +125,22 @@ class LossTerm(C.Structure):
     _fields_ = [('a', c_p), ('b', c_p), ('da', c_p), ('M', c_l), ('kind', c_i), ('C', c_i), ('cs', c_i), ('target', c_f), ('scale', c_f)]
 
 
+class PixelDGeom(C.Structure):
+    _fields_ = [(n, c_i) for n in ('N', 'HW', 'C0', 'xcs', 'C1', 'C2', 'w1cs', 'groups', 'docs')] + [('slope1', c_f), ('slope2', c_f)]
+
+
+class PixelDPlan(C.Structure):
+    _fields_ = [(n, c_i) for n in ('tile_px', 'tiles', 'fwd_grid', 'b1_blocks', 'b2_tiles', 'b2_grid', 'fwd_lds', 'b2_lds')] + \
+               [(n, c_l) for n in ('table_floats', 'ws1_floats', 'ws2_floats')]
+
+
 PAD_ZERO, PAD_REFLECT = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_RELU6 = 0, 1, 2, 3, 4
 NORM_INSTANCE, NORM_BATCH = 0, 1
 LOSS_L1, LOSS_LSGAN, LOSS_HINGE_D_REAL, LOSS_HINGE_D_FAKE, LOSS_NEG_MEAN, LOSS_MSE, LOSS_BCE_LOGITS, LOSS_MEAN = range(8)
 
 _G, _NG, _TG = C.POINTER(ConvGeom), C.POINTER(NormGeom), C.POINTER(TConv)
+_PD = C.POINTER(PixelDGeom)
 # name -> (restype, argtypes); mirrors include/cat_hip.h one to one (tests check every symbol is exported)
 SIGNATURES = {
     'cat_hip_last_error': (C.c_char_p, []),
@@ -255,6 +265,11 @@ SIGNATURES = {
     'cat_spectral_norm_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p]),
     'cat_rng_draw': (c_i, [c_p, c_p, c_p]),
     'cat_dropout_apply': (c_i, [C.POINTER(DropGeom), c_p, c_p, c_p, c_p, c_p, c_p]),
+    'cat_pixeld_plan': (c_i, [_PD, C.POINTER(PixelDPlan)]),
+    'cat_pixeld_fwd1': (c_i, [_PD, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    'cat_pixeld_fwd3': (c_i, [_PD, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    'cat_pixeld_bwd1': (c_i, [_PD, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    'cat_pixeld_bwd2': (c_i, [_PD, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
 }
 
 _lib = None

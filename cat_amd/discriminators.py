@@ -32,6 +32,28 @@ class NLayerDiscriminator(BaseNetwork):
         return self.model(input)
 
 
+class PixelDiscriminator(BaseNetwork):
+    """reference discriminators.py:82-126: the 1x1 PatchGAN (PixelGAN), a per-pixel MLP input_nc -> ndf -> 2 ndf -> 1 of 1x1 convs with one norm
+    and two LeakyReLU(0.2); `net.{i}` state_dict keys.  The first conv always has a bias, the second AND the last only with InstanceNorm.
+    Where cat_amd.pixel_d.applicable() holds the whole network is three fused launches (csrc/pixel_d.hip); everywhere else `net` runs layer
+    by layer on the general kernels."""
+
+    def __init__(self, input_nc, ndf=64, norm_layer=cnn.BatchNorm2d, active_fn='nn.ReLU'):
+        super().__init__()
+        norm_cls = norm_layer.func if isinstance(norm_layer, functools.partial) else norm_layer
+        bias = isinstance(norm_cls, type) and issubclass(norm_cls, nn.InstanceNorm2d)      # get_norm_layer('none') is a lambda: no bias
+        act = get_active_fn(active_fn)
+        self.net = cnn.FusedSequential(cnn.Conv2d(input_nc, ndf, kernel_size=1, stride=1, padding=0), act(0.2),
+                                       cnn.Conv2d(ndf, ndf * 2, kernel_size=1, stride=1, padding=0, bias=bias), norm_layer(ndf * 2), act(0.2),
+                                       cnn.Conv2d(ndf * 2, 1, kernel_size=1, stride=1, padding=0, bias=bias))
+
+    def forward(self, input):
+        from . import pixel_d
+        if pixel_d.applicable(self, input):
+            return pixel_d.forward(self, input)
+        return self.net(input)
+
+
 class SPADENLayerDiscriminator(BaseNetwork):
     """reference discriminators.py:129-182: `model{i}` children; forward returns every intermediate output."""
 

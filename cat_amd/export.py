@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import nn as cnn
+from .discriminators import PixelDiscriminator
 from .inception_generator import InceptionGenerator
 from .inception_modules import Conv, ConvSyncBNReLU, InceptionSPADE, InvertedResidualChannels, SPADEInvertedResidualChannels
 from .inception_spade_generator import InceptionSPADEGenerator
@@ -65,6 +66,17 @@ class TwinConvNormAct(nn.Module):
 
     def forward(self, x):
         return self.active(self.norm(self.conv(x)))
+
+
+class TwinPixelDiscriminator(nn.Module):
+    """discriminators.PixelDiscriminator: its one child `net`."""
+
+    def __init__(self, net):
+        super().__init__()
+        self.net = net
+
+    def forward(self, x):
+        return self.net(x)
 
 
 class TwinConv(nn.Module):
@@ -237,6 +249,8 @@ def _convert(m):
         return TwinConvNormAct(_convert(m.conv), _convert(m.norm), _convert(m.active))
     if isinstance(m, Conv):
         return TwinConv(_convert(m.conv))
+    if isinstance(m, PixelDiscriminator):
+        return TwinPixelDiscriminator(_convert(m.net))
     if isinstance(m, nn.ModuleList):
         return nn.ModuleList([_convert(c) for c in m])
     if isinstance(m, nn.Sequential):      # FusedSequential, ConvBNReLU: same child names (indices)

@@ -109,6 +109,9 @@ def define_D(input_nc, ndf, netD, n_layers_D=3, norm='batch', init_type='normal'
     elif netD == 'n_layers':
         from .discriminators import NLayerDiscriminator
         net = NLayerDiscriminator(input_nc, ndf, n_layers_D, norm_layer=norm_layer, active_fn=opt.active_fn_D)
+    elif netD == 'pixel':      # reference networks.py:257-262
+        from .discriminators import PixelDiscriminator
+        net = PixelDiscriminator(input_nc, ndf, norm_layer=norm_layer, active_fn=opt.active_fn_D)
     else:
         raise NotImplementedError('Discriminator model name [%s] is not recognized' % netD)
     return init_net(net, init_type, init_gain, gpu_ids)

@@ -673,6 +673,50 @@ typedef struct {
 int cat_dropout_apply(const cat_drop_t* g, const float* x, const float* scale, const float* shift, const int* ticket, float* y,
                       cat_stream_t stream);
 
+/* The 1x1 PixelGAN discriminator (pixel_d.hip).  Replaces models/modules/discriminators.py:103-126 -- Conv2d(C0, C1, 1) -> LeakyReLU ->
+ * Conv2d(C1, C2 = 2 C1, 1) -> train-mode BatchNorm2d / InstanceNorm2d -> LeakyReLU -> Conv2d(C2, 1, 1) -- and its autograd backward.
+ * Everything is exact fp32 (v_mfma_f32_32x32x2_f32 for the two C1 x C2 products).  x is NHWC with pixel stride xcs (pad lanes never
+ * read), z = the pre-norm tensor [N * HW][C2], out / dout are 1-channel activations with pixel stride 4 (pad lanes written 0).
+ * C1 % 16 == 0, C1 <= 128, C0 <= 8.  groups = N (InstanceNorm) or 1 (BatchNorm). */
+typedef struct {
+  int N, HW;           /* images, pixels per image */
+  int C0, xcs;         /* input channels and pixel stride (4 | 8); dx has the same stride */
+  int C1, C2;          /* hidden widths: ndf and 2 ndf */
+  int w1cs;            /* floats per row of the first conv's weight [C1][w1cs] (and of its gradient) */
+  int groups;          /* statistics groups: N or 1 */
+  int docs;            /* pixel stride of dout (multiple of 4) */
+  float slope1, slope2;
+} cat_pixeld_t;
+typedef struct {
+  int tile_px;         /* pixels per statistics entry of cat_pixeld_fwd1's table: Ho = 1, Wo = HW, th = 1, tw = tile_px for cat_tnorm_finalize2 */
+  int tiles;           /* statistics entries per image */
+  int fwd_grid;        /* persistent workgroups of cat_pixeld_fwd1 (each walks entries fwd_grid apart, at least 4 where there are that many) */
+  int b1_blocks;       /* workgroups per image of cat_pixeld_bwd1 */
+  int b2_tiles, b2_grid; /* 64-pixel tiles of cat_pixeld_bwd2 (all images) and its persistent workgroups = partial sums its reduce adds */
+  int fwd_lds, b2_lds; /* dynamic LDS bytes of the two MFMA kernels */
+  int64_t table_floats, ws1_floats, ws2_floats; /* the statistics table, the workspaces of cat_pixeld_bwd1 and cat_pixeld_bwd2 */
+} cat_pixeld_plan_t;
+int cat_pixeld_plan(const cat_pixeld_t* g, cat_pixeld_plan_t* plan);
+/* discriminators.py:104-111 (net.0 .. net.2): z = W2 lrelu(W1 x + b1) (+ b2), with per-entry [sum | M2 about the entry's mean] of z per
+ * channel in `table` [N * tiles][2][C2]. */
+int cat_pixeld_fwd1(const cat_pixeld_t* g, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* z,
+                    float* table, cat_stream_t stream);
+/* discriminators.py:112-119 (net.3 .. net.5) from the finalized scale / shift rows [groups][C2]: out = w3 . lrelu(scale z + shift) (+ b3). */
+int cat_pixeld_fwd3(const cat_pixeld_t* g, const float* z, const float* scale, const float* shift, const float* w3, const float* b3,
+                    float* out, cat_stream_t stream);
+/* backward of net.3 .. net.5: the per-group sums of g = dout w3 lrelu'(.) and g zhat, left as coefficient rows coef [groups][7][C2]
+ * (scale, shift, mean, rstd, scale w3, mean(g), mean(g zhat)) for cat_pixeld_bwd2, and -- where the pointer is not NULL -- the gradients of
+ * net.5.weight, net.5.bias, net.3.weight, net.3.bias (added to the destination if accumulate).  Partial sums + one ordered reduce. */
+int cat_pixeld_bwd1(const cat_pixeld_t* g, const float* z, const float* dout, const float* scale, const float* shift, const float* mean,
+                    const float* rstd, const float* w3, float* coef, float* dw3, float* db3, float* dgamma, float* dbeta, int accumulate,
+                    float* ws, cat_stream_t stream);
+/* backward of net.0 .. net.2 (and of the norm's normalisation): dz from coef, h1 recomputed; dx (NULL: not wanted) and, if params, the
+ * gradients of net.0.weight [C1][w1cs], net.0.bias, net.2.weight [C2][C1], net.2.bias (NULL: skipped), per-workgroup partials reduced in
+ * workgroup order. */
+int cat_pixeld_bwd2(const cat_pixeld_t* g, const float* x, const float* z, const float* dout, const float* coef, const float* w1,
+                    const float* b1, const float* w2, float* dx, int params, float* dw1, float* db1, float* dw2, float* db2, int accumulate,
+                    float* ws, cat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
