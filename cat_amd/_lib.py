@@ -159,6 +159,8 @@ SIGNATURES = {
     'cat_conv2d_fwd_ex': (c_i, [_G, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
     'cat_seg_up_logsoftmax': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_p]),
     'cat_seg_confusion': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
+    'cat_image_quantize': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p]),
+    'cat_image_normalize': (c_i, [c_p, c_l, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_i, c_p]),
     'cat_kid_poly_sums_ws_bytes': (C.c_size_t, [c_i, c_i]),
     'cat_kid_poly_sums': (c_i, [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_d, c_d, c_i, c_p, c_p, c_p]),
     'cat_fid_mean': (c_i, [c_p, c_i, c_i, c_p, c_p]),

@@ -274,9 +274,9 @@ class BaseInceptionDistiller(host.StepHost):
         aligned = self.opt.dataset_mode == 'aligned'
 
         def images(j):
-            out = {'input': E.tensor2im(self.real_A[j]), 'Sfake': E.tensor2im(self.Sfake_B[j]), 'Tfake': E.tensor2im(self.Tfake_B[j])}
+            out = {'input': E.image_of(self, self.real_A[j]), 'Sfake': E.image_of(self, self.Sfake_B[j]), 'Tfake': E.image_of(self, self.Tfake_B[j])}
             if aligned:
-                out['real'] = E.tensor2im(self.real_B[j])
+                out['real'] = E.image_of(self, self.real_B[j])
             return out
         want_miou = 'cityscapes' in str(getattr(self.opt, 'dataroot', '')) and getattr(self.opt, 'direction', 'AtoB') == 'BtoA'
         return E.evaluate(self, step, self.netG_student, self.set_input if aligned else self.set_single_input, images, True, want_miou,

@@ -122,8 +122,8 @@ class BaseSPADEDistiller(SPADEStep, host.StepHost):
         from . import evaluation as E
 
         def images(j):
-            return {'input': E.tensor2label(self.input_semantics[j], self.opt.input_nc + 2), 'real': E.tensor2im(self.real_B[j]),
-                    'Tfake': E.tensor2im(self.Tfake_B[j]), 'Sfake': E.tensor2im(self.Sfake_B[j])}
+            return {'input': E.tensor2label(self.input_semantics[j], self.opt.input_nc + 2), 'real': E.image_of(self, self.real_B[j]),
+                    'Tfake': E.image_of(self, self.Tfake_B[j]), 'Sfake': E.image_of(self, self.Sfake_B[j])}
         want_fid = not getattr(self.opt, 'no_fid', False)
         want_miou = 'cityscapes' in str(getattr(self.opt, 'dataroot', '')) and not getattr(self.opt, 'no_mIoU', False)
         return E.evaluate(self, step, self.modules_on_one_gpu.netG_student, self.set_input, images, want_fid, want_miou, save_all=save_image)

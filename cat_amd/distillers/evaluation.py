@@ -17,7 +17,12 @@ base_spade_distiller.py:166-170: `DRNSeg('drn_d_105', 19, pretrained=False)` + `
     model.miou_fn = lambda fakes, names: ...
 
 (`fakes` is the reference's list of NCHW CPU tensors, one per eval batch) still wins.  Either way the reference's bookkeeping comes back:
-`is_best`, `best_fid / best_mIoU`, the 3-evaluation running means and the `metric/*` dict that `Trainer` logs."""
+`is_best`, `best_fid / best_mIoU`, the 3-evaluation running means and the `metric/*` dict that `Trainer` logs.
+
+The teacher models evaluate through the same loop (models/pix2pix_model.py, models/cycle_gan_model.py: `evaluate`'s keyword arguments name
+their loaders, attributes and metric keys).  `model.eval_images = 'device'` keeps the generated set on the GPU as uint8
+(cat_amd.metric.DeviceImages, csrc/image_ops.hip) whenever every metric of the evaluation is the package's own; the image dumps then come
+from the same quantise kernel (`image_of`) and only uint8 crosses to the host."""
 import ntpath
 import os
 
@@ -70,10 +75,10 @@ def save_image(arr, path):
     Image.fromarray(arr).save(path.replace('.jpg', '.png'))
 
 
-def _track(model, value, best_attr, hist_attr, better):
+def _track(model, value, best_attr, hist_attr, better, is_best='is_best'):
     """best value + is_best + running mean of the last 3 evaluations (inception_distiller.py:251-256, 271-276)."""
     if better(value, getattr(model, best_attr)):
-        model.is_best = True
+        setattr(model, is_best, True)
         setattr(model, best_attr, value)
     hist = getattr(model, hist_attr)
     hist.append(value)
@@ -115,45 +120,102 @@ def attach_miou(model, state_dict, table_path=None, data_dir=None):
     return net
 
 
-def evaluate(model, step, student, feed, images, want_fid, want_miou, save_all=False):
-    """feed(batch): set_input / set_single_input; images(j): {'input'|'real'|'Tfake'|'Sfake': HWC uint8} of sample j of the batch."""
-    if getattr(model, 'eval_dataloader', None) is None:
-        raise RuntimeError('evaluate_model: attach model.eval_dataloader (the reference builds it from --dataroot in __init__; '
-                           'cat_amd does not own datasets)')
-    if want_fid and getattr(model, 'fid_fn', None) is None:
-        if getattr(model, 'inception_model', None) is not None and getattr(model, 'npz', None) is not None:
-            from .. import metric      # the reference's own call: get_fid(fakes, self.inception_model, self.npz, ...) (inception_distiller.py:246-249)
-            if getattr(model, 'fid_frechet', 'host') == 'device':
-                model.fid_fn = lambda fakes: metric.get_fid(fakes, model.inception_model, model.npz_device, device=model.device,
-                                                            batch_size=getattr(model.opt, 'eval_batch_size', 1), use_tqdm=False,
-                                                            frechet='device', cache=model.fid_cache)
-            else:
-                model.fid_fn = lambda fakes: metric.get_fid(fakes, model.inception_model, model.npz, device=model.device,
-                                                            batch_size=getattr(model.opt, 'eval_batch_size', 1), use_tqdm=False)
-        else:
-            raise RuntimeError('evaluate_model: call evaluation.attach_fid(model, fid_checkpoint, real_stat_path) or attach model.fid_fn '
-                               '(cat_amd/distillers/evaluation.py)')
-    if want_miou and getattr(model, 'miou_fn', None) is None:
-        if getattr(model, 'drn_model', None) is not None:
-            from .. import metric      # the reference's own call: get_mIoU(fakes, names, self.drn_model, ...) (inception_distiller.py:263-270)
-            table_path = getattr(model, 'miou_table_path', None) or model.opt.table_path
-            data_dir = getattr(model, 'miou_data_dir', None) or model.opt.cityscapes_path
-            model.miou_fn = lambda fakes, names: metric.get_mIoU(fakes, names, model.drn_model, model.device, table_path=table_path,
-                                                                 data_dir=data_dir, batch_size=getattr(model.opt, 'eval_batch_size', 1),
-                                                                 num_workers=getattr(model.opt, 'num_threads', 8), use_tqdm=False)
-        else:
-            raise RuntimeError('evaluate_model: call evaluation.attach_miou(model, drn_checkpoint, table_path, data_dir) or attach model.miou_fn = '
-                               'lambda fakes, names: ... (cat_amd/distillers/evaluation.py)')
-    model.is_best = False
-    save_dir = os.path.join(model.opt.log_dir, 'eval', str(step))
+def image_of(model, t):
+    """tensor2im of one sample for the image dumps.  A model with eval_images == 'device' quantises a device tensor with the kernel that
+    fills the DeviceImages set (cat_image_quantize: the same bytes), so only uint8 crosses to the host; everything else is tensor2im."""
+    if getattr(model, 'eval_images', 'host') == 'device' and isinstance(t, torch.Tensor) and t.is_cuda:
+        from ..metric import images
+        return images.tensor2im(t)
+    return tensor2im(t)
+
+
+def _builtin(fn):
+    fn.cat_builtin = True      # evaluate keeps its own callables in model.fid_fn / model.miou_fn: the mark tells them from an attached one
+    return fn
+
+
+def _fid_callable(model, npz):
+    """(fid_fn, built_in): an attached model.fid_fn wins; otherwise the reference's own call get_fid(fakes, self.inception_model, self.npz,
+    ...) (inception_distiller.py:246-249) on cat_amd.metric, `npz` naming the attribute that holds the real set's statistics."""
+    fn = getattr(model, 'fid_fn', None)
+    if fn is not None and not getattr(fn, 'cat_builtin', False):
+        return fn, False
+    if getattr(model, 'inception_model', None) is None or getattr(model, npz, None) is None:
+        raise RuntimeError('evaluate_model: call evaluation.attach_fid(model, fid_checkpoint, real_stat_path) or attach model.fid_fn '
+                           '(cat_amd/distillers/evaluation.py)')
+    from .. import metric
+    if getattr(model, 'fid_frechet', 'host') == 'device':
+        cache = model.fid_cache if npz == 'npz' else model.fid_cache.setdefault(npz, {})
+        fn = lambda fakes: metric.get_fid(fakes, model.inception_model, getattr(model, npz + '_device'), device=model.device,      # noqa: E731
+                                          batch_size=getattr(model.opt, 'eval_batch_size', 1), use_tqdm=False, frechet='device', cache=cache)
+    else:
+        fn = lambda fakes: metric.get_fid(fakes, model.inception_model, getattr(model, npz), device=model.device,      # noqa: E731
+                                          batch_size=getattr(model.opt, 'eval_batch_size', 1), use_tqdm=False)
+    model.fid_fn = _builtin(fn)
+    return fn, True
+
+
+def _miou_callable(model):
+    """(miou_fn, built_in): an attached model.miou_fn wins; otherwise get_mIoU(fakes, names, self.drn_model, ...) (inception_distiller.py:263-270)."""
+    fn = getattr(model, 'miou_fn', None)
+    if fn is not None and not getattr(fn, 'cat_builtin', False):
+        return fn, False
+    if getattr(model, 'drn_model', None) is None:
+        raise RuntimeError('evaluate_model: call evaluation.attach_miou(model, drn_checkpoint, table_path, data_dir) or attach model.miou_fn = '
+                           'lambda fakes, names: ... (cat_amd/distillers/evaluation.py)')
+    from .. import metric
+    table_path = getattr(model, 'miou_table_path', None) or model.opt.table_path
+    data_dir = getattr(model, 'miou_data_dir', None) or model.opt.cityscapes_path
+    fn = lambda fakes, names: metric.get_mIoU(fakes, names, model.drn_model, model.device, table_path=table_path, data_dir=data_dir,      # noqa: E731
+                                              batch_size=getattr(model.opt, 'eval_batch_size', 1), num_workers=getattr(model.opt, 'num_threads', 8),
+                                              use_tqdm=False)
+    model.miou_fn = _builtin(fn)
+    return fn, True
+
+
+def evaluate(model, step, student, feed, images, want_fid, want_miou, save_all=False, *, loader='eval_dataloader', run=None, fake='Sfake_B',
+             subdir='', npz='npz', is_best='is_best', best_fid='best_fid', fids='fids', fid_key='metric/fid', best_miou='best_mIoU',
+             mious='mIoUs', miou_key='metric/mIoU'):
+    """feed(batch): set_input / set_single_input; images(j): {'input'|'real'|'Tfake'|'Sfake': HWC uint8} of sample j of the batch.
+    student: the generator, or the generators, that run in eval mode during the loop.  The keyword arguments name what differs between the
+    models, and their defaults are the distillers': `loader` the attribute holding the dataloader, `run` the function of one test pass
+    (model.test), `fake` the attribute holding the generated batch, `subdir` the directory under eval/<step> the image kinds go to, `npz` the
+    attribute with the real statistics, `is_best` / `best_*` / `fids` / `mious` the bookkeeping attributes and `*_key` the metric names.
+
+    model.eval_images == 'device' (the default is 'host', the reference's list of CPU float tensors): the generated batches are quantised
+    into a metric.DeviceImages where they lie and the package's own metrics read that set.  An attached fid_fn / miou_fn has the
+    reference's contract and forces the host path for the evaluation."""
+    if getattr(model, loader, None) is None:
+        raise RuntimeError('evaluate_model: attach model.%s (the reference builds it from --dataroot in __init__; '
+                           'cat_amd does not own datasets)' % loader)
+    mode = getattr(model, 'eval_images', 'host')
+    if mode not in ('host', 'device'):
+        raise ValueError("evaluate_model: model.eval_images must be 'host' or 'device' (got %r)" % (mode,))
+    fid_fn, fid_own = _fid_callable(model, npz) if want_fid else (None, True)
+    miou_fn, miou_own = _miou_callable(model) if want_miou else (None, True)
+    on_device = mode == 'device' and fid_own and miou_own
+    setattr(model, is_best, False)
+    save_dir = os.path.join(model.opt.log_dir, 'eval', str(step), subdir)
     os.makedirs(save_dir, exist_ok=True)
-    student.eval()
-    fakes, names, cnt = [], [], 0
+    students = list(student) if isinstance(student, (list, tuple)) else [student]
+    run = model.test if run is None else run
+    for net in students:
+        net.eval()
+    names, cnt = [], 0
+    if on_device:
+        from ..metric import DeviceImages
+        fakes = DeviceImages()
+    else:
+        fakes = []
     try:
-        for batch in model.eval_dataloader:
+        batches = getattr(model, loader)
+        for batch in batches:
             feed(batch)
-            model.test()
-            fakes.append(model.Sfake_B.detach().cpu().contiguous())
+            run()
+            out = getattr(model, fake)
+            if on_device and len(fakes) == 0 and hasattr(batches, '__len__'):
+                fakes = DeviceImages(capacity=out.shape[0] * len(batches))      # sized once where the loader tells: no growth copies
+            fakes.append(out if on_device else out.detach().cpu().contiguous())
             for j in range(len(model.image_paths)):
                 name = os.path.splitext(ntpath.basename(model.image_paths[j]))[0]
                 names.append(name)
@@ -162,16 +224,19 @@ def evaluate(model, step, student, feed, images, want_fid, want_miou, save_all=F
                         save_image(arr, os.path.join(save_dir, kind, '%s.png' % name))
                 cnt += 1
     finally:
-        student.train()
+        for net in students:
+            net.train()
     ret = {}
     if want_fid:
-        fid = float(model.fid_fn(fakes))
-        ret['metric/fid'] = fid
-        ret['metric/fid-mean'] = _track(model, fid, 'best_fid', 'fids', lambda a, b: a < b)
-        ret['metric/fid-best'] = model.best_fid
+        fid = float(fid_fn(fakes))
+        ret[fid_key] = fid
+        ret[fid_key + '-mean'] = _track(model, fid, best_fid, fids, lambda a, b: a < b, is_best)
+        ret[fid_key + '-best'] = getattr(model, best_fid)
     if want_miou:
-        miou = float(model.miou_fn(fakes, names))
-        ret['metric/mIoU'] = miou
-        ret['metric/mIoU-mean'] = _track(model, miou, 'best_mIoU', 'mIoUs', lambda a, b: a > b)
-        ret['metric/mIoU-best'] = model.best_mIoU
+        miou = float(miou_fn(fakes, names))
+        ret[miou_key] = miou
+        ret[miou_key + '-mean'] = _track(model, miou, best_miou, mious, lambda a, b: a > b, is_best)
+        ret[miou_key + '-best'] = getattr(model, best_miou)
     return ret
+
+

@@ -37,13 +37,17 @@ def pooled_features(model, batch, pool=None):
 
 
 def feature_batches(load, n, model, batch_size, device, full_only=False, pool=None):
-    """Yields (start, end, features) per batch of n images; load(start, end) returns the [B, 3, H, W] numpy batch as the network takes it.
+    """Yields (start, end, features) per batch of n images; load(start, end) returns the [B, 3, H, W] numpy batch as the network takes it, or
+    the same batch as a float32 device tensor (DeviceImages.batch), which goes in as it is.
     full_only: images beyond the last full batch are dropped; otherwise the last batch may be short."""
     model.eval()
     stop = n - n % batch_size if full_only else n
     for start in range(0, stop, batch_size):
         end = min(start + batch_size, stop)
-        yield start, end, pooled_features(model, torch.from_numpy(load(start, end)).type(torch.FloatTensor).to(device), pool)
+        batch = load(start, end)
+        if not isinstance(batch, torch.Tensor):
+            batch = torch.from_numpy(batch).type(torch.FloatTensor).to(device)
+        yield start, end, pooled_features(model, batch, pool)
 
 
 def add_inception_arguments(parser, batch_size):      # returns the parser

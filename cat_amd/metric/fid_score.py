@@ -20,7 +20,12 @@ NS_REL_STEP = 1e-14         # a step counts while the trace still grows by more 
 
 
 def _scaled(ims):
-    """load(start, end) over float images [N, H, W, 3] (or [N, 3, H, W]) in [0, 255]: the NCHW view of a slice, scaled IN PLACE"""
+    """load(start, end) over float images [N, H, W, 3] (or [N, 3, H, W]) in [0, 255]: the NCHW view of a slice, scaled IN PLACE.  A
+    DeviceImages set (cat_amd/metric/images.py) hands over the same `u8 / 255` batch as a device activation; nothing of it is changed."""
+    from .images import DeviceImages
+    if isinstance(ims, DeviceImages):
+        return ims.batch
+
     def load(start, end):
         images = ims[start:end] if ims.shape[1] == 3 else ims[start:end].transpose((0, 3, 1, 2))
         images /= 255

@@ -25,7 +25,11 @@ SCALAR_KEYS = ('tr_xy', 'sq_xx', 'sq_yy', 'sq_xy')                      # [S] ea
 
 # ---------------------------------------------------------------------------------------------------------------- features
 def _activations(load, n, model, batch_size, dims, device, verbose):
-    """The loop of get_activations (:51-97): `load(start, end)` returns the float32 [B, 3, H, W] batch in [0, 1]."""
+    """The loop of get_activations (:51-97): `load(start, end)` returns the float32 [B, 3, H, W] batch in [0, 1]; a DeviceImages set in its
+    place hands over its own `u8 / 255` batches, on the device."""
+    from .images import DeviceImages
+    if isinstance(load, DeviceImages):
+        load = load.batch
     if n % batch_size != 0:
         print(('Warning: number of images is not a multiple of the '
                'batch size. Some samples are going to be ignored.'))
@@ -55,7 +59,11 @@ def _load_files(files):
 
 
 def _load_uint8(ims):
-    """uint8 [N, H, W, 3] images exactly as `_load_files` hands over the same images read back from PNG files"""
+    """uint8 [N, H, W, 3] images exactly as `_load_files` hands over the same images read back from PNG files (a DeviceImages set: itself)"""
+    from .images import DeviceImages
+    if isinstance(ims, DeviceImages):
+        return ims
+
     def load(start, end):
         return (ims[start:end].astype(np.float32) / 255.).transpose((0, 3, 1, 2))
     return load

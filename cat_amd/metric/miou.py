@@ -92,17 +92,26 @@ def confusion(logp, label, hist, n_classes, pred=None):
 
 def confusion_matrix(ims, names, model, device, table_path, data_dir, batch_size, num_classes, progress=None, preds=None):
     """The loop of `test` (:220-241) -> int64 [n, n] numpy matrix.  ims: uint8 [N, H, W, 3]; preds: optional list that receives the uint8
-    class maps (one [B, Hl, Wl] array per batch)."""
+    class maps (one [B, Hl, Wl] array per batch).  ims may be a DeviceImages set (cat_amd/metric/images.py): every batch is then normalised
+    from the bytes where they lie (cat_image_normalize: the values of normalize_images), and no float copy of the set exists."""
+    from .images import DeviceImages
     labels = read_label_list(names, table_path)
     model.eval()
     device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-    x = normalize_images(ims).to(device)      # the whole normalised set goes up once
+    if isinstance(ims, DeviceImages):
+        def load(s):
+            return ims.batch(s, s + batch_size, MEAN, STD)
+    else:
+        x = normalize_images(ims).to(device)      # the whole normalised set goes up once
+
+        def load(s):
+            return x[s:s + batch_size]
     hist = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=device)
     batches = range(0, len(names), batch_size)
     with torch.no_grad():
         for s in (progress(batches) if progress is not None else batches):
             lab = torch.from_numpy(load_labels(labels[s:s + batch_size], data_dir)).to(device)
-            final = model(x[s:s + batch_size])[0]
+            final = model(load(s))[0]
             pred = torch.empty_like(lab) if preds is not None else None
             confusion(final, lab, hist, num_classes, pred)
             if preds is not None:

@@ -1,7 +1,8 @@
 """BaseModel: the host-side glue of models/base_model.py:12-232 that `train.py` / `Trainer` touch (device, save_dir, setup,
 schedulers, loss dictionary, requires_grad toggling, checkpoints with the reference's file names and state_dict keys).  Dataset
-loaders stay with the reference; FID / mIoU evaluation is the distillers' path (cat_amd/distillers/evaluation.py,
-cat_amd/metric: InceptionV3 and DRN-D-105 on the HIP kernels)."""
+loaders stay with the reference: the integrator attaches the evaluation dataloaders.  `evaluate_model` of the three
+models goes through cat_amd/distillers/evaluation.evaluate; the metric networks (cat_amd/metric: InceptionV3 and DRN-D-105 on the HIP kernels)
+are created on first use from the checkpoints the options name (`_prepare_evaluation`)."""
 from abc import ABC, abstractmethod
 
 import torch
@@ -58,7 +59,35 @@ class BaseModel(host.StepHost, ABC):
         self.dp = reducer
         reducer.broadcast_parameters([getattr(self, 'net' + n) for n in self.model_names])
 
-    def evaluate_model(self, step):
-        raise NotImplementedError('teacher-training models: evaluate with the distillers\' path -- cat_amd.distillers.evaluation.evaluate + '
-                                  'attach_fid / attach_miou (InceptionV3 pool3 features and the DRN-D-105 cityscapes mIoU on the HIP kernels, '
-                                  'cat_amd.metric); mIoU needs the reference\'s DRN checkpoint and the cityscapes data (SURVEY §2 rows 18-19)')
+    def _prepare_evaluation(self, stats, want_miou):
+        """What the reference's __init__ builds for evaluation, created on first use: the inception model (opt.inception_path) and the real
+        statistics -- stats = {attribute: name of the option with its file} -- unless a fid_fn is attached; the DRN model (opt.drn_path,
+        opt.table_path, opt.cityscapes_path) if want_miou, unless a miou_fn is attached."""
+        import numpy as np
+
+        from ..distillers import evaluation as E
+
+        def attached(name):
+            fn = getattr(self, name, None)
+            return fn is not None and not getattr(fn, 'cat_builtin', False)
+        if not attached('fid_fn'):
+            if getattr(self, 'inception_model', None) is None:
+                ckpt = getattr(self.opt, 'inception_path', None)
+                if ckpt is None:
+                    raise RuntimeError('evaluate_model: FID needs the torchvision-keyed FID inception checkpoint (opt.inception_path), an '
+                                       'attached model.inception_model or an attached model.fid_fn')
+                from ..metric.features import load_inception
+                self.inception_model = load_inception(2048, ckpt, self.device, 'FID')
+            for attr, option in stats.items():
+                if getattr(self, attr, None) is None:
+                    path = getattr(self.opt, option, None)
+                    if path is None:
+                        raise RuntimeError('evaluate_model: FID needs the real statistics {mu, sigma} (opt.%s), an attached model.%s or an '
+                                           'attached model.fid_fn' % (option, attr))
+                    setattr(self, attr, np.load(path))
+        if want_miou and not attached('miou_fn') and getattr(self, 'drn_model', None) is None:
+            ckpt = getattr(self.opt, 'drn_path', None)
+            if ckpt is None:
+                raise RuntimeError('evaluate_model: the cityscapes mIoU needs the DRN-D-105 checkpoint (opt.drn_path; evaluation.attach_miou) '
+                                   'or an attached model.miou_fn = lambda fakes, names: ...')
+            E.attach_miou(self, ckpt, getattr(self.opt, 'table_path', None), getattr(self.opt, 'cityscapes_path', None))

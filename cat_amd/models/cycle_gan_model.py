@@ -15,6 +15,7 @@ from .image_pool import ImagePool
 
 
 class CycleGANModel(BaseModel):
+    eval_images = 'device'      # evaluate_model keeps the generated set on the GPU as uint8 (metric.DeviceImages); 'host' = the reference's list
     _FLAGS = [  # cycle_gan_model.py:27-108
         ('--restore_G_A_path', dict(type=str, default=None)),
         ('--restore_D_A_path', dict(type=str, default=None)),
@@ -147,3 +148,23 @@ class CycleGANModel(BaseModel):
         generator = getattr(self, 'netG_%s' % direction[0])
         with torch.no_grad():
             self.fake_B = generator(self.real_A)
+
+    def evaluate_model(self, step, save_image=False):
+        """reference cycle_gan_model.py:310-365 through distillers/evaluation.evaluate, once per direction: both generators in eval mode,
+        `eval_dataloader_<direction>`, set_single_input + test_single_side, <direction>/input and <direction>/fake image dumps, FID against
+        npz_B for AtoB and npz_A for BtoA.  The bookkeeping pairs as the reference's does: AtoB sets is_best_A and best_fid_B / fids_B, BtoA
+        is_best_B and best_fid_A / fids_A."""
+        from ..distillers import evaluation as E
+        self._prepare_evaluation({'npz_A': 'real_stat_A_path', 'npz_B': 'real_stat_B_path'}, False)
+        self.is_best_A = self.is_best_B = False
+
+        def images(j):
+            return {'input': E.image_of(self, self.real_A[j]), 'fake': E.image_of(self, self.fake_B[j])}
+        ret = {}
+        for direction in ('AtoB', 'BtoA'):
+            s = direction[-1]
+            ret.update(E.evaluate(self, step, [self.netG_A, self.netG_B], self.set_single_input, images, True, False, save_all=save_image,
+                                  loader='eval_dataloader_' + direction, run=lambda: self.test_single_side(direction), fake='fake_B',
+                                  subdir=direction, npz='npz_' + s, is_best='is_best_' + direction[0], best_fid='best_fid_' + s, fids='fids_' + s,
+                                  fid_key='metric/fid_' + s))
+        return ret

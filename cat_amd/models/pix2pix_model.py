@@ -9,6 +9,7 @@ from .base_model import BaseModel
 
 
 class Pix2PixModel(BaseModel):
+    eval_images = 'device'      # evaluate_model keeps the generated set on the GPU as uint8 (metric.DeviceImages); 'host' = the reference's list
     _FLAGS = [  # pix2pix_model.py:21-65
         ('--restore_G_path', dict(type=str, default=None)),
         ('--restore_D_path', dict(type=str, default=None)),
@@ -97,3 +98,14 @@ class Pix2PixModel(BaseModel):
         if self.dp is not None:
             self.dp.reduce(self.optimizer_G)
         self.optimizer_G.step()
+
+    def evaluate_model(self, step, save_image=False):
+        """reference pix2pix_model.py:209-281 through distillers/evaluation.evaluate: netG in eval mode over `self.eval_dataloader`,
+        input / real / fake image dumps, FID always and the cityscapes mIoU iff 'cityscapes' is in opt.dataroot."""
+        from ..distillers import evaluation as E
+        want_miou = 'cityscapes' in str(getattr(self.opt, 'dataroot', ''))
+        self._prepare_evaluation({'npz': 'real_stat_path'}, want_miou)
+
+        def images(j):
+            return {'input': E.image_of(self, self.real_A[j]), 'real': E.image_of(self, self.real_B[j]), 'fake': E.image_of(self, self.fake_B[j])}
+        return E.evaluate(self, step, self.netG, self.set_input, images, True, want_miou, save_all=save_image, fake='fake_B')

@@ -138,8 +138,8 @@ class SPADEModel(SPADEStep, BaseModel):
             self._prepare_evaluation()
 
         def images(j):
-            return {'input': E.tensor2label(self.input_semantics[j], self.opt.input_nc + 2), 'real': E.tensor2im(self.real_B[j]),
-                    'fake': E.tensor2im(self.fake_B[j])}
+            return {'input': E.tensor2label(self.input_semantics[j], self.opt.input_nc + 2), 'real': E.image_of(self, self.real_B[j]),
+                    'fake': E.image_of(self, self.fake_B[j])}
         want_fid, want_miou = self._want_metrics()
         return E.evaluate(_EvalView(self), step, self.modules_on_one_gpu.netG, self.set_input, images, want_fid, want_miou, save_all=save_image)
 

@@ -334,6 +334,17 @@ int cat_seg_up_logsoftmax(const float* x, int xcs, int N, int h, int w, int C, c
  * across calls; label: uint8 [N][Hl][Wl] (255 = ignore); pred: uint8 [N][Hl][Wl] or NULL. */
 int cat_seg_confusion(const float* logp, int lcs, int N, int h, int w, int C, const unsigned char* label, int Hl, int Wl, int n_classes,
                       long long* hist, unsigned char* pred, cat_stream_t stream);
+/* ---- evaluation path: the generated image set as uint8 on the device (csrc/image_ops.hip, cat_amd/metric/images.py). ---- */
+/* util.tensor2im (utils/util.py:58-88): byte c of out pixel = (uint8) clip((x_c + 1) / 2 * 255, 0, 255), every float32 operation rounded on its
+ * own (no fused multiply-add), truncating cast; +inf -> 255, -inf and NaN -> 0.  x: NHWC float32 [N][H][W][xcs], 16-byte aligned, C in 1..4;
+ * out: uint8 [*][H][W][4], one dword per pixel with bytes [C, 4) = 0; the N images are written from image img_off of the set on (64-bit
+ * offsets: a set may exceed 2^31 bytes). */
+int cat_image_quantize(const float* x, int xcs, int N, int H, int W, int C, unsigned char* out, long long img_off, cat_stream_t stream);
+/* ToTensor + Normalize (metric/mIoU_score.py:28-51): y_c = ((u8_c / 255) - mean_c) / std_c with correctly rounded float32 division and
+ * subtraction, for the N images from image img_off of the uint8 [*][H][W][4] set on; y: NHWC float32 [N][H][W][ycs], 16-byte aligned,
+ * padding channels [C, 4) written as 0.  mean 0 / std 1 is FID's and KID's `u8 / 255`. */
+int cat_image_normalize(const unsigned char* u8, long long img_off, int N, int H, int W, int C, float mean0, float mean1, float mean2,
+                        float mean3, float std0, float std1, float std2, float std3, float* y, int ycs, cat_stream_t stream);
 /* ---- evaluation path: the kernel inception distance (metric/kid_score.py:184-281: polynomial_mmd + _mmd2_and_variance). ---- */
 /* For each of S subsets, the sums _mmd2_and_variance reads of the three polynomial kernels K = (gamma * A B^T + coef0)^degree of (X, X), (Y, Y)
  * and (X, Y), in float64 on the f64 MFMA; no K is ever stored.  X: [nx][d], Y: [ny][d] float32 (may be one buffer), d % 4 == 0, 16-byte
