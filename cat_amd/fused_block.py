@@ -23,6 +23,7 @@ weight-gradient batch), the stage-2 launch with the closing pw_bn and the residu
 Same arithmetic as the general path (same conv accumulation order per output, statistics merged pairwise instead of sequentially):
 results agree to ~1e-6 relative; tests/test_fused_block_gpu.py pins both against the CPU oracle."""
 import os
+import weakref
 
 import torch
 
@@ -36,6 +37,25 @@ from . import fused_unit as U
 from .fused_unit import prepare_many, prepare_plans      # noqa: F401  (the generator's per-step preparation: inception_generator.py)
 
 _ENABLED = os.environ.get('CAT_FUSED_BLOCK', '1') != '0'
+# Per-block opt-in to this path in eval() mode: cat_amd.infer.StudentRunner registers the blocks of the network it owns.  An InstanceNorm2d
+# without running statistics computes the same function in eval() as in train(), so forward(block, x, save=None) is the block's eval
+# forward as it stands: per-sample statistics collected and finalized, no running statistics to touch (fused_unit.slices passes none).
+# A block that is not registered takes, in eval mode, the path it always took.  The registry holds the block OBJECTS weakly and nothing is
+# written on the module: a copy.deepcopy of an owned network (shrink_model, load_pretrained_student copy the teacher) is not owned.
+# The value is the owner's LDS-tile threshold for this block (fewest 8 x 16 output tiles; None: ops' process-wide one).
+_EVAL_OWNED = weakref.WeakKeyDictionary()
+
+
+def own_eval(block, min_tiles=None):
+    _EVAL_OWNED[block] = (None if min_tiles is None else int(min_tiles),)
+
+
+def disown_eval(block):
+    _EVAL_OWNED.pop(block, None)
+
+
+def eval_owned(block):
+    return block in _EVAL_OWNED
 
 
 def set_enabled(on):
@@ -54,14 +74,17 @@ def _dropout(block):
 
 
 def applicable(block, x):
-    if not _ENABLED or not block.training or not x.is_cuda or block.padding_type not in ('reflect', 'zero'):
+    if not _ENABLED or not x.is_cuda or block.padding_type not in ('reflect', 'zero'):
+        return False
+    owner = None if block.training else _EVAL_OWNED.get(block)
+    if not block.training and (owner is None or torch.is_grad_enabled()):
         return False
     if _dropout(block) is None:
         return False
     if len(block.res_ops) + len(block.dw_ops) == 0 or not ops.is_act(x):
         return False
     n, c, h, w = x.shape
-    if not ops.tconv_applicable(n, h, w, c, 3, 3, 1, 1):
+    if not ops.tconv_applicable(n, h, w, c, 3, 3, 1, 1, min_tiles=owner[0] if owner is not None else None):
         return False
     norms = [op[1][1] for op in block.res_ops] + [op[0][1] for op in block.dw_ops] + [op[2][1] for op in block.dw_ops] + [block.pw_bn]
     kind = type(norms[0])
@@ -75,6 +98,8 @@ def applicable(block, x):
         return False
     if kind is cnn.InstanceNorm2d and any(m.track_running_stats for m in norms):
         return False
+    if not block.training and (kind is not cnn.InstanceNorm2d or any(m.training for m in norms) or _dropout(block)[0] != 0):
+        return False      # eval mode: only norms that keep no statistics compute train()'s function (BatchNorm: cat_amd/frozen.py)
     first_act = block.res_ops[0][1][2] if len(block.res_ops) else block.dw_ops[0][0][2]
     if cnn._act_code(first_act)[0] not in (L.ACT_RELU, L.ACT_LRELU):     # the staging paths apply ReLU / LeakyReLU only (nn.ReLU6: general path)
         return False

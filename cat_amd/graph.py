@@ -16,6 +16,24 @@ import os
 import torch
 
 
+def capture(run, warmup):
+    """`run(i)` `warmup` times eagerly on a side stream (settles lazy state: flattened optimiser buffers, weight re-housing, folds, filter
+    packs, workspaces), then once more, run(warmup), under capture -> (graph, what that call returned).  The graph addresses what those
+    calls allocated: static buffers `run` reads, the graph's pool, and every cached operand a kernel was handed by pointer."""
+    cur = torch.cuda.current_stream()
+    side = torch.cuda.Stream()
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        for i in range(warmup):
+            run(i)
+    cur.wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = run(warmup)
+    return graph, out
+
+
 class GraphedStep:
     def __init__(self, model, example_batch, warmup=3):
         if getattr(model, 'dp', None) is not None:
@@ -25,19 +43,10 @@ class GraphedStep:
         # outside the graph); non-tensor entries (image paths) are refreshed per call
         dev = getattr(model, 'device', None) or torch.device('cuda', torch.cuda.current_device())
         self.static = {k: (v.to(dev).clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()}
-        cur = torch.cuda.current_stream()
-        side = torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            for i in range(warmup):          # settles lazy state: flattened optimiser buffers, weight re-housing, workspaces
-                model.set_input(self.static)
-                model.optimize_parameters(i)
-        cur.wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        def step(i):
             model.set_input(self.static)
-            model.optimize_parameters(warmup)
+            model.optimize_parameters(i)
+        self.graph, _ = capture(step, warmup)      # `warmup` eager steps, then step number `warmup` captured
         self.replays = 0
         # the graph's outputs are the tensors the model's attributes were bound to DURING the capture (loss terms, fake images, input
         # fields, tapped activations).  An eager fallback step rebinds those attributes to fresh tensors; the bindings are restored before

@@ -290,6 +290,12 @@ def seg_at(segmap, size):
     return out
 
 
+def forget_seg_pyramid(segmap):
+    """Drop the resized copies seg_at keeps on `segmap`.  A hipGraph capture that reads a static input buffer calls this first: the copies of
+    the warm-up runs carry the buffer's current version, and a capture that found them would bake THEIR values in instead of the resize."""
+    segmap.__dict__.pop('_cat_pyramid', None)
+
+
 class InceptionSPADE(nn.Module):
     """SPADE with inception-style gamma/beta branches (reference inception_modules.py:564-769):
     out = param_free_norm(x) * (1 + gamma) + beta, [gamma | beta] = sum_k res_k(seg) + sum_k dw_k(seg)."""

@@ -356,7 +356,7 @@ def set_tconv_min_tiles(n):
     return old
 
 
-def tconv_applicable(n, h, w, cout, kh, kw, stride, pad, cin=None):
+def tconv_applicable(n, h, w, cout, kh, kw, stride, pad, cin=None, min_tiles=None):
     """Stride-1 "same" 3x3 / 5x5 convolutions with enough output tiles to fill the chip go through csrc/conv_pk.hip (forward and
     input gradient); tiny planes (the SPADE generators' 4x8 .. 16x32 stages) keep the split-K im2col kernels, Cout <= 3 the direct ones.
     Wide layers the direct-to-LDS 128 x 128 x 32 GEMM tiles accept (reduction channels % 32 == 0, more than 96 output channels: e.g. the
@@ -365,7 +365,8 @@ def tconv_applicable(n, h, w, cout, kh, kw, stride, pad, cin=None):
         return False
     if cin is not None and cin % 32 == 0 and cout > 96:
         return False
-    return n * ((h + 7) // 8) * ((w + 15) // 16) >= _TCONV_MIN_TILES
+    # min_tiles: a caller's own threshold (an inference runner's fused blocks, fused_block.own_eval) instead of the process-wide one
+    return n * ((h + 7) // 8) * ((w + 15) // 16) >= (_TCONV_MIN_TILES if min_tiles is None else min_tiles)
 
 
 def packed_filter(weight, wcl, mode):
