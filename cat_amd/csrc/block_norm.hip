@@ -206,8 +206,8 @@ __global__ __launch_bounds__(256) void affine_res_kernel(const float* __restrict
 
 // Backward of ReflectionPad2d with separate pixel strides (channel slices of wider buffers) and an optional addend:
 // dx[n,y,x,:] = add[n,y,x,:] + sum of the (up to 3 x 3) padded positions that mirror onto (y, x)
-__global__ __launch_bounds__(256) void reflect_fold2_kernel(const float* __restrict__ dxp, int pcs, float* __restrict__ dx, int dcs,
-                                                            const float* __restrict__ add, int acs, int N, int H, int W, int nq, int pad) {
+__global__ __launch_bounds__(256) void reflect_fold_kernel(const float* __restrict__ dxp, int pcs, float* __restrict__ dx, int dcs,
+                                                           const float* __restrict__ add, int acs, int N, int H, int W, int nq, int pad) {
   const int64_t total = (int64_t)N * H * W * nq;
   const int Hp = H + 2 * pad, Wp = W + 2 * pad;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -432,8 +432,7 @@ int cat_affine_res_fwd(const float* x, int xcs, const float* scale, const float*
   CAT_REQUIRE((xcs & 3) == 0 && (ycs & 3) == 0 && (C4 & 3) == 0 && C4 <= xcs && C4 <= ycs, "affine_res: channel layout");
   CAT_REQUIRE((int64_t)Pg * (C4 / 4) < (int64_t)4000000000LL, "affine_res: group too large");
   cat::ProfScope prof("affine_res", 0.0, (res ? 12.0 : 8.0) * (double)G * Pg * C4, stream);
-  int64_t b = ((int64_t)Pg * (C4 / 4) + 255) / 256;
-  const int gx = (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+  const int gx = cat::ew_grid((int64_t)Pg * (C4 / 4), 4096);
   affine_res_kernel<<<dim3(gx, G), 256, 0, (hipStream_t)stream>>>(x, xcs, scale, shift, sstride, res, rcs, y, ycs, Pg, C4 / 4, act, slope);
   return cat::check_launch("affine_res");
 }
@@ -444,9 +443,17 @@ int cat_reflect_pad_bwd2(const float* dxp, int pcs, float* dx, int dcs, const fl
               "reflect_pad_bwd2: bad geometry");
   cat::ProfScope prof("reflect_pad_bwd", 0.0, 8.0 * N * H * W * C4, stream);
   const int64_t total = (int64_t)N * H * W * (C4 / 4);
-  int64_t b = (total + 255) / 256;
-  reflect_fold2_kernel<<<(int)(b < 1 ? 1 : (b > 8192 ? 8192 : b)), 256, 0, (hipStream_t)stream>>>(dxp, pcs, dx, dcs, add, acs, N, H, W, C4 / 4, pad);
+  reflect_fold_kernel<<<cat::ew_grid(total, 8192), 256, 0, (hipStream_t)stream>>>(dxp, pcs, dx, dcs, add, acs, N, H, W, C4 / 4, pad);
   return cat::check_launch("reflect_pad_bwd2");
+}
+
+// the dense form: one pixel stride cs for both tensors, no addend
+int cat_reflect_pad_bwd(const float* dxp, float* dx, int N, int H, int W, int C, int cs, int pad, cat_stream_t stream) {
+  cat::ProfScope prof("reflect_pad_bwd", 0.0, 8.0 * N * H * W * cs, stream);
+  CAT_REQUIRE(cs % 4 == 0 && cs >= C && pad < H && pad < W, "reflect_pad_bwd: bad geometry");
+  const int64_t total = (int64_t)N * H * W * (cs / 4);
+  reflect_fold_kernel<<<cat::ew_grid(total, 8192), 256, 0, (hipStream_t)stream>>>(dxp, cs, dx, cs, nullptr, 0, N, H, W, cs / 4, pad);
+  return cat::check_launch("reflect_pad_bwd");
 }
 
 int cat_dwm_fwd(const cat_dwm_t* g, const float* x, const float* scale, const float* shift, const float* w25, const float* bias, float* y,

@@ -78,6 +78,35 @@ static inline void lds_optin(LdsOptIn& st, const void* fn, int bytes) {
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
+// Workgroups of a 256-lane grid-stride walk over `items`: clamp(cdiv(items, 256), 1, cap).
+static inline int ew_grid(int64_t items, int cap) {
+  const int64_t b = (items + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+// Column reductions and pixel walks over [P][cs] (norm.hip, spade.hip, elementwise.hip): a workgroup is ppl pixel lanes x zq channel quads
+// (every access a float4, a wave touches whole pixels), nz such workgroups cover the nq quads of a pixel, nb of them share the pixels.
+// nb aims at `target` workgroups over all `groups`, keeps at least min_pix pixels per pixel lane and stays within cap (INT_MAX: none).
+struct ColPlan {
+  int nq, nz, zq, ppl, nb;
+};
+static inline int col_blocks(int64_t P, int ppl, int groups_nz, int target, int min_pix, int cap) {
+  int nb = cdiv(target, groups_nz);
+  if (nb > cap) nb = cap;
+  const int maxb = cdiv(P, (int64_t)ppl * min_pix);
+  if (nb > maxb) nb = maxb;
+  return nb < 1 ? 1 : nb;
+}
+static inline ColPlan col_plan(int64_t P, int cs, int groups, int target, int min_pix, int cap) {
+  ColPlan p;
+  p.nq = cs / 4;
+  p.nz = cdiv(p.nq, 256);
+  p.zq = cdiv(p.nq, p.nz);  // quads per z-block (<= 256)
+  p.ppl = 256 / p.zq;
+  p.nb = col_blocks(P, p.ppl, groups * p.nz, target, min_pix, cap);
+  return p;
+}
+
 __device__ __forceinline__ float apply_act(float v, int act, float slope) {
   switch (act) {
     case CAT_ACT_RELU: return v > 0.f ? v : 0.f;
@@ -188,6 +217,41 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// A ColPlan workgroup's lane: channel quad cq (cq_l within z-block z), pixel lane pl; inactive lanes only take part in the combine.
+struct ColLanes {
+  int cq_l, pl, cq;
+  bool active;
+};
+__device__ __forceinline__ ColLanes col_lanes(int z, int zq, int ppl, int cs) {
+  const int tid = threadIdx.x;
+  ColLanes L;
+  L.cq_l = tid % zq;
+  L.pl = tid / zq;
+  L.cq = z * zq + L.cq_l;
+  L.active = L.pl < ppl && L.cq * 4 < cs;
+  return L;
+}
+
+// Block combine of NS per-lane sums: through LDS, pixel lane 0 adds lanes 1 .. ppl-1 in that order (deterministic) and stores sum k of its
+// quad at dst + k * cs + cq * 4.  The two-sum stats kernels accumulate in named f4s and hand over a copy: an array indexed in their pixel
+// loops is promoted to registers only after unrolling, which costs them ~20 register moves.
+template <int NS>
+__device__ __forceinline__ void col_block_store(f4 (&s)[NS], f4 (*red)[256], const ColLanes& L, int zq, int ppl, int cs, float* dst) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < NS; ++k) red[k][tid] = s[k];
+  __syncthreads();
+  if (L.pl == 0 && L.cq * 4 < cs) {
+    for (int j = 1; j < ppl; ++j) {
+#pragma unroll
+      for (int k = 0; k < NS; ++k) s[k] += red[k][j * zq + L.cq_l];
+    }
+    dst += L.cq * 4;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) *reinterpret_cast<f4*>(dst + k * cs) = s[k];
+  }
 }
 
 }  // namespace cat

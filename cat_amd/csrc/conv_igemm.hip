@@ -1670,8 +1670,7 @@ static SplitPlan split_plan(int M, int n, int nk) {
 
 static void launch_splitk_reduce(const float* part, const float* bias, float* out, int64_t P, int C, int cw, int cs, int ksplit, int act,
                                  float slope, hipStream_t s) {
-  const int64_t b = (P * ((cw + 3) / 4) + 255) / 256;
-  splitk_reduce_kernel<<<(int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)), 256, 0, s>>>(part, bias, out, P, C, cw, cs, ksplit, act, slope);
+  splitk_reduce_kernel<<<cat::ew_grid(P * ((cw + 3) / 4), 4096), 256, 0, s>>>(part, bias, out, P, C, cw, cs, ksplit, act, slope);
 }
 
 // The tile kernels zero the lanes [C, cw) that fall inside their own column tiles, which always covers [C, round_up(C, 4)) -- every in-tree
@@ -1691,8 +1690,7 @@ __global__ __launch_bounds__(256) void zero_lanes_kernel(float* __restrict__ out
 static void zero_lanes_past_c4(float* out, int64_t P, int C, int cw, int cs, hipStream_t s) {
   const int c4 = (C + 3) & ~3;
   if (cw <= c4) return;
-  const int64_t b = (P * ((cw - c4 + 3) / 4) + 255) / 256;
-  zero_lanes_kernel<<<(int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)), 256, 0, s>>>(out, P, cs, c4, cw);
+  zero_lanes_kernel<<<cat::ew_grid(P * ((cw - c4 + 3) / 4), 4096), 256, 0, s>>>(out, P, cs, c4, cw);
 }
 
 // dynamic LDS of the double-buffered 128 x 128 x 32 tiles

@@ -8,10 +8,12 @@
 // K = 176 + 9*44 + 25*44 = 1672.  The LDS-tile kernel (conv_pk.hip) served it at 0.73 of the matrix pipe: its 1 x 1 segments are one
 // 64-MFMA group per barrier, and its filter fragments come through VGPR loads that queue behind the staging loads.  With N = 256 the
 // im2col form is the right one: the A operand re-read per tap comes from L2 (the hidden tensors are 11 MB), the tile is conv_fwd32d's
-// (2 x 2 waves of 4 x 4 v_mfma_f32_16x16x4_f32 tiles, XOR-swizzled [row][32 k] images written by buffer_load ... lds), and a chunk
-// is ONE tap x <= 8 channel quads of one segment, so the per-lane part of every address changes only when the walk moves to the next tap.
-//   * Channel counts per tap are multiples of 4, not of 32: a tap's Q quads are split into ceil(Q / 8) balanced chunks (44 channels:
-//     6 + 5 quads; 176: 8 + 8 + 7 + 7 + 7 + 7); the quads of a chunk beyond its length are not fetched (voffset beyond num_records).
+// (2 x 2 waves of 4 x 4 v_mfma_f32_16x16x4_f32 tiles, XOR-swizzled [row][32 k] images written by buffer_load ... lds), and K of a
+// segment is walked as the FLAT sequence of its (tap, channel quad) pairs in chunks of 8 quads.
+//   * Channel counts per tap are multiples of 4, not of 32.  A segment with Q >= 8 quads per tap takes the next 8 pairs whatever tap they
+//     belong to (44 channels = 11 quads: 8, then 3 of this tap + 5 of the next, ...; only a segment's last chunk is short): a chunk crosses at
+//     most ONE tap boundary, so a lane chooses between the offsets of the current and of the next tap and nothing else.  A segment with Q < 8
+//     takes one tap per chunk.  The quads of a chunk beyond its length are not fetched (voffset beyond num_records).
 //   * MFMA steps of a chunk: full sets of 4 quads through ds_read_b128 (lane quarter lq <-> quad 4h + lq, element t <-> step t, as in
 //     conv_fwd32d), then the remaining 1..3 quads one step each through ds_read_b32 (lane quarter lq <-> element lq of quad 4h + t):
 //     no zero-padded k-steps -- 44 channels cost 11 steps, not 12.
@@ -128,7 +130,7 @@ __device__ __forceinline__ void ksum_body(const Args& p) {
     rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sg.src), 0, 0x7fffffff, 0x00020000);
     rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sg.w), 0, 0x7fffffff, 0x00020000);
     wq = sg.q;
-    wflat = sg.q >= 8;
+    wflat = sg.q >= 8;      // invariant of the flat walk: a tap is at least as long as a chunk (8 quads), so a chunk holds quads of at most two taps
     wks = sg.ks;
     wtaps = sg.ks * sg.ks;
     wpad = sg.pad;

@@ -139,9 +139,7 @@ int cat_dropout_apply(const cat_drop_t* g, const float* x, const float* scale, c
   CAT_REQUIRE(total < (int64_t)4000000000LL, "dropout: tensor too large");
   CAT_REQUIRE((int64_t)g->npix * g->xcs < ((int64_t)1 << 40) && (int64_t)g->npix * g->ycs < ((int64_t)1 << 40), "dropout: tensor too large");
   cat::ProfScope prof(g->mode == CAT_DROP_NORM ? "dropout_norm" : "dropout", 0.0, 8.0 * (double)total * 4, stream);
-  const int64_t b = (total + 255) / 256;
-  const int gx = (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-  dropout_kernel<<<gx, 256, 0, (hipStream_t)stream>>>(*g, x, scale, shift, ticket, y, (unsigned)total, nq);
+  dropout_kernel<<<cat::ew_grid(total, 4096), 256, 0, (hipStream_t)stream>>>(*g, x, scale, shift, ticket, y, (unsigned)total, nq);
   return cat::check_launch("dropout");
 }
 

@@ -282,8 +282,7 @@ __global__ __launch_bounds__(256) void dw_dgrad_kernel(DwArgs p, int Hin, int Wi
 
 // dw[c][tap] partials: lanes = (pixel-lane, channel quad); each lane keeps one float4 accumulator per tap of ONE filter row
 // (blockIdx.y = ky) to bound registers at kw*4; block-reduced through LDS; partial [nb][taps][cs] in ws.
-// IT = index type of the pixel walk (int64_t; the int instantiation is kept switched off -- `idx32_on` -- when N*Ho*Wo < 2^31: the two div/mods per pixel are emulated at 64 bits)
-template <int KW, typename IT>
+template <int KW>
 __global__ __launch_bounds__(256) void dw_wgrad_kernel(DwArgs p, float* __restrict__ part, int nb, int ppl) {
   __shared__ f4 red[256];
   const int nq = p.xcs / 4;
@@ -296,15 +295,15 @@ __global__ __launch_bounds__(256) void dw_wgrad_kernel(DwArgs p, float* __restri
 #pragma unroll
   for (int k = 0; k < KW; ++k) acc[k] = f4{0.f, 0.f, 0.f, 0.f};
   if (pl < ppl) {
-    for (IT q = (IT)(pbeg + pl); q < (IT)pend; q += (IT)ppl) {
+    for (int64_t q = pbeg + pl; q < pend; q += ppl) {
       const int ox = (int)(q % p.Wo);
-      const IT r = q / p.Wo;
+      const int64_t r = q / p.Wo;
       const int oy = (int)(r % p.Ho);
       const int n = (int)(r / p.Ho);
       int iy = oy - p.pad + ky;
       if (p.reflect) iy = cat::reflect_idx(iy, p.H);
       else if ((unsigned)iy >= (unsigned)p.H) continue;
-      const f4 gv = *reinterpret_cast<const f4*>(p.y + (int64_t)q * p.ycs + cq * 4);  // p.y = dy here (read only)
+      const f4 gv = *reinterpret_cast<const f4*>(p.y + q * p.ycs + cq * 4);  // p.y = dy here (read only)
       const float* xr = p.x + ((int64_t)n * p.H + iy) * p.W * p.xcs + cq * 4;
 #pragma unroll
       for (int kx = 0; kx < KW; ++kx) {
@@ -338,10 +337,7 @@ __global__ void dw_wgrad_final_kernel(const float* __restrict__ part, float* __r
   dw[i] = accumulate ? dw[i] + s : s;
 }
 
-int ew_grid(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
+constexpr int kEwCap = 8192;   // most workgroups of an element walk (cat::ew_grid)
 
 int dw_check(const cat_conv_t* g) {
   CAT_REQUIRE(g->Cin == g->Cout && g->stride == 1, "dwconv: needs Cin == Cout, stride 1");
@@ -387,7 +383,7 @@ int cat_dwconv2d_fwd(const cat_conv_t* g, const float* x, const float* w, const 
   a.act = g->act;
   a.slope = g->slope;
   cat::ProfScope prof("dwconv_fwd", 2.0 * g->N * g->Ho * g->Wo * g->Cin * g->kh * g->kw, 2 * 4.0 * (double)g->N * g->Ho * g->Wo * own, stream);
-  dw_fwd_kernel<<<ew_grid((int64_t)g->N * g->Ho * g->Wo * a.cq), 256, (size_t)g->kh * g->kw * own * sizeof(float), (hipStream_t)stream>>>(a);
+  dw_fwd_kernel<<<cat::ew_grid((int64_t)g->N * g->Ho * g->Wo * a.cq, kEwCap), 256, (size_t)g->kh * g->kw * own * sizeof(float), (hipStream_t)stream>>>(a);
   return cat::check_launch("dwconv2d_fwd");
 }
 
@@ -430,7 +426,7 @@ int cat_dwconv2d_multi_fwd(const cat_dwmulti_t* g, const float* x, const float* 
     dw_multi_tile_kernel<<<g->N * t.tiles * t.ng, 256, DWT_LDS, (hipStream_t)stream>>>(t);
     return cat::check_launch("dwconv2d_multi_fwd");
   }
-  dw_multi_fwd_kernel<<<ew_grid(npix * g->nq), 256, (size_t)26 * 4 * g->nq * sizeof(float), (hipStream_t)stream>>>(a);
+  dw_multi_fwd_kernel<<<cat::ew_grid(npix * g->nq, kEwCap), 256, (size_t)26 * 4 * g->nq * sizeof(float), (hipStream_t)stream>>>(a);
   return cat::check_launch("dwconv2d_multi_fwd");
 }
 
@@ -442,7 +438,7 @@ int cat_dwconv2d_dgrad(const cat_conv_t* g, const float* dy, const float* w, flo
   cat::ProfScope prof("dwconv_dgrad", 2.0 * g->N * g->Ho * g->Wo * g->Cin * g->kh * g->kw, 2 * 4.0 * (double)g->N * g->Ho * g->Wo * g->ycs, stream);
   const bool refl = g->pad_mode == CAT_PAD_REFLECT;
   const int Hin = refl ? g->H + 2 * g->pad : g->H, Win = refl ? g->W + 2 * g->pad : g->W, pe = refl ? 0 : g->pad;
-  dw_dgrad_kernel<<<ew_grid((int64_t)g->N * Hin * Win * (dxcs / 4)), 256, (size_t)g->kh * g->kw * dxcs * sizeof(float), (hipStream_t)stream>>>(a, Hin, Win, pe,
+  dw_dgrad_kernel<<<cat::ew_grid((int64_t)g->N * Hin * Win * (dxcs / 4), kEwCap), 256, (size_t)g->kh * g->kw * dxcs * sizeof(float), (hipStream_t)stream>>>(a, Hin, Win, pe,
                                                                                                                                             dxcs);
   return cat::check_launch("dwconv2d_dgrad");
 }
@@ -460,20 +456,13 @@ int cat_dwconv2d_wgrad(const cat_conv_t* g, const float* x, const float* dy, flo
   hipStream_t s = (hipStream_t)stream;
   cat::ProfScope prof("dwconv_wgrad", 2.0 * g->N * g->Ho * g->Wo * g->Cin * g->kh * g->kw, 2 * 4.0 * (double)g->N * g->Ho * g->Wo * g->ycs, stream);
   dim3 grid(pl.nb, g->kh);
-  constexpr int idx32_on = 0;
-  const bool i32 = idx32_on && (int64_t)g->N * g->Ho * g->Wo < (int64_t)2147483647 - 65536;
-#define DW_WGRAD(KW)                                                                             \
-  if (i32) dw_wgrad_kernel<KW, int><<<grid, 256, 0, s>>>(a, (float*)ws, pl.nb, pl.ppl);          \
-  else dw_wgrad_kernel<KW, int64_t><<<grid, 256, 0, s>>>(a, (float*)ws, pl.nb, pl.ppl);          \
-  break
   switch (g->kw) {
-    case 1: DW_WGRAD(1);
-    case 3: DW_WGRAD(3);
-    case 5: DW_WGRAD(5);
-    case 7: DW_WGRAD(7);
+    case 1: dw_wgrad_kernel<1><<<grid, 256, 0, s>>>(a, (float*)ws, pl.nb, pl.ppl); break;
+    case 3: dw_wgrad_kernel<3><<<grid, 256, 0, s>>>(a, (float*)ws, pl.nb, pl.ppl); break;
+    case 5: dw_wgrad_kernel<5><<<grid, 256, 0, s>>>(a, (float*)ws, pl.nb, pl.ppl); break;
+    case 7: dw_wgrad_kernel<7><<<grid, 256, 0, s>>>(a, (float*)ws, pl.nb, pl.ppl); break;
     default: CAT_REQUIRE(false, "dwconv wgrad: kw %d unsupported", g->kw);
   }
-#undef DW_WGRAD
   dw_wgrad_final_kernel<<<cdiv(g->Cin * g->kh * g->kw, 256), 256, 0, s>>>((const float*)ws, dw, g->Cin, g->xcs, g->kh * g->kw, pl.nb,
                                                                             accumulate);
   return cat::check_launch("dwconv2d_wgrad");

@@ -1,15 +1,13 @@
 // HBM-bound elementwise / layout / optimizer kernels (gfx950).  All of them move float4 per lane over flat NHWC
-// buffers (pixel stride is a multiple of 4 floats) and grid-stride over at most 8192 workgroups.
+// buffers (pixel stride is a multiple of 4 floats) and grid-stride over at most kEwCap workgroups (cat::ew_grid).
 #include "common.h"
+#include <limits.h>
 #include <stdint.h>
 
 namespace {
 using cat::cdiv;
 
-int ew_grid(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
+constexpr int kEwCap = 8192;
 
 __global__ __launch_bounds__(256) void act_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t nq, int act, float slope) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nq; i += (int64_t)gridDim.x * 256) {
@@ -164,23 +162,18 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, co
   }
 }
 
-// per-channel sums over pixels, two deterministic stages
+// per-channel sums over pixels, two deterministic stages (lane layout and block combine: cat::col_lanes / col_block_store, common.h)
 __global__ __launch_bounds__(256) void chansum_partial_kernel(const float* __restrict__ x, float* __restrict__ part, int64_t M, int cs,
                                                               int zq, int ppl, int nb) {
-  __shared__ f4 red[256];
-  const int b = blockIdx.x, z = blockIdx.y, tid = threadIdx.x;
-  const int cq_l = tid % zq, pl = tid / zq, cq = z * zq + cq_l;
+  __shared__ f4 red[1][256];
+  const int b = blockIdx.x;
+  const cat::ColLanes L = cat::col_lanes(blockIdx.y, zq, ppl, cs);
   const int64_t per = (M + nb - 1) / nb;
   const int64_t pbeg = b * per, pend = pbeg + per < M ? pbeg + per : M;
-  f4 s = {0.f, 0.f, 0.f, 0.f};
-  if (pl < ppl && cq * 4 < cs)
-    for (int64_t p = pbeg + pl; p < pend; p += ppl) s += *reinterpret_cast<const f4*>(x + p * cs + cq * 4);
-  red[tid] = s;
-  __syncthreads();
-  if (pl == 0 && cq * 4 < cs) {
-    for (int j = 1; j < ppl; ++j) s += red[j * zq + cq_l];
-    *reinterpret_cast<f4*>(part + (int64_t)b * cs + cq * 4) = s;
-  }
+  f4 s[1] = {{0.f, 0.f, 0.f, 0.f}};
+  if (L.active)
+    for (int64_t p = pbeg + L.pl; p < pend; p += ppl) s[0] += *reinterpret_cast<const f4*>(x + p * cs + L.cq * 4);
+  cat::col_block_store(s, red, L, zq, ppl, cs, part + (int64_t)b * cs);
 }
 // 16 channels x 16 partial lanes per workgroup, four independent loads per lane and step, lanes combined pairwise through LDS in a fixed order
 // (round 6: 64 channels x 4 lanes walked up to 128 dependent loads per lane: 16 us for 64 KB of partials)
@@ -211,47 +204,8 @@ __global__ __launch_bounds__(256) void chansum_final_kernel(const float* __restr
   if (zl == 0 && c < C) out[c] = accumulate ? out[c] + red[threadIdx.x] : red[threadIdx.x];
 }
 
-struct CsPlan { int nq, nz, zq, ppl, nb; };
-CsPlan cs_plan(int64_t M, int cs) {
-  CsPlan p;
-  p.nq = cs / 4;
-  p.nz = cdiv(p.nq, 256);
-  p.zq = cdiv(p.nq, p.nz);
-  p.ppl = 256 / p.zq;
-  int nb = cdiv(512, p.nz);
-  const int maxb = cdiv(M, (int64_t)p.ppl * 16);
-  if (nb > maxb) nb = maxb;
-  if (nb < 1) nb = 1;
-  p.nb = nb;
-  return p;
-}
-
-// backward of ReflectionPad2d: every source pixel gathers the (up to 3 x 3) padded positions that mirror onto it
-__global__ __launch_bounds__(256) void reflect_fold_kernel(const float* __restrict__ dxp, float* __restrict__ dx, int N, int H, int W,
-                                                           int cs, int pad) {
-  const int nq = cs / 4;
-  const int64_t total = (int64_t)N * H * W * nq;
-  const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int cq = (int)(i % nq);
-    int64_t r = i / nq;
-    const int xw = (int)(r % W);
-    r /= W;
-    const int yh = (int)(r % H);
-    const int n = (int)(r / H);
-    int ys[3], xs[3], ny = 0, nx = 0;
-    ys[ny++] = yh + pad;
-    if (yh >= 1 && yh <= pad) ys[ny++] = pad - yh;
-    if (yh <= H - 2 && yh >= H - 1 - pad) ys[ny++] = pad + 2 * (H - 1) - yh;
-    xs[nx++] = xw + pad;
-    if (xw >= 1 && xw <= pad) xs[nx++] = pad - xw;
-    if (xw <= W - 2 && xw >= W - 1 - pad) xs[nx++] = pad + 2 * (W - 1) - xw;
-    f4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int a = 0; a < ny; ++a)
-      for (int b = 0; b < nx; ++b) s += *reinterpret_cast<const f4*>(dxp + (((int64_t)n * Hp + ys[a]) * Wp + xs[b]) * cs + cq * 4);
-    *reinterpret_cast<f4*>(dx + i * 4) = s;
-  }
-}
+// channel sum: ~512 workgroups, at least 16 pixels per pixel lane
+cat::ColPlan chansum_plan(int64_t M, int cs) { return cat::col_plan(M, cs, 1, 512, 16, INT_MAX); }
 
 // nn.ReplicationPad2d(pad) (reference inception_modules.py:114-115, padding_type='replicate'): the padded copy is materialised (the option is
 // not used by any launch script; the convolution behind it then runs with padding 0) and its backward folds the clamped positions
@@ -302,7 +256,7 @@ int cat_replicate_pad_fwd(const float* x, float* y, int N, int H, int W, int C, 
   cat::ProfScope prof("elementwise", 0.0, 8.0 * N * (H + 2 * pad) * (W + 2 * pad) * cs, stream);
   CAT_REQUIRE(cs % 4 == 0 && cs >= C && pad >= 0 && N > 0 && H > 0 && W > 0, "replicate_pad_fwd: bad geometry");
   const int64_t total = (int64_t)N * (H + 2 * pad) * (W + 2 * pad) * (cs / 4);
-  replicate_pad_fwd_kernel<<<ew_grid(total), 256, 0, (hipStream_t)stream>>>(x, y, N, H, W, cs, pad);
+  replicate_pad_fwd_kernel<<<cat::ew_grid(total, kEwCap), 256, 0, (hipStream_t)stream>>>(x, y, N, H, W, cs, pad);
   return cat::check_launch("replicate_pad_fwd");
 }
 
@@ -310,21 +264,21 @@ int cat_replicate_pad_bwd(const float* dyp, float* dx, int N, int H, int W, int 
   cat::ProfScope prof("elementwise", 0.0, 8.0 * N * (H + 2 * pad) * (W + 2 * pad) * cs, stream);
   CAT_REQUIRE(cs % 4 == 0 && cs >= C && pad >= 0 && N > 0 && H > 0 && W > 0, "replicate_pad_bwd: bad geometry");
   const int64_t total = (int64_t)N * H * W * (cs / 4);
-  replicate_pad_bwd_kernel<<<ew_grid(total), 256, 0, (hipStream_t)stream>>>(dyp, dx, N, H, W, cs, pad);
+  replicate_pad_bwd_kernel<<<cat::ew_grid(total, kEwCap), 256, 0, (hipStream_t)stream>>>(dyp, dx, N, H, W, cs, pad);
   return cat::check_launch("replicate_pad_bwd");
 }
 
 int cat_act_fwd(const float* x, float* y, int64_t n, int act, float slope, cat_stream_t stream) {
   cat::ProfScope prof("elementwise", 0.0, 8.0 * n, stream);
   CAT_REQUIRE(n % 4 == 0, "act_fwd: n must be a multiple of 4");
-  act_fwd_kernel<<<ew_grid(n / 4), 256, 0, (hipStream_t)stream>>>(x, y, n / 4, act, slope);
+  act_fwd_kernel<<<cat::ew_grid(n / 4, kEwCap), 256, 0, (hipStream_t)stream>>>(x, y, n / 4, act, slope);
   return cat::check_launch("act_fwd");
 }
 
 int cat_act_bwd(const float* y, const float* dy, float* dx, int64_t n, int act, float slope, cat_stream_t stream) {
   cat::ProfScope prof("elementwise", 0.0, 12.0 * n, stream);
   CAT_REQUIRE(n % 4 == 0, "act_bwd: n must be a multiple of 4");
-  act_bwd_kernel<<<ew_grid(n / 4), 256, 0, (hipStream_t)stream>>>(y, dy, dx, n / 4, act, slope);
+  act_bwd_kernel<<<cat::ew_grid(n / 4, kEwCap), 256, 0, (hipStream_t)stream>>>(y, dy, dx, n / 4, act, slope);
   return cat::check_launch("act_bwd");
 }
 
@@ -334,7 +288,7 @@ int cat_add_n(const float* const* srcs, int nsrc, float* dst, int64_t n, cat_str
   AddSrcs s{};
   for (int i = 0; i < nsrc; ++i) s.p[i] = srcs[i];
   hipStream_t st = (hipStream_t)stream;
-  const int grid = ew_grid(n / 4);
+  const int grid = cat::ew_grid(n / 4, kEwCap);
   switch (nsrc) {
     case 1: add_n_kernel<1><<<grid, 256, 0, st>>>(s, dst, n / 4); break;
     case 2: add_n_kernel<2><<<grid, 256, 0, st>>>(s, dst, n / 4); break;
@@ -351,14 +305,14 @@ int cat_add_n(const float* const* srcs, int nsrc, float* dst, int64_t n, cat_str
 int cat_concat2(const float* a, int ca, int acs, const float* b, int cb, int bcs, float* y, int ycs, int64_t M, cat_stream_t stream) {
   cat::ProfScope prof("elementwise", 0.0, 8.0 * M * ycs, stream);
   CAT_REQUIRE(ca + cb <= ycs, "concat2: ycs too small");
-  concat2_kernel<<<ew_grid(M * ycs), 256, 0, (hipStream_t)stream>>>(a, ca, acs, b, cb, bcs, y, ycs, M);
+  concat2_kernel<<<cat::ew_grid(M * ycs, kEwCap), 256, 0, (hipStream_t)stream>>>(a, ca, acs, b, cb, bcs, y, ycs, M);
   return cat::check_launch("concat2");
 }
 
 int cat_slice_channels(const float* x, int xcs, int c0, int c, float* y, int ycs, int64_t M, cat_stream_t stream) {
   cat::ProfScope prof("elementwise", 0.0, 8.0 * M * ycs, stream);
   CAT_REQUIRE(c0 + c <= xcs && c <= ycs, "slice_channels: bad range");
-  slice_kernel<<<ew_grid(M * ycs), 256, 0, (hipStream_t)stream>>>(x, xcs, c0, c, y, ycs, M);
+  slice_kernel<<<cat::ew_grid(M * ycs, kEwCap), 256, 0, (hipStream_t)stream>>>(x, xcs, c0, c, y, ycs, M);
   return cat::check_launch("slice_channels");
 }
 
@@ -367,7 +321,7 @@ int cat_nchw_to_nhwc(const float* x, float* y, int N, int C, int H, int W, int y
   CAT_REQUIRE(ycs >= C, "nchw_to_nhwc: ycs < C");
   if (ycs == 4 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) {
     const int64_t total = (int64_t)N * H * W;
-    nchw_to_nhwc4_kernel<<<ew_grid(total), 256, 0, (hipStream_t)stream>>>(x, y, C, H * W, total);
+    nchw_to_nhwc4_kernel<<<cat::ew_grid(total, kEwCap), 256, 0, (hipStream_t)stream>>>(x, y, C, H * W, total);
     return cat::check_launch("nchw_to_nhwc");
   }
   dim3 grid(cdiv(H * W, 64), cdiv(ycs, 64), N);
@@ -386,13 +340,13 @@ int cat_nhwc_to_nchw(const float* x, float* y, int N, int C, int H, int W, int x
 int cat_fill(float* p, int64_t n, float v, cat_stream_t stream) {
   cat::ProfScope prof("fill", 0.0, 4.0 * n, stream);
   if (n <= 0) return 0;
-  fill_kernel<<<ew_grid(n), 256, 0, (hipStream_t)stream>>>(p, n, v);
+  fill_kernel<<<cat::ew_grid(n, kEwCap), 256, 0, (hipStream_t)stream>>>(p, n, v);
   return cat::check_launch("fill");
 }
 
 int cat_axpy(float* y, const float* x, int64_t n, float a, cat_stream_t stream) {
   if (n <= 0) return 0;
-  axpy_kernel<<<ew_grid(n), 256, 0, (hipStream_t)stream>>>(y, x, n, a);
+  axpy_kernel<<<cat::ew_grid(n, kEwCap), 256, 0, (hipStream_t)stream>>>(y, x, n, a);
   return cat::check_launch("axpy");
 }
 
@@ -405,7 +359,7 @@ int cat_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   const float step_size = (float)((double)lr / bc1);
   const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-  adam_kernel<<<ew_grid(n), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, beta1, beta2, eps, weight_decay, step_size, inv_bc2_sqrt,
+  adam_kernel<<<cat::ew_grid(n, kEwCap), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, beta1, beta2, eps, weight_decay, step_size, inv_bc2_sqrt,
                                                             grad_scale);
   return cat::check_launch("adam");
 }
@@ -415,28 +369,20 @@ int cat_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, f
   CAT_REQUIRE(hyper, "adam: device hyper-parameter block required");
   hipStream_t s = (hipStream_t)stream;
   adam_tick_kernel<<<1, 1, 0, s>>>(hyper);
-  if (n > 0) adam_dev_kernel<<<ew_grid(n), 256, 0, s>>>(p, g, m, v, n, hyper, grad_scale);
+  if (n > 0) adam_dev_kernel<<<cat::ew_grid(n, kEwCap), 256, 0, s>>>(p, g, m, v, n, hyper, grad_scale);
   return cat::check_launch("adam");
 }
 
-size_t cat_channel_sum_ws_bytes(int M, int cs) { return (size_t)cs_plan(M, cs).nb * cs * sizeof(float); }
+size_t cat_channel_sum_ws_bytes(int M, int cs) { return (size_t)chansum_plan(M, cs).nb * cs * sizeof(float); }
 
 int cat_channel_sum(const float* x, int M, int C, int cs, float* out, int accumulate, void* ws, cat_stream_t stream) {
   cat::ProfScope prof("channel_sum", 0.0, 4.0 * M * cs, stream);
   CAT_REQUIRE(cs % 4 == 0 && cs >= C && ws, "channel_sum: bad arguments");
-  const CsPlan p = cs_plan(M, cs);
+  const cat::ColPlan p = chansum_plan(M, cs);
   hipStream_t s = (hipStream_t)stream;
   chansum_partial_kernel<<<dim3(p.nb, p.nz), 256, 0, s>>>(x, (float*)ws, M, cs, p.zq, p.ppl, p.nb);
   chansum_final_kernel<<<cdiv(C, 16), 256, 0, s>>>((const float*)ws, out, C, cs, p.nb, accumulate);
   return cat::check_launch("channel_sum");
-}
-
-int cat_reflect_pad_bwd(const float* dxp, float* dx, int N, int H, int W, int C, int cs, int pad, cat_stream_t stream) {
-  cat::ProfScope prof("reflect_pad_bwd", 0.0, 8.0 * N * H * W * cs, stream);
-  CAT_REQUIRE(cs % 4 == 0 && cs >= C && pad < H && pad < W, "reflect_pad_bwd: bad geometry");
-  const int64_t total = (int64_t)N * H * W * (cs / 4);
-  reflect_fold_kernel<<<ew_grid(total), 256, 0, (hipStream_t)stream>>>(dxp, dx, N, H, W, cs, pad);
-  return cat::check_launch("reflect_pad_bwd");
 }
 
 }  // extern "C"

@@ -89,10 +89,7 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __res
   }
 }
 
-int walk_grid(int64_t items) {
-  int64_t b = (items + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
-}
+constexpr int kEwCap = 16384;   // most workgroups of an element walk (cat::ew_grid)
 
 }  // namespace
 
@@ -105,7 +102,7 @@ int cat_pool2d_fwd(const float* x, int xcs, int N, int H, int W, int C4, int k, 
   CAT_REQUIRE(k >= 1 && k <= 7 && stride >= 1 && pad >= 0 && 2 * pad <= k && (mode == POOL_MAX || mode == POOL_AVG_EXCL), "pool2d: window");
   CAT_REQUIRE(Ho == (H + 2 * pad - k) / stride + 1 && Wo == (W + 2 * pad - k) / stride + 1 && Ho > 0 && Wo > 0, "pool2d: output size");
   cat::ProfScope prof("pool2d", 0.0, 4.0 * ((double)N * H * W + (double)N * Ho * Wo) * C4, stream);
-  pool2d_kernel<<<walk_grid((int64_t)N * Ho * Wo * (C4 / 4)), 256, 0, (hipStream_t)stream>>>(x, xcs, N, H, W, C4 / 4, k, stride, pad, mode, y, ycs, Ho, Wo);
+  pool2d_kernel<<<cat::ew_grid((int64_t)N * Ho * Wo * (C4 / 4), kEwCap), 256, 0, (hipStream_t)stream>>>(x, xcs, N, H, W, C4 / 4, k, stride, pad, mode, y, ycs, Ho, Wo);
   return cat::check_launch("pool2d");
 }
 
@@ -123,7 +120,7 @@ int cat_resize_bilinear_fwd(const float* x, int xcs, int N, int H, int W, int C,
   CAT_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0 && (xcs & 3) == 0 && (ycs & 3) == 0 && xcs >= C4 && ycs >= C4,
               "resize bilinear: layout");
   cat::ProfScope prof("resize_bilinear", 0.0, 4.0 * ((double)N * H * W + (double)N * Ho * Wo) * C4, stream);
-  resize_bilinear_kernel<<<walk_grid((int64_t)N * Ho * Wo * (C4 / 4)), 256, 0, (hipStream_t)stream>>>(x, xcs, N, H, W, C, C4 / 4, y, ycs, Ho, Wo, (float)H / (float)Ho,
+  resize_bilinear_kernel<<<cat::ew_grid((int64_t)N * Ho * Wo * (C4 / 4), kEwCap), 256, 0, (hipStream_t)stream>>>(x, xcs, N, H, W, C, C4 / 4, y, ycs, Ho, Wo, (float)H / (float)Ho,
                                                                                                       (float)W / (float)Wo, a, b);
   return cat::check_launch("resize_bilinear");
 }

@@ -43,11 +43,6 @@ __global__ __launch_bounds__(256) void image_normalize_kernel(const unsigned int
   }
 }
 
-int image_grid(int64_t npix) {
-  const int64_t b = (npix + 255) / 256;
-  return (int)(b > 16384 ? 16384 : b);
-}
-
 }  // namespace
 
 extern "C" {
@@ -57,7 +52,7 @@ int cat_image_quantize(const float* x, int xcs, int N, int H, int W, int C, unsi
   CAT_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 3) == 0, "image quantize: x must be 16-byte aligned, out 4-byte aligned");
   const int64_t npix = (int64_t)N * H * W;
   cat::ProfScope prof("image_quantize", 0.0, 20.0 * (double)npix, stream);
-  image_quantize_kernel<<<image_grid(npix), 256, 0, (hipStream_t)stream>>>(x, xcs, npix, C,
+  image_quantize_kernel<<<cat::ew_grid(npix, 16384), 256, 0, (hipStream_t)stream>>>(x, xcs, npix, C,
                                                                           reinterpret_cast<unsigned int*>(out) + (int64_t)img_off * H * W);
   return cat::check_launch("image_quantize");
 }
@@ -68,7 +63,7 @@ int cat_image_normalize(const unsigned char* u8, long long img_off, int N, int H
   CAT_REQUIRE(((uintptr_t)y & 15) == 0 && ((uintptr_t)u8 & 3) == 0, "image normalize: y must be 16-byte aligned, u8 4-byte aligned");
   const int64_t npix = (int64_t)N * H * W;
   cat::ProfScope prof("image_normalize", 0.0, 20.0 * (double)npix, stream);
-  image_normalize_kernel<<<image_grid(npix), 256, 0, (hipStream_t)stream>>>(reinterpret_cast<const unsigned int*>(u8) + (int64_t)img_off * H * W, npix, C,
+  image_normalize_kernel<<<cat::ew_grid(npix, 16384), 256, 0, (hipStream_t)stream>>>(reinterpret_cast<const unsigned int*>(u8) + (int64_t)img_off * H * W, npix, C,
                                                                            f4{mean0, mean1, mean2, mean3}, f4{std0, std1, std2, std3}, y, ycs);
   return cat::check_launch("image_normalize");
 }

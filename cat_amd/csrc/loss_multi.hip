@@ -90,10 +90,7 @@ int fwd_nb(const cat_loss_term_t& L) {      // cat_loss_fwd's grid: 1024 quads p
   const int64_t b = (L.M * (L.cs / 4) + 1023) / 1024;
   return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
 }
-int bwd_nb(const cat_loss_term_t& L) {
-  const int64_t b = (L.M * (L.cs / 4) + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
+int bwd_nb(const cat_loss_term_t& L) { return cat::ew_grid(L.M * (L.cs / 4), 4096); }
 
 int check_terms(const cat_loss_term_t* terms, int T, const char* what) {
   CAT_REQUIRE(terms && T >= 1, "%s: empty table", what);

@@ -3,35 +3,26 @@
 //   pass 1  per-(group, channel) shifted sums   sum(x - x0), sum((x - x0)^2)   -> deterministic partials in ws
 //   pass 2  finalize: mean / rstd (biased var, eps inside the sqrt), running stats, per-(group,channel) scale+shift
 //   pass 3  y = act(x * scale + shift), float4 per lane
-// Reduction layout: a workgroup walks pixels with (256 / quads) pixel-lanes x quads channel-quads, so every global
-// access is a float4 and a wave touches whole pixels (cs*4 contiguous bytes); cross-lane combine goes through LDS.
+// Reduction layout and block combine of pass 1: cat::ColPlan / col_lanes / col_block_store (common.h); the pass-3 pixel walks use the same lanes.
 #include "common.h"
+#include <limits.h>
 #include <stdlib.h>
 
 namespace {
 using cat::cdiv;
 
-struct NormPlan {
-  int G, Pg, nq, nz, zq, ppl, nb;
+struct NormPlan : cat::ColPlan {
+  int G, Pg;
   size_t part_off, scale_off, shift_off, c1_off, c2_off, bytes;
 };
 
 NormPlan plan(const cat_norm_t* g) {
-  NormPlan p;
-  p.G = g->mode == CAT_NORM_INSTANCE ? g->N : 1;
-  p.Pg = g->mode == CAT_NORM_INSTANCE ? g->HW : g->N * g->HW;
-  p.nq = g->cs / 4;
-  p.nz = cdiv(p.nq, 256);
-  p.zq = cdiv(p.nq, p.nz);  // quads per z-block (<= 256)
-  p.ppl = 256 / p.zq;
-  int nb = cdiv(2048, p.G * p.nz);
-  if (nb > 1024) nb = 1024;
-  const int maxb = cdiv(p.Pg, p.ppl * 16);
-  if (nb > maxb) nb = maxb;
-  if (nb < 1) nb = 1;
-  p.nb = nb;
+  const int G = g->mode == CAT_NORM_INSTANCE ? g->N : 1, Pg = g->mode == CAT_NORM_INSTANCE ? g->HW : g->N * g->HW;
+  NormPlan p{cat::col_plan(Pg, g->cs, G, 2048, 16, 1024)};   // stats: ~2048 workgroups, at most 1024 per group, >= 16 pixels per pixel lane
+  p.G = G;
+  p.Pg = Pg;
   size_t off = 0;
-  p.part_off = off; off += (size_t)p.G * nb * 2 * g->cs;
+  p.part_off = off; off += (size_t)p.G * p.nb * 2 * g->cs;
   p.scale_off = off; off += (size_t)p.G * g->cs;
   p.shift_off = off; off += (size_t)p.G * g->cs;
   p.c1_off = off; off += (size_t)p.G * g->cs;
@@ -48,17 +39,15 @@ __global__ __launch_bounds__(256) void norm_stats_kernel(const float* __restrict
                                                          float* __restrict__ part, int Pg, int C, int cs, int zq, int ppl, int nb,
                                                          int act, float slope) {
   __shared__ f4 red[2][256];
-  const int g = blockIdx.y, b = blockIdx.x, z = blockIdx.z;
-  const int tid = threadIdx.x;
-  const int cq_l = tid % zq, pl = tid / zq;
-  const int cq = z * zq + cq_l;
-  const bool active = pl < ppl && cq * 4 < cs;
+  const int g = blockIdx.y, b = blockIdx.x;
+  const cat::ColLanes L = cat::col_lanes(blockIdx.z, zq, ppl, cs);
+  const int pl = L.pl;
   const int per = (Pg + nb - 1) / nb;
   const int pbeg = b * per, pend = min(Pg, pbeg + per);
   const float* xg = x + (int64_t)g * Pg * cs;
   f4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-  if (active) {
-    const int c = cq * 4;
+  if (L.active) {
+    const int c = L.cq * 4;
     if (MODE == 0) {
       const f4 sh = *reinterpret_cast<const f4*>(xg + c);
       for (int p0 = pbeg + pl; p0 < pend; p0 += 4 * ppl) {
@@ -109,18 +98,8 @@ __global__ __launch_bounds__(256) void norm_stats_kernel(const float* __restrict
       }
     }
   }
-  red[0][tid] = s0;
-  red[1][tid] = s1;
-  __syncthreads();
-  if (pl == 0 && cq * 4 < cs) {
-    for (int j = 1; j < ppl; ++j) {
-      s0 += red[0][j * zq + cq_l];
-      s1 += red[1][j * zq + cq_l];
-    }
-    float* dst = part + ((int64_t)(g * nb + b) * 2) * cs + cq * 4;
-    *reinterpret_cast<f4*>(dst) = s0;
-    *reinterpret_cast<f4*>(dst + cs) = s1;
-  }
+  f4 s[2] = {s0, s1};
+  cat::col_block_store(s, red, L, zq, ppl, cs, part + ((int64_t)(g * nb + b) * 2) * cs);
 }
 
 __global__ __launch_bounds__(256) void norm_fwd_finalize_kernel(const float* __restrict__ x, const float* __restrict__ part,
@@ -171,13 +150,11 @@ __global__ __launch_bounds__(256) void norm_fwd_finalize_kernel(const float* __r
 }
 
 // y = act(x * scale[g][c] + shift[g][c]); scale/shift hold zeros on padding channels.
-// IT = index type of the element walk: int64_t, or int (kept switched off: `idx32`'s `on`) when the tensor has < 2^31 quads -- the `%` and `/` below are
-// emulated in ~100 instructions each at 64 bits, which is most of what these HBM-bound kernels execute per float4.
-template <typename IT>
+// The 64-bit `%` and `/` below are emulated in ~100 instructions each, which is most of what these HBM-bound element walks execute per float4.
 __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict__ x, const float* __restrict__ scale,
-                                                         const float* __restrict__ shift, float* __restrict__ y, IT nquads, int nq,
-                                                         IT qpg, int cs, int act, float slope) {
-  for (IT i = (IT)blockIdx.x * 256 + threadIdx.x; i < nquads; i += (IT)gridDim.x * 256) {
+                                                         const float* __restrict__ shift, float* __restrict__ y, int64_t nquads, int nq,
+                                                         int64_t qpg, int cs, int act, float slope) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nquads; i += (int64_t)gridDim.x * 256) {
     const int cq = (int)(i % nq);
     const int g = (int)(i / qpg);
     const f4 v = *reinterpret_cast<const f4*>(x + (int64_t)i * 4);
@@ -259,14 +236,13 @@ __global__ __launch_bounds__(256) void norm_bwd_param_kernel(const float* __rest
 }
 
 // dx = gamma*rstd * (g - mean(g) - xhat * mean(g*xhat))
-template <typename IT>
 __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
                                                              const float* __restrict__ mean, const float* __restrict__ rstd,
                                                              const float* __restrict__ c1, const float* __restrict__ c2,
-                                                             const float* __restrict__ scale, float* __restrict__ dx, IT nquads,
-                                                             int nq, IT qpg, int C, int cs, int act, float slope) {
-  for (IT i = (IT)blockIdx.x * 256 + threadIdx.x; i < nquads; i += (IT)gridDim.x * 256) {
+                                                             const float* __restrict__ scale, float* __restrict__ dx, int64_t nquads,
+                                                             int nq, int64_t qpg, int C, int cs, int act, float slope) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nquads; i += (int64_t)gridDim.x * 256) {
     const int cq = (int)(i % nq);
     const int g = (int)(i / qpg);
     const int c = cq * 4;
@@ -377,12 +353,7 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_walk_kernel(const float* _
 }
 
 // block count of the apply walks: ~4096 workgroups, at least 8 pixels per pixel lane
-static int walk_blocks(const NormPlan& p) {
-  int nb = cdiv(4096, p.G * p.nz);
-  const int maxb = cdiv(p.Pg, p.ppl * 8);
-  if (nb > maxb) nb = maxb;
-  return nb < 1 ? 1 : nb;
-}
+static int walk_blocks(const NormPlan& p) { return cat::col_blocks(p.Pg, p.ppl, p.G * p.nz, 4096, 8, INT_MAX); }
 static bool walk_on() {
   static const int on = getenv("CAT_NORM_WALK") ? atoi(getenv("CAT_NORM_WALK")) : 1;
   return on != 0;
@@ -397,11 +368,10 @@ __global__ void bn_fold_kernel(const float* gamma, const float* beta, const floa
   shift[c] = (beta ? beta[c] : 0.f) - rm[c] * s;
 }
 
-template <typename IT>
 __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict__ x, const float* __restrict__ scale,
-                                                         const float* __restrict__ shift, float* __restrict__ y, IT nquads, int nq,
+                                                         const float* __restrict__ shift, float* __restrict__ y, int64_t nquads, int nq,
                                                          int C, int act, float slope) {
-  for (IT i = (IT)blockIdx.x * 256 + threadIdx.x; i < nquads; i += (IT)gridDim.x * 256) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nquads; i += (int64_t)gridDim.x * 256) {
     const int c = (int)(i % nq) * 4;
     const f4 v = *reinterpret_cast<const f4*>(x + (int64_t)i * 4);
     f4 o;
@@ -411,16 +381,7 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
   }
 }
 
-int ew_grid(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
-
-// 32-bit element walk (opt-in): the loop variable may run one grid stride (<= 8192 * 256) past nquads
-bool idx32(int64_t nquads) {
-  constexpr int on = 0;
-  return on && nquads < (int64_t)2147483647 - 8192 * 256;
-}
+constexpr int kEwCap = 8192;   // most workgroups of an element walk (cat::ew_grid)
 
 }  // namespace
 
@@ -453,12 +414,8 @@ int cat_norm_fwd(const cat_norm_t* g, const float* x, const float* gamma, const 
     norm_apply_walk_kernel<<<dim3(nbw, p.G, p.nz), 256, 0, s>>>(x, w + p.scale_off, w + p.shift_off, y, p.Pg, g->cs, p.zq, p.ppl, nbw, g->act, g->slope);
     return cat::check_launch("norm_fwd");
   }
-  if (idx32(nquads))
-    norm_apply_kernel<int><<<ew_grid(nquads), 256, 0, s>>>(x, w + p.scale_off, w + p.shift_off, y, (int)nquads, p.nq, p.Pg * p.nq, g->cs,
-                                                            g->act, g->slope);
-  else
-    norm_apply_kernel<int64_t><<<ew_grid(nquads), 256, 0, s>>>(x, w + p.scale_off, w + p.shift_off, y, nquads, p.nq, (int64_t)p.Pg * p.nq,
-                                                                g->cs, g->act, g->slope);
+  norm_apply_kernel<<<cat::ew_grid(nquads, kEwCap), 256, 0, s>>>(x, w + p.scale_off, w + p.shift_off, y, nquads, p.nq, (int64_t)p.Pg * p.nq, g->cs,
+                                                                 g->act, g->slope);
   return cat::check_launch("norm_fwd");
 }
 
@@ -485,14 +442,9 @@ int cat_norm_bwd(const cat_norm_t* g, const float* x, const float* dy, const flo
                                                                      w + p.scale_off, dx, p.Pg, g->C, g->cs, p.zq, p.ppl, nbw, g->act, g->slope);
     return cat::check_launch("norm_bwd");
   }
-  if (idx32(nquads))
-    norm_bwd_apply_kernel<int><<<ew_grid(nquads), 256, 0, s>>>(x, dy, gamma, beta, save_mean, save_rstd, w + p.c1_off, w + p.c2_off,
-                                                                w + p.scale_off, dx, (int)nquads, p.nq, p.Pg * p.nq, g->C, g->cs, g->act,
-                                                                g->slope);
-  else
-    norm_bwd_apply_kernel<int64_t><<<ew_grid(nquads), 256, 0, s>>>(x, dy, gamma, beta, save_mean, save_rstd, w + p.c1_off, w + p.c2_off,
-                                                                    w + p.scale_off, dx, nquads, p.nq, (int64_t)p.Pg * p.nq, g->C, g->cs,
-                                                                    g->act, g->slope);
+  norm_bwd_apply_kernel<<<cat::ew_grid(nquads, kEwCap), 256, 0, s>>>(x, dy, gamma, beta, save_mean, save_rstd, w + p.c1_off, w + p.c2_off,
+                                                                     w + p.scale_off, dx, nquads, p.nq, (int64_t)p.Pg * p.nq, g->C, g->cs,
+                                                                     g->act, g->slope);
   return cat::check_launch("norm_bwd");
 }
 
@@ -507,8 +459,7 @@ int cat_affine_act_fwd(const float* x, const float* scale, const float* shift, f
   CAT_REQUIRE(cs % 4 == 0 && cs >= C, "affine_act: bad channel stride");
   const int64_t nquads = M * (cs / 4);
   cat::ProfScope prof("affine_act", 0.0, 8.0 * M * cs, stream);
-  if (idx32(nquads)) affine_act_kernel<int><<<ew_grid(nquads), 256, 0, (hipStream_t)stream>>>(x, scale, shift, y, (int)nquads, cs / 4, C, act, slope);
-  else affine_act_kernel<int64_t><<<ew_grid(nquads), 256, 0, (hipStream_t)stream>>>(x, scale, shift, y, nquads, cs / 4, C, act, slope);
+  affine_act_kernel<<<cat::ew_grid(nquads, kEwCap), 256, 0, (hipStream_t)stream>>>(x, scale, shift, y, nquads, cs / 4, C, act, slope);
   return cat::check_launch("affine_act");
 }
 

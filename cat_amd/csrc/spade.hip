@@ -8,33 +8,17 @@
 //   * nearest interpolation / x2 upsampling, 3x3 s2 average pooling without pad count, 2x2 max pooling, one-hot + instance
 //     edges, spectral-norm power iteration (one step per forward, torch.nn.utils.spectral_norm semantics).
 #include "common.h"
+#include <limits.h>
 
 namespace {
 using cat::cdiv;
+using cat::ColPlan;
 
-int ew_grid(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
-}
+constexpr int kEwCap = 16384;   // most workgroups of an element walk (cat::ew_grid)
 
 // ------------------------------------------------------------------------------------------ per-channel column statistics
-struct ColPlan {
-  int nq, nz, zq, ppl, nb;
-};
-
-ColPlan col_plan(int64_t M, int cs) {
-  ColPlan p;
-  p.nq = cs / 4;
-  p.nz = cdiv(p.nq, 256);
-  p.zq = cdiv(p.nq, p.nz);
-  p.ppl = 256 / p.zq;
-  int nb = cdiv(2048, p.nz);
-  const int maxb = cdiv(M, (int64_t)p.ppl * 8);
-  if (nb > maxb) nb = maxb;
-  if (nb < 1) nb = 1;
-  p.nb = nb;
-  return p;
-}
+// lane layout and block combine: cat::col_lanes / col_block_store (common.h); ~2048 workgroups, at least 8 pixels per pixel lane
+ColPlan stats_plan(int64_t M, int cs) { return cat::col_plan(M, cs, 1, 2048, 8, INT_MAX); }
 
 struct ColArgs {
   const float* x;       // activation [M][cs]
@@ -59,17 +43,15 @@ struct ColArgs {
 template <int MODE>
 __global__ __launch_bounds__(256) void col_stats_kernel(const ColArgs A) {
   __shared__ f4 red[2][256];
-  const int b = blockIdx.x, z = blockIdx.y;
-  const int tid = threadIdx.x;
-  const int cq_l = tid % A.zq, pl = tid / A.zq;
-  const int cq = z * A.zq + cq_l;
+  const int b = blockIdx.x;
   const int cs = A.cs, C = A.C;
-  const bool active = pl < A.ppl && cq * 4 < cs;
+  const cat::ColLanes L = cat::col_lanes(blockIdx.y, A.zq, A.ppl, cs);
+  const int pl = L.pl;
   const int64_t per = (A.M + A.nb - 1) / A.nb;
   const int64_t pbeg = b * per, pend = min(A.M, pbeg + per);
   f4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-  if (active) {
-    const int c = cq * 4;
+  if (L.active) {
+    const int c = L.cq * 4;
     if (MODE == 0) {
       const f4 sh = *reinterpret_cast<const f4*>(A.x + c);
       for (int64_t p = pbeg + pl; p < pend; p += A.ppl) {
@@ -134,18 +116,8 @@ __global__ __launch_bounds__(256) void col_stats_kernel(const ColArgs A) {
       }
     }
   }
-  red[0][tid] = s0;
-  red[1][tid] = s1;
-  __syncthreads();
-  if (pl == 0 && cq * 4 < cs) {
-    for (int j = 1; j < A.ppl; ++j) {
-      s0 += red[0][j * A.zq + cq_l];
-      s1 += red[1][j * A.zq + cq_l];
-    }
-    float* dst = A.part + ((int64_t)b * 2) * cs + cq * 4;
-    *reinterpret_cast<f4*>(dst) = s0;
-    *reinterpret_cast<f4*>(dst + cs) = s1;
-  }
+  f4 s[2] = {s0, s1};
+  cat::col_block_store(s, red, L, A.zq, A.ppl, cs, A.part + ((int64_t)b * 2) * cs);
 }
 
 // sums[0][c], sums[1][c] = column sums of the nb partials; block = 16 channels x 16 partial lanes.
@@ -577,7 +549,7 @@ __global__ __launch_bounds__(256) void sn_bwd_kernel(const float* __restrict__ g
 
 extern "C" {
 
-size_t cat_bn_ws_bytes(int64_t M, int cs) { return (size_t)col_plan(M, cs).nb * 2 * cs * sizeof(float); }
+size_t cat_bn_ws_bytes(int64_t M, int cs) { return (size_t)stats_plan(M, cs).nb * 2 * cs * sizeof(float); }
 
 static int launch_col(int mode, ColArgs& A, const ColPlan& p, hipStream_t s) {
   A.zq = p.zq;
@@ -594,7 +566,7 @@ int cat_bn_stats_fwd(const float* x, int64_t M, int C, int cs, float* sums, void
   CAT_REQUIRE(cs % 4 == 0 && cs >= C && M > 0 && ws && sums, "bn_stats_fwd: bad arguments");
   cat::ProfScope prof("bn_stats", 0.0, 4.0 * (double)M * cs, stream);
   hipStream_t s = (hipStream_t)stream;
-  const ColPlan p = col_plan(M, cs);
+  const ColPlan p = stats_plan(M, cs);
   ColArgs A = {};
   A.x = x;
   A.part = (float*)ws;
@@ -620,7 +592,7 @@ int cat_bn_stats_bwd(const float* x, const float* dy, const float* gamma, const 
   CAT_REQUIRE(cs % 4 == 0 && cs >= C && M > 0 && ws && sums, "bn_stats_bwd: bad arguments");
   cat::ProfScope prof("bn_stats", 0.0, 8.0 * (double)M * cs, stream);
   hipStream_t s = (hipStream_t)stream;
-  const ColPlan p = col_plan(M, cs);
+  const ColPlan p = stats_plan(M, cs);
   ColArgs A = {};
   A.x = x;
   A.dy = dy;
@@ -648,7 +620,7 @@ int cat_bn_apply_bwd(const float* x, const float* dy, const float* gamma, const 
   if (dgamma || dbeta) bn_param_grad_kernel<<<cdiv(C, 256), 256, 0, s>>>(local_sums, dgamma, dbeta, C, cs, accumulate);
   if (dx) {
     const int64_t nquads = M * (cs / 4);
-    bn_bwd_apply_kernel<<<ew_grid(nquads), 256, 0, s>>>(x, dy, gamma, beta, a, b, sums, (float)(1.0 / count), dx, nquads, cs / 4, C, cs, act,
+    bn_bwd_apply_kernel<<<cat::ew_grid(nquads, kEwCap), 256, 0, s>>>(x, dy, gamma, beta, a, b, sums, (float)(1.0 / count), dx, nquads, cs / 4, C, cs, act,
                                                          slope);
   }
   return cat::check_launch("bn_apply_bwd");
@@ -659,7 +631,7 @@ int cat_spade_fwd(const float* x, const float* a, const float* b, const float* g
   CAT_REQUIRE(cs % 4 == 0 && cs >= C && gcs % 4 == 0 && gcs >= 2 * C && M > 0, "spade_fwd: bad geometry");
   cat::ProfScope prof("spade_fwd", 0.0, 4.0 * (double)M * (2 * cs + gcs), stream);
   const int64_t nquads = M * (cs / 4);
-  spade_fwd_kernel<<<ew_grid(nquads), 256, 0, (hipStream_t)stream>>>(x, a, b, gb, y, nquads, cs / 4, C, cs, gcs, act, slope);
+  spade_fwd_kernel<<<cat::ew_grid(nquads, kEwCap), 256, 0, (hipStream_t)stream>>>(x, a, b, gb, y, nquads, cs / 4, C, cs, gcs, act, slope);
   return cat::check_launch("spade_fwd");
 }
 
@@ -668,7 +640,7 @@ int cat_spade_bwd_stats(const float* x, const float* a, const float* b, const fl
   CAT_REQUIRE(cs % 4 == 0 && cs >= C && gcs % 4 == 0 && gcs >= 2 * C && M > 0 && ws, "spade_bwd_stats: bad geometry");
   cat::ProfScope prof("spade_bwd", 0.0, 4.0 * (double)M * (5 * cs + 2 * gcs), stream);
   hipStream_t s = (hipStream_t)stream;
-  const ColPlan p = col_plan(M, cs);
+  const ColPlan p = stats_plan(M, cs);
   if (gcs > 2 * C) hipMemsetAsync(dgb, 0, (size_t)M * gcs * sizeof(float), s);   // ragged 2C: keep the padding lanes zero
   ColArgs A = {};
   A.x = x;
@@ -696,7 +668,7 @@ int cat_spade_bwd_apply(const float* x, const float* a, const float* b, const fl
   CAT_REQUIRE(cs % 4 == 0 && cs >= C && M > 0 && count > 0, "spade_bwd_apply: bad geometry");
   cat::ProfScope prof("spade_bwd", 0.0, 12.0 * (double)M * cs, stream);
   const int64_t nquads = M * (cs / 4);
-  spade_bwd_apply_kernel<<<ew_grid(nquads), 256, 0, (hipStream_t)stream>>>(x, a, b, sums, (float)(1.0 / count), dx, nquads, cs / 4, cs);
+  spade_bwd_apply_kernel<<<cat::ew_grid(nquads, kEwCap), 256, 0, (hipStream_t)stream>>>(x, a, b, sums, (float)(1.0 / count), dx, nquads, cs / 4, cs);
   return cat::check_launch("spade_bwd_apply");
 }
 
@@ -705,7 +677,7 @@ int cat_interp_nearest_fwd(const float* x, float* y, int N, int Hi, int Wi, int 
               "interp_nearest: bad geometry");
   cat::ProfScope prof("interp_nearest", 0.0, 8.0 * (double)N * Ho * Wo * ycs, stream);
   const int64_t total = (int64_t)N * Ho * Wo * (ycs / 4);
-  interp_nearest_kernel<<<ew_grid(total), 256, 0, (hipStream_t)stream>>>(x, y, total, Hi, Wi, Ho, Wo, ycs / 4, xcs, ycs, (float)Hi / (float)Ho,
+  interp_nearest_kernel<<<cat::ew_grid(total, kEwCap), 256, 0, (hipStream_t)stream>>>(x, y, total, Hi, Wi, Ho, Wo, ycs / 4, xcs, ycs, (float)Hi / (float)Ho,
                                                                          (float)Wi / (float)Wo);
   return cat::check_launch("interp_nearest");
 }
@@ -714,7 +686,7 @@ int cat_upsample_nearest_bwd(const float* dy, float* dx, int N, int Hi, int Wi, 
   CAT_REQUIRE(cs % 4 == 0 && cs >= C && f >= 1 && N > 0, "upsample_nearest_bwd: bad geometry");
   cat::ProfScope prof("upsample_bwd", 0.0, 4.0 * (double)N * Hi * Wi * cs * (f * f + 1), stream);
   const int64_t total = (int64_t)N * Hi * Wi * (cs / 4);
-  upsample_bwd_kernel<<<ew_grid(total), 256, 0, (hipStream_t)stream>>>(dy, dx, total, Hi, Wi, f, cs / 4, cs);
+  upsample_bwd_kernel<<<cat::ew_grid(total, kEwCap), 256, 0, (hipStream_t)stream>>>(dy, dx, total, Hi, Wi, f, cs / 4, cs);
   return cat::check_launch("upsample_nearest_bwd");
 }
 
@@ -723,7 +695,7 @@ int cat_avgpool3x3s2_fwd(const float* x, float* y, int N, int H, int W, int C, i
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   cat::ProfScope prof("avgpool", 0.0, 4.0 * (double)N * cs * ((double)H * W + (double)Ho * Wo), stream);
   const int64_t total = (int64_t)N * Ho * Wo * (cs / 4);
-  avgpool_fwd_kernel<<<ew_grid(total), 256, 0, (hipStream_t)stream>>>(x, y, total, H, W, Ho, Wo, cs / 4, cs);
+  avgpool_fwd_kernel<<<cat::ew_grid(total, kEwCap), 256, 0, (hipStream_t)stream>>>(x, y, total, H, W, Ho, Wo, cs / 4, cs);
   return cat::check_launch("avgpool_fwd");
 }
 
@@ -732,7 +704,7 @@ int cat_avgpool3x3s2_bwd(const float* dy, float* dx, int N, int H, int W, int C,
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   cat::ProfScope prof("avgpool", 0.0, 4.0 * (double)N * cs * ((double)H * W + (double)Ho * Wo), stream);
   const int64_t total = (int64_t)N * H * W * (cs / 4);
-  avgpool_bwd_kernel<<<ew_grid(total), 256, 0, (hipStream_t)stream>>>(dy, dx, total, H, W, Ho, Wo, cs / 4, cs);
+  avgpool_bwd_kernel<<<cat::ew_grid(total, kEwCap), 256, 0, (hipStream_t)stream>>>(dy, dx, total, H, W, Ho, Wo, cs / 4, cs);
   return cat::check_launch("avgpool_bwd");
 }
 
@@ -741,7 +713,7 @@ int cat_maxpool2x2_fwd(const float* x, float* y, int N, int H, int W, int C, int
   const int Ho = H / 2, Wo = W / 2;
   cat::ProfScope prof("maxpool", 0.0, 5.0 * (double)N * Ho * Wo * cs * 4.0, stream);
   const int64_t total = (int64_t)N * Ho * Wo * (cs / 4);
-  maxpool_fwd_kernel<<<ew_grid(total), 256, 0, (hipStream_t)stream>>>(x, y, total, H, W, Ho, Wo, cs / 4, cs);
+  maxpool_fwd_kernel<<<cat::ew_grid(total, kEwCap), 256, 0, (hipStream_t)stream>>>(x, y, total, H, W, Ho, Wo, cs / 4, cs);
   return cat::check_launch("maxpool_fwd");
 }
 
@@ -752,14 +724,14 @@ int cat_maxpool2x2_bwd(const float* x, const float* dy, float* dx, int N, int H,
   hipStream_t s = (hipStream_t)stream;
   if ((H & 1) || (W & 1)) hipMemsetAsync(dx, 0, (size_t)N * H * W * cs * sizeof(float), s);   // odd edge rows / columns get no gradient
   const int64_t total = (int64_t)N * Ho * Wo * (cs / 4);
-  maxpool_bwd_kernel<<<ew_grid(total), 256, 0, s>>>(x, dy, dx, total, H, W, Ho, Wo, cs / 4, cs);
+  maxpool_bwd_kernel<<<cat::ew_grid(total, kEwCap), 256, 0, s>>>(x, dy, dx, total, H, W, Ho, Wo, cs / 4, cs);
   return cat::check_launch("maxpool_bwd");
 }
 
 int cat_onehot_edges(const int* label, const int* inst, float* y, int N, int H, int W, int nc, int cs, cat_stream_t stream) {
   CAT_REQUIRE(cs % 4 == 0 && cs >= nc + (inst ? 1 : 0) && N > 0 && label, "onehot_edges: bad geometry");
   const int64_t total = (int64_t)N * H * W * (cs / 4);
-  onehot_edges_kernel<<<ew_grid(total), 256, 0, (hipStream_t)stream>>>(label, inst, y, total, H, W, nc, cs / 4, cs);
+  onehot_edges_kernel<<<cat::ew_grid(total, kEwCap), 256, 0, (hipStream_t)stream>>>(label, inst, y, total, H, W, nc, cs / 4, cs);
   return cat::check_launch("onehot_edges");
 }
 
@@ -783,7 +755,7 @@ int cat_spectral_norm_fwd(const float* w, int O, int I, int taps, int wcs, float
     sn_sigma_kernel<<<1, 1024, 0, s>>>(sv, u, sigma, O);
   }
   const int64_t n4 = (int64_t)O * Kp / 4;
-  sn_scale_kernel<<<ew_grid(n4), 256, 0, s>>>(w, sigma, w_sn, n4);
+  sn_scale_kernel<<<cat::ew_grid(n4, kEwCap), 256, 0, s>>>(w, sigma, w_sn, n4);
   return cat::check_launch("spectral_norm_fwd");
 }
 
@@ -795,7 +767,7 @@ int cat_spectral_norm_bwd(const float* gw, const float* w_sn, const float* u, co
   int npart = (int)((n + 256 * 64 - 1) / (256 * 64));
   if (npart > 1024) npart = 1024;
   sn_dot_kernel<<<npart, 256, 0, s>>>(gw, w_sn, (float*)ws, n);
-  sn_bwd_kernel<<<ew_grid(n), 256, 0, s>>>(gw, (const float*)ws, npart, u, vp, sigma, dw, n, taps * wcs, accumulate);
+  sn_bwd_kernel<<<cat::ew_grid(n, kEwCap), 256, 0, s>>>(gw, (const float*)ws, npart, u, vp, sigma, dw, n, taps * wcs, accumulate);
   return cat::check_launch("spectral_norm_bwd");
 }
 
