@@ -272,6 +272,7 @@ SIGNATURES = {
     'cat_pixeld_fwd3': (c_i, [_PD, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     'cat_pixeld_bwd1': (c_i, [_PD, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
     'cat_pixeld_bwd2': (c_i, [_PD, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    'cat_image_pool_query': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p]),
 }
 
 _lib = None

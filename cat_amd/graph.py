@@ -10,7 +10,8 @@ torch.cuda.CUDAGraph, which also pins the caching-allocator pool the captured ke
 
 What is captured is exactly model.set_input + model.optimize_parameters, including the side-stream branches (fork / join
 events become graph dependencies) and both Adam updates.  Loss tensors are graph outputs: `model.get_current_losses()` reads
-them after a replay.  Data-parallel steps (RCCL collectives between the backward passes) stay eager."""
+them after a replay.  Host decisions a capture cannot record -- the random draws of the CycleGAN image pools -- are taken per replay by
+`model.stage_replay(batch)` and handed to the graph through device memory (models/image_pool.py).  Data-parallel steps (RCCL collectives between the backward passes) stay eager."""
 import os
 
 import torch
@@ -86,6 +87,9 @@ class GraphedStep:
         for opt in self.model.optimizers:       # LambdaLR / manual lr changes since the capture
             if hasattr(opt, 'sync_hyper_for_replay'):
                 opt.sync_hyper_for_replay()
+        stage = getattr(self.model, 'stage_replay', None)      # host.StepHost's hook; a bare stand-in model has nothing to stage
+        if stage is not None:
+            stage(batch)
         self.graph.replay()
         if self._stale:
             self._rebind()

@@ -87,6 +87,11 @@ class StepHost:
         gradient all-reduce and Adam update in flight until the weights are needed): called by everything that reads weights or optimizer
         state.  Nothing is ever pending in the other steps."""
 
+    def stage_replay(self, batch):
+        """Called by cat_amd.graph.GraphedStep before it replays the captured step on `batch`: host decisions the capture could not record
+        (the CycleGAN image pools' random draws) are taken here and handed to the graph through device memory.  Nothing to stage in the
+        other steps."""
+
     def get_current_visuals(self):
         self.finish_pending()
         return OrderedDict((n, getattr(self, n)) for n in self.visual_names if hasattr(self, n))

@@ -144,6 +144,11 @@ class CycleGANModel(BaseModel):
             self.dp.reduce(self.optimizer_D)
         self.optimizer_D.step()
 
+    def stage_replay(self, batch):
+        # the order in which the eager step queries the pools (backward_D_A first): they share one generator
+        self.fake_B_pool.stage(batch['A'].shape[0])
+        self.fake_A_pool.stage(batch['B'].shape[0])
+
     def test_single_side(self, direction):
         generator = getattr(self, 'netG_%s' % direction[0])
         with torch.no_grad():

@@ -728,6 +728,17 @@ int cat_pixeld_bwd2(const cat_pixeld_t* g, const float* x, const float* z, const
                     const float* b1, const float* w2, float* dx, int params, float* dw1, float* db1, float* dw2, float* db2, int accumulate,
                     float* ws, cat_stream_t stream);
 
+/* The image history pool of the CycleGAN discriminators (image_pool.hip).  Replaces the per-image loop of utils/image_pool.py:27-53 by one
+ * launch.  images / out are [n][per], pool is [pool_size][per], per = floats of one NHWC image (a multiple of 4).  codes holds n int32 values in
+ * DEVICE memory (a captured launch reads what the host staged for this replay), applied in image order:
+ *   -1      pass:  out[i] = images[i]
+ *   s >= 0  swap:  out[i] = pool[s], then pool[s] = images[i]
+ *   -2 - s  store: pool[s] = images[i], out[i] = images[i]      (the pool is still filling)
+ * Sequential like the reference's loop (a slot may repeat within a batch): one lane owns one float4 element of every image and slot.
+ * A code whose slot is outside [0, pool_size) is applied as a pass.  n == 0 is a no-op. */
+int cat_image_pool_query(const float* images, float* pool, float* out, const int32_t* codes, int n, int pool_size, int64_t per,
+                         cat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
