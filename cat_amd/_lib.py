@@ -134,6 +134,18 @@ class PixelDPlan(C.Structure):
                [(n, c_l) for n in ('table_floats', 'ws1_floats', 'ws2_floats')]
 
 
+DATA_MAXPLANES = 4
+DATA_IMAGE, DATA_LABEL, DATA_INT32 = 0, 1, 2
+
+
+class DataPlane(C.Structure):
+    _fields_ = [('src', c_p), ('dst', c_p)] + [(n, c_i) for n in ('M', 'H', 'W', 'Hc', 'Wc', 'kind', 'C', 'cs', 'slot')]
+
+
+class DataBatch(C.Structure):
+    _fields_ = [('planes', c_i), ('N', c_i), ('unknown', c_f), ('plane', DataPlane * DATA_MAXPLANES)]
+
+
 PAD_ZERO, PAD_REFLECT = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_RELU6 = 0, 1, 2, 3, 4
 NORM_INSTANCE, NORM_BATCH = 0, 1
@@ -273,6 +285,7 @@ SIGNATURES = {
     'cat_pixeld_bwd1': (c_i, [_PD, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
     'cat_pixeld_bwd2': (c_i, [_PD, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
     'cat_image_pool_query': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p]),
+    'cat_data_batch': (c_i, [C.POINTER(DataBatch), c_p, c_p]),
 }
 
 _lib = None

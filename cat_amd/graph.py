@@ -16,6 +16,8 @@ import os
 
 import torch
 
+from . import ops
+
 
 def capture(run, warmup):
     """`run(i)` `warmup` times eagerly on a side stream (settles lazy state: flattened optimiser buffers, weight re-housing, folds, filter
@@ -35,6 +37,19 @@ def capture(run, warmup):
     return graph, out
 
 
+def _static_input(v, dev):
+    """The static buffer of one input tensor.  clone() compacts a view that is not dense -- an NHWC activation of 3 channels in 4 lanes would
+    come back with 3 floats per pixel, no activation any more -- so an activation is cloned with its pad lanes and stays one: set_input then
+    passes it through, and data.DeviceLoader.fill can write the next batch into it."""
+    v = v.to(dev)
+    if v.dim() == 4 and ops.is_act(v) and not v.is_contiguous():
+        n, c, h, w = v.shape
+        cs = ops.act_cs(v)
+        full = torch.as_strided(v, (n, h, w, cs), (h * w * cs, w * cs, cs, 1)).clone()
+        return full[..., :c].permute(0, 3, 1, 2)
+    return v.clone()
+
+
 class GraphedStep:
     def __init__(self, model, example_batch, warmup=3):
         if getattr(model, 'dp', None) is not None:
@@ -43,7 +58,7 @@ class GraphedStep:
         # static input buffers live on the model's device (a DataLoader batch is a host tensor: its H2D copy is done per call,
         # outside the graph); non-tensor entries (image paths) are refreshed per call
         dev = getattr(model, 'device', None) or torch.device('cuda', torch.cuda.current_device())
-        self.static = {k: (v.to(dev).clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()}
+        self.static = {k: (_static_input(v, dev) if torch.is_tensor(v) else v) for k, v in example_batch.items()}
         def step(i):
             model.set_input(self.static)
             model.optimize_parameters(i)
@@ -80,6 +95,8 @@ class GraphedStep:
                 self._stale = True
                 return
         for k, v in batch.items():
+            if k in self.static and v is self.static[k]:           # written in place (data.DeviceLoader.fill(codes, out=step.static)): nothing to copy
+                continue
             if torch.is_tensor(v):
                 self.static[k].copy_(v, non_blocking=True)
             else:

@@ -739,6 +739,36 @@ int cat_pixeld_bwd2(const cat_pixeld_t* g, const float* x, const float* z, const
 int cat_image_pool_query(const float* images, float* pool, float* out, const int32_t* codes, int n, int pool_size, int64_t per,
                          cat_stream_t stream);
 
+/* A training batch out of a device-resident image set (data_ops.hip).  Replaces, per batch, the per-sample crop / flip / ToTensor / Normalize of
+ * data/base_dataset.py:85-129, the H2D copy and the layout launch of set_input by one launch over up to 4 planes.  For every plane, output pixel
+ * (n, i, j) reads source pixel (idx_n, y_n + i, flip_n ? x_n + Wc - 1 - j : x_n + j) of that plane's set.  codes: int32 [N][2 + 3 * planes] in
+ * DEVICE memory, row n = { sample index of slot 0, of slot 1, then (x, y, flip) of plane 0, of plane 1, ... }; a plane reads the index its
+ * `slot` names (the A and B sides of unaligned data are indexed independently; planes of one sample share slot 0).  Source coordinates and
+ * indices are clamped into the set: the host validates the codes it draws, a bad one reads a wrong pixel, never outside the set.
+ *   CAT_DATA_IMAGE  src uint8 [M][H][W][4] (RGBx, one dword per pixel, as cat_image_quantize writes) -> dst float32 NHWC [N][Hc][Wc][cs]:
+ *                   lane c < C = ((u / 255) - 0.5) / 0.5, every float32 operation rounded on its own; lanes [C, cs) = 0.  C = 1 or 3.
+ *   CAT_DATA_LABEL  src uint8 [M][H][W] -> dst float32 [N][1][Hc][Wc]: (float)u, 255 -> `unknown` (ToTensor(label) * 255.0 and the
+ *                   `== 255` replacement of data/cityscapes_dataset.py:91-93; fl(fl(u / 255) * 255) == u for all 256 bytes)
+ *   CAT_DATA_INT32  src int32 [M][H][W] -> dst int32 [N][1][Hc][Wc] (the instance map)
+ * N == 0 is a no-op. */
+#define CAT_DATA_MAXPLANES 4
+enum { CAT_DATA_IMAGE = 0, CAT_DATA_LABEL = 1, CAT_DATA_INT32 = 2 };
+typedef struct {
+  const void* src; /* the plane's set on the device */
+  void* dst;       /* this batch's output */
+  int M, H, W;     /* images in the set and their size */
+  int Hc, Wc;      /* output (crop) size, Hc <= H, Wc <= W */
+  int kind;        /* CAT_DATA_* */
+  int C, cs;       /* CAT_DATA_IMAGE: logical channels and the destination's floats per pixel (multiple of 4) */
+  int slot;        /* which of the row's two sample indices this plane reads: 0 or 1 */
+} cat_data_plane_t;
+typedef struct {
+  int planes, N;   /* 1 .. CAT_DATA_MAXPLANES planes, N samples */
+  float unknown;   /* CAT_DATA_LABEL: the value written for byte 255 */
+  cat_data_plane_t plane[CAT_DATA_MAXPLANES];
+} cat_data_batch_t;
+int cat_data_batch(const cat_data_batch_t* t, const int32_t* codes, cat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
