@@ -28,7 +28,7 @@ WGRAD_BATCH_MAX = 8
 
 class NormGeom(C.Structure):
     _fields_ = [('N', c_i), ('HW', c_i), ('C', c_i), ('cs', c_i), ('mode', c_i), ('eps', c_f), ('momentum', c_f),
-                ('act', c_i), ('slope', c_f)]
+                ('act', c_i), ('slope', c_f), ('shards', c_i)]
 
 
 TCONV_MAXSEG = 8
@@ -208,6 +208,7 @@ SIGNATURES = {
     'cat_tstage1_dgrad': (c_i, [C.POINTER(Stage1Geom), c_p, c_p, c_p, c_p, c_p]),
     'cat_tnorm_finalize': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_p]),
     'cat_tnorm_finalize2': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_p]),
+    'cat_tnorm_finalize_groups': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_p]),
     'cat_tnorm_sums': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
     'cat_tnorm_finalize_sums': (c_i, [c_p, c_d, c_i, c_p, c_p, c_i, c_p, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p]),
     'cat_qconv_min_tiles16': (c_i, [c_i]),
@@ -245,6 +246,9 @@ SIGNATURES = {
     'cat_ka_ws_bytes': (C.c_size_t, [c_i]),
     'cat_ka_fwd': (c_i, [c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p]),
     'cat_ka_bwd': (c_i, [c_p, c_l, c_i, c_p, c_p, c_p, c_p]),
+    'cat_ka_sharded_ws_bytes': (C.c_size_t, [c_i, c_i]),
+    'cat_ka_sharded_fwd': (c_i, [c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p]),
+    'cat_ka_sharded_bwd': (c_i, [c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     'cat_loss_ws_bytes': (C.c_size_t, [c_l]),
     'cat_loss_fwd': (c_i, [c_i, c_p, c_p, c_f, c_l, c_i, c_i, c_p, c_p, c_p]),
     'cat_loss_bwd': (c_i, [c_i, c_p, c_p, c_f, c_l, c_i, c_i, c_p, c_f, c_p, c_p]),

@@ -23,8 +23,11 @@ struct FinArgs {
 };
 
 // grid (cdiv(cs, 4), G), one wave per channel; part[((g * tiles + t) * 2 + {0,1}) * scs + c]
+// Group g = images [g * ipg, min(nimg, (g + 1) * ipg)).  rows != 0 (groups of several samples, cat_tnorm_finalize_groups): scale / shift are
+// written once per IMAGE of the group ([nimg][cs], the per-sample form every consumer already takes for InstanceNorm), mean / rstd once per
+// group, and only group 0 touches the running statistics.
 __global__ __launch_bounds__(256) void tnorm_finalize_kernel(const float* __restrict__ part, int scs, int tiles, int tiles_x, int Ho, int Wo,
-                                                             int th, int tw, int ncls, int imgs_per_group, const float* __restrict__ gamma,
+                                                             int th, int tw, int ncls, int ipg, int nimg, int rows, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, FinArgs fa, float eps, float momentum,
                                                              float* __restrict__ scale, float* __restrict__ shift,
                                                              float* __restrict__ mean_out, float* __restrict__ rstd_out, int cs,
@@ -41,16 +44,18 @@ __global__ __launch_bounds__(256) void tnorm_finalize_kernel(const float* __rest
   int sl = -1;
   for (int k = 0; k < fa.nsl; ++k)
     if (c >= fa.sl[k].c0 && c < fa.sl[k].c0 + fa.sl[k].c) sl = k;
-  const int idx = g * cs + c, midx = g * mstride + c;
+  const int imgs_per_group = min(ipg, nimg - g * ipg);      // (the last group may be short)
+  const int nrow = rows ? imgs_per_group : 1;
+  const int idx = (rows ? g * ipg : g) * cs + c, midx = g * mstride + c;
   if (sl < 0) {
     if (lane == 0) {
-      scale[idx] = shift[idx] = 0.f;
+      for (int r = 0; r < nrow; ++r) scale[idx + r * cs] = shift[idx + r * cs] = 0.f;
       if (c < mstride) mean_out[midx] = rstd_out[midx] = 0.f;
     }
     return;
   }
   const int per_img = tiles, ntile = tiles * imgs_per_group;
-  const float* pg = part + (int64_t)g * ntile * 2 * scs + c;
+  const float* pg = part + (int64_t)g * tiles * ipg * 2 * scs + c;
   // every lane fetches its tiles' (sum, M2) pairs up front (independent loads: one L2 round trip instead of one per tile and pass)
   constexpr int R = 16;                  // tiles per lane kept in registers (1024 / 4096 tiles); longer tables loop
   float s = 0.f;
@@ -111,15 +116,18 @@ __global__ __launch_bounds__(256) void tnorm_finalize_kernel(const float* __rest
   rstd_out[midx] = rstd;
   const cat_nslice_t& S = fa.sl[sl];
   const int cl = c - S.c0;
-  if (S.running_mean) {   // BatchNorm2d.train(): momentum update with the unbiased variance
+  if (S.running_mean && g == 0) {   // BatchNorm2d.train(): momentum update with the unbiased variance (sample groups: replica 0's only)
     S.running_mean[cl] = (1.f - momentum) * S.running_mean[cl] + momentum * mean;
     const float unb = count > 1.f ? var * count / (count - 1.f) : var;
     S.running_var[cl] = (1.f - momentum) * S.running_var[cl] + momentum * unb;
     if (S.num_batches && cl == 0) *S.num_batches += 1;
   }
   const float ga = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
-  scale[idx] = ga * rstd;
-  shift[idx] = be - mean * ga * rstd;
+  const float sc = ga * rstd, sh = be - mean * ga * rstd;
+  for (int r = 0; r < nrow; ++r) {
+    scale[idx + r * cs] = sc;
+    shift[idx + r * cs] = sh;
+  }
 }
 
 // SynchronizedBatchNorm over ranks for the fused units (models/modules/sync_batchnorm/batchnorm.py:103-140): the tile table of THIS rank is
@@ -393,7 +401,27 @@ int cat_tnorm_finalize2(const float* part, int scs, int G, int N, int Ho, int Wo
   CAT_REQUIRE(th > 0 && tw > 0 && ncls >= 1, "tnorm finalize: tile geometry");
   const int tiles_x = cdiv(Wo, tw), tiles = tiles_x * cdiv(Ho, th) * ncls;
   const int64_t ntile = (int64_t)tiles * (G == 1 ? N : 1);
-  tnorm_finalize_kernel<<<dim3(ntile > 1024 ? scs : cdiv(scs, 4), G), 256, 0, (hipStream_t)stream>>>(part, scs, tiles, tiles_x, Ho, Wo, th, tw, ncls, G == 1 ? N : 1, gamma,
+  tnorm_finalize_kernel<<<dim3(ntile > 1024 ? scs : cdiv(scs, 4), G), 256, 0, (hipStream_t)stream>>>(part, scs, tiles, tiles_x, Ho, Wo, th, tw, ncls, G == 1 ? N : 1, N, 0, gamma,
+                                                                                  beta, fa, eps, momentum, scale, shift, mean, rstd, scs, mstride);
+  return cat::check_launch("tnorm_finalize");
+}
+
+int cat_tnorm_finalize_groups(const float* part, int scs, int P, int N, int Ho, int Wo, int th, int tw, int ncls, const float* gamma,
+                              const float* beta, int nslices, const cat_nslice_t* slices, float eps, float momentum, float* scale, float* shift,
+                              float* mean, float* rstd, int mstride, cat_stream_t stream) {
+  CAT_REQUIRE(N >= 1 && P >= 1 && P <= N, "tnorm finalize groups: %d samples per group of a batch of %d", P, N);
+  CAT_REQUIRE(nslices >= 1 && nslices <= CAT_TNORM_MAXSLICE && (scs & 3) == 0, "tnorm finalize: %d slices", nslices);
+  FinArgs fa{};
+  fa.nsl = nslices;
+  for (int k = 0; k < nslices; ++k) {
+    fa.sl[k] = slices[k];
+    CAT_REQUIRE(slices[k].c0 >= 0 && slices[k].c > 0 && slices[k].c0 + slices[k].c <= scs, "tnorm finalize: slice %d outside the table", k);
+  }
+  CAT_REQUIRE(th > 0 && tw > 0 && ncls >= 1, "tnorm finalize: tile geometry");
+  const int G = cdiv(N, P);
+  const int tiles_x = cdiv(Wo, tw), tiles = tiles_x * cdiv(Ho, th) * ncls;
+  const int64_t ntile = (int64_t)tiles * P;
+  tnorm_finalize_kernel<<<dim3(ntile > 1024 ? scs : cdiv(scs, 4), G), 256, 0, (hipStream_t)stream>>>(part, scs, tiles, tiles_x, Ho, Wo, th, tw, ncls, P, N, 1, gamma,
                                                                                   beta, fa, eps, momentum, scale, shift, mean, rstd, scs, mstride);
   return cat::check_launch("tnorm_finalize");
 }

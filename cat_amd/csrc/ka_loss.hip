@@ -7,6 +7,9 @@
 // lane l loads X[row = l&15][k0 + 4*(l>>4) .. +3]  (4 lanes x 16 B = 64 contiguous bytes per row per load).
 // Partials are written per workgroup and reduced by a single finalize block (deterministic).
 // Backward: dX = gout * 2 * Cx X with the N x N matrix Cx = Gy/sqrt(sxx syy) - sxy Gx/(sxx^1.5 syy^0.5).
+// Sharded form (cat_ka_sharded_*): the batch is cut like torch.chunk(batch, S) into shards of P = ceil(N / S) consecutive rows (the last may be
+// short) and every kernel takes the shard from blockIdx.y -- the KA of each shard's own Gram pair, as S data-parallel replicas compute
+// it, summed or averaged by one more single-block launch.  One shard (gridDim.y == 1) is the plain form, launch for launch.
 #include "common.h"
 
 namespace {
@@ -15,9 +18,12 @@ using cat::cdiv;
 constexpr int KA_MAXN = 64;
 
 template <int NT>
-__global__ __launch_bounds__(256) void gram_kernel(const float* __restrict__ X, int64_t D, int N, float* __restrict__ part,
+__global__ __launch_bounds__(256) void gram_kernel(const float* __restrict__ X, int64_t D, int Ntot, int P, float* __restrict__ part,
                                                    int64_t chunk) {
-  // part: [gridDim.x][NT*16][NT*16]
+  // part: [gridDim.y][gridDim.x][NT*16][NT*16]; shard blockIdx.y = rows [y * P, min(Ntot, (y + 1) * P))
+  const int N = min(P, Ntot - (int)blockIdx.y * P);
+  X += (int64_t)blockIdx.y * P * D;
+  part += (int64_t)blockIdx.y * gridDim.x * (NT * 16) * (NT * 16);
   __shared__ float red[4][NT * NT][256];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 15, lq = lane >> 4;
@@ -66,16 +72,19 @@ __global__ __launch_bounds__(256) void gram_kernel(const float* __restrict__ X, 
   }
 }
 
-// ws layout (floats): [0..3] sxy, sxx, syy, ka | Gx[N*N] | Gy[N*N] | partX[nb][NN*NN] | partY[nb][NN*NN]
+// ws layout (floats): G shard heads of hs = 4 + 2 * P * P floats, each [0..3] sxy, sxx, syy, ka | Gx[N*N] | Gy[N*N] (N = the shard's rows), then
+// partX[G][nbx][NN*NN] | partY[G][nby][NN*NN]
 // stage 1: Gx / Gy entries = sum of the per-workgroup partials; 16 entries x 16 partial-lanes per workgroup, four independent loads per lane and
 // step, lanes combined pairwise through LDS in a fixed order (round 6: 64 entries x 4 lanes = 4 workgroups walked 2 x 128 dependent loads
 // per lane: 43 us per loss term for 2 MB of partials)
-__global__ __launch_bounds__(256) void ka_gram_reduce_kernel(float* __restrict__ ws, int N, int NN, int nbx, int nby) {
+__global__ __launch_bounds__(256) void ka_gram_reduce_kernel(float* __restrict__ ws, int Ntot, int P, int NN, int nbx, int nby) {
   __shared__ float red[2][256];
-  float* Gx = ws + 4;
+  const int sh = blockIdx.y, G = gridDim.y, N = min(P, Ntot - sh * P);
+  const int64_t hs = 4 + 2 * (int64_t)P * P;
+  float* Gx = ws + sh * hs + 4;
   float* Gy = Gx + N * N;
-  const float* px = Gy + N * N;
-  const float* py = px + (int64_t)nbx * NN * NN;
+  const float* px = ws + G * hs + (int64_t)sh * nbx * NN * NN;
+  const float* py = ws + G * hs + (int64_t)G * nbx * NN * NN + (int64_t)sh * nby * NN * NN;
   const int e = blockIdx.x * 16 + (threadIdx.x & 15), zl = threadIdx.x >> 4;
   float gx = 0.f, gy = 0.f;
   if (e < N * N) {
@@ -120,8 +129,10 @@ __global__ __launch_bounds__(256) void ka_gram_reduce_kernel(float* __restrict__
 }
 
 // stage 2: ws[0..3] = sxy, sxx, syy, ka
-__global__ __launch_bounds__(256) void ka_finalize_kernel(float* __restrict__ ws, int N, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void ka_finalize_kernel(float* __restrict__ ws, int Ntot, int P, float* __restrict__ out) {
   __shared__ float red[3][256];
+  const int N = min(P, Ntot - (int)blockIdx.x * P);
+  ws += blockIdx.x * (4 + 2 * (int64_t)P * P);
   const float* Gx = ws + 4;
   const float* Gy = Gx + N * N;
   float sxy = 0.f, sxx = 0.f, syy = 0.f;
@@ -150,18 +161,30 @@ __global__ __launch_bounds__(256) void ka_finalize_kernel(float* __restrict__ ws
     ws[1] = b;
     ws[2] = c;
     ws[3] = ka;
-    out[0] = ka;
+    if (out) out[0] = ka;
   }
 }
 
+// out[0] = scale * (ka_0 + ka_1 + ...) in shard order: the sum of the replicas' terms, or their mean
+__global__ void ka_combine_kernel(const float* __restrict__ ws, int G, int64_t hs, float scale, float* __restrict__ out) {
+  if (threadIdx.x != 0) return;
+  float s = 0.f;
+  for (int g = 0; g < G; ++g) s += ws[g * hs + 3];
+  out[0] = s * scale;
+}
+
 // dX[i][k] = gout * 2 * sum_j Cx[i][j] X[j][k]; one lane per float4 column, 8 output rows at a time.
-__global__ __launch_bounds__(256) void ka_bwd_kernel(const float* __restrict__ X, int64_t D, int N, const float* __restrict__ gout,
-                                                     const float* __restrict__ ws, float* __restrict__ dX) {
+__global__ __launch_bounds__(256) void ka_bwd_kernel(const float* __restrict__ X, int64_t D, int Ntot, int P, float gscale,
+                                                     const float* __restrict__ gout, const float* __restrict__ ws, float* __restrict__ dX) {
   __shared__ float C[KA_MAXN * KA_MAXN];
+  const int N = min(P, Ntot - (int)blockIdx.y * P);      // shard blockIdx.y: its rows of X / dX, its head of ws
+  X += (int64_t)blockIdx.y * P * D;
+  dX += (int64_t)blockIdx.y * P * D;
+  ws += blockIdx.y * (4 + 2 * (int64_t)P * P);
   const float sxy = ws[0], sxx = ws[1], syy = ws[2];
   const float* Gx = ws + 4;
   const float* Gy = Gx + N * N;
-  const float g = gout[0] * 2.f;
+  const float g = gout[0] * gscale;
   const float ca = g / sqrtf(sxx * syy), cb = g * sxy / (sxx * sqrtf(sxx * syy));
   for (int e = threadIdx.x; e < N * N; e += 256) C[e] = ca * Gy[e] - cb * Gx[e];
   __syncthreads();
@@ -200,14 +223,44 @@ GramPlan gram_plan(int N, int64_t D) {
 }
 constexpr int KA_MAXNB = 512;
 
-int launch_gram(const float* X, int64_t D, int N, float* part, const GramPlan& p, hipStream_t s) {
+// the Grams of G shards of P rows (the last may be short) of the N rows of X: one launch
+int launch_gram(const float* X, int64_t D, int N, int P, int G, float* part, const GramPlan& p, hipStream_t s) {
+  const dim3 grid(p.nb, G);
   switch (p.NT) {
-    case 1: gram_kernel<1><<<p.nb, 256, 0, s>>>(X, D, N, part, p.chunk); break;
-    case 2: gram_kernel<2><<<p.nb, 256, 0, s>>>(X, D, N, part, p.chunk); break;
-    case 3: gram_kernel<3><<<p.nb, 256, 0, s>>>(X, D, N, part, p.chunk); break;
-    default: gram_kernel<4><<<p.nb, 256, 0, s>>>(X, D, N, part, p.chunk); break;
+    case 1: gram_kernel<1><<<grid, 256, 0, s>>>(X, D, N, P, part, p.chunk); break;
+    case 2: gram_kernel<2><<<grid, 256, 0, s>>>(X, D, N, P, part, p.chunk); break;
+    case 3: gram_kernel<3><<<grid, 256, 0, s>>>(X, D, N, P, part, p.chunk); break;
+    default: gram_kernel<4><<<grid, 256, 0, s>>>(X, D, N, P, part, p.chunk); break;
   }
   return cat::check_launch("ka_gram");
+}
+
+// forward and backward of G shards of P rows each; G == 1, P == N is the unsharded form
+int ka_fwd(const float* X, int64_t Dx, const float* Y, int64_t Dy, int N, int P, int G, float scale, float* out, void* ws, hipStream_t s) {
+  const GramPlan px = gram_plan(P, Dx), py = gram_plan(P, Dy);
+  float* w = (float*)ws;
+  const int64_t hs = 4 + 2 * (int64_t)P * P;
+  float* partx = w + G * hs;
+  float* party = partx + (int64_t)G * px.nb * px.NN * px.NN;
+  if (int e = launch_gram(X, Dx, N, P, G, partx, px, s)) return e;
+  if (int e = launch_gram(Y, Dy, N, P, G, party, py, s)) return e;
+  ka_gram_reduce_kernel<<<dim3(cdiv(P * P, 16), G), 256, 0, s>>>(w, N, P, px.NN, px.nb, py.nb);
+  ka_finalize_kernel<<<G, 256, 0, s>>>(w, N, P, G == 1 ? out : nullptr);
+  if (G > 1) ka_combine_kernel<<<1, 64, 0, s>>>(w, G, hs, scale, out);
+  return cat::check_launch("ka_finalize");
+}
+
+int ka_bwd(const float* X, int64_t Dx, int N, int P, int G, float scale, const float* gout, const void* ws, float* dX, hipStream_t s) {
+  int64_t nb = (Dx / 4 + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  ka_bwd_kernel<<<dim3((int)nb, G), 256, 0, s>>>(X, Dx, N, P, 2.f * scale, gout, (const float*)ws, dX);
+  return cat::check_launch("ka_bwd");
+}
+
+// torch.chunk(batch of N, S): P rows per shard, G = the number of shards that hold any
+void ka_shards(int N, int S, int& P, int& G) {
+  P = cdiv(N, S);
+  G = cdiv(N, P);
 }
 
 // ------------------------------------------------------------------------------------------------ scalar losses
@@ -271,26 +324,43 @@ size_t cat_ka_ws_bytes(int N) {
 int cat_ka_fwd(const float* X, int64_t Dx, const float* Y, int64_t Dy, int N, float* out, void* ws, cat_stream_t stream) {
   CAT_REQUIRE(N >= 1 && N <= KA_MAXN, "ka: batch N=%d outside [1,%d]", N, KA_MAXN);
   CAT_REQUIRE(Dx % 4 == 0 && Dy % 4 == 0 && ws, "ka: row lengths must be multiples of 4");
-  const GramPlan px = gram_plan(N, Dx), py = gram_plan(N, Dy);
   cat::ProfScope prof("ka_fwd", 2.0 * N * N * (double)(Dx + Dy), 4.0 * N * (double)(Dx + Dy), stream);
-  float* w = (float*)ws;
-  float* partx = w + 4 + 2 * N * N;
-  float* party = partx + (int64_t)px.nb * px.NN * px.NN;
-  hipStream_t s = (hipStream_t)stream;
-  if (int e = launch_gram(X, Dx, N, partx, px, s)) return e;
-  if (int e = launch_gram(Y, Dy, N, party, py, s)) return e;
-  ka_gram_reduce_kernel<<<cdiv(N * N, 16), 256, 0, s>>>(w, N, px.NN, px.nb, py.nb);
-  ka_finalize_kernel<<<1, 256, 0, s>>>(w, N, out);
-  return cat::check_launch("ka_finalize");
+  return ka_fwd(X, Dx, Y, Dy, N, N, 1, 1.f, out, ws, (hipStream_t)stream);
 }
 
 int cat_ka_bwd(const float* X, int64_t Dx, int N, const float* gout, const void* ws, float* dX, cat_stream_t stream) {
   CAT_REQUIRE(N >= 1 && N <= KA_MAXN && Dx % 4 == 0, "ka bwd: bad arguments");
-  int64_t nb = (Dx / 4 + 255) / 256;
-  if (nb > 4096) nb = 4096;
   cat::ProfScope prof("ka_bwd", 2.0 * N * N * (double)Dx, 8.0 * N * (double)Dx, stream);
-  ka_bwd_kernel<<<(int)nb, 256, 0, (hipStream_t)stream>>>(X, Dx, N, gout, (const float*)ws, dX);
-  return cat::check_launch("ka_bwd");
+  return ka_bwd(X, Dx, N, N, 1, 1.f, gout, ws, dX, (hipStream_t)stream);
+}
+
+size_t cat_ka_sharded_ws_bytes(int N, int S) {
+  if (N < 1 || S < 1) return 0;
+  int P, G;
+  ka_shards(N, S, P, G);
+  const int NN = cdiv(P, 16) * 16;
+  return (size_t)G * (4 + 2 * (size_t)P * P + 2 * (size_t)KA_MAXNB * NN * NN) * sizeof(float);
+}
+
+int cat_ka_sharded_fwd(const float* X, int64_t Dx, const float* Y, int64_t Dy, int N, int S, int mean, float* out, void* ws,
+                       cat_stream_t stream) {
+  CAT_REQUIRE(N >= 1 && S >= 1, "ka sharded: N=%d rows in S=%d shards", N, S);
+  int P, G;
+  ka_shards(N, S, P, G);
+  CAT_REQUIRE(P <= KA_MAXN, "ka sharded: %d rows per shard outside [1,%d]", P, KA_MAXN);
+  CAT_REQUIRE(Dx % 4 == 0 && Dy % 4 == 0 && ws, "ka: row lengths must be multiples of 4");
+  cat::ProfScope prof("ka_fwd", 2.0 * N * P * (double)(Dx + Dy), 4.0 * N * (double)(Dx + Dy), stream);
+  return ka_fwd(X, Dx, Y, Dy, N, P, G, mean ? 1.f / (float)G : 1.f, out, ws, (hipStream_t)stream);
+}
+
+int cat_ka_sharded_bwd(const float* X, int64_t Dx, int N, int S, int mean, const float* gout, const void* ws, float* dX,
+                       cat_stream_t stream) {
+  CAT_REQUIRE(N >= 1 && S >= 1 && Dx % 4 == 0 && ws, "ka sharded bwd: bad arguments");
+  int P, G;
+  ka_shards(N, S, P, G);
+  CAT_REQUIRE(P <= KA_MAXN, "ka sharded bwd: %d rows per shard outside [1,%d]", P, KA_MAXN);
+  cat::ProfScope prof("ka_bwd", 2.0 * N * P * (double)Dx, 8.0 * N * (double)Dx, stream);
+  return ka_bwd(X, Dx, N, P, G, mean ? 1.f / (float)G : 1.f, gout, ws, dX, (hipStream_t)stream);
 }
 
 size_t cat_loss_ws_bytes(int64_t M) { (void)M; return 1024 * sizeof(float); }

@@ -12,15 +12,21 @@ namespace {
 using cat::cdiv;
 
 struct NormPlan : cat::ColPlan {
-  int G, Pg;
+  int G, Pg, Ptot;      // Ptot = all pixels: a sharded batch norm's last group may hold fewer than Pg
   size_t part_off, scale_off, shift_off, c1_off, c2_off, bytes;
 };
 
 NormPlan plan(const cat_norm_t* g) {
-  const int G = g->mode == CAT_NORM_INSTANCE ? g->N : 1, Pg = g->mode == CAT_NORM_INSTANCE ? g->HW : g->N * g->HW;
+  int G = g->mode == CAT_NORM_INSTANCE ? g->N : 1, Pg = g->mode == CAT_NORM_INSTANCE ? g->HW : g->N * g->HW;
+  if (g->mode == CAT_NORM_BATCH && g->shards > 1) {      // torch.chunk(batch, shards): groups of ceil(N / shards) consecutive samples
+    const int per = cdiv(g->N, g->shards);
+    G = cdiv(g->N, per);
+    Pg = per * g->HW;
+  }
   NormPlan p{cat::col_plan(Pg, g->cs, G, 2048, 16, 1024)};   // stats: ~2048 workgroups, at most 1024 per group, >= 16 pixels per pixel lane
   p.G = G;
   p.Pg = Pg;
+  p.Ptot = g->N * g->HW;
   size_t off = 0;
   p.part_off = off; off += (size_t)p.G * p.nb * 2 * g->cs;
   p.scale_off = off; off += (size_t)p.G * g->cs;
@@ -36,14 +42,14 @@ template <int MODE>
 __global__ __launch_bounds__(256) void norm_stats_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                         float* __restrict__ part, int Pg, int C, int cs, int zq, int ppl, int nb,
-                                                         int act, float slope) {
+                                                         float* __restrict__ part, int Pg, int Ptot, int C, int cs, int zq, int ppl,
+                                                         int nb, int act, float slope) {
   __shared__ f4 red[2][256];
   const int g = blockIdx.y, b = blockIdx.x;
   const cat::ColLanes L = cat::col_lanes(blockIdx.z, zq, ppl, cs);
   const int pl = L.pl;
   const int per = (Pg + nb - 1) / nb;
-  const int pbeg = b * per, pend = min(Pg, pbeg + per);
+  const int pbeg = b * per, pend = min(min(Pg, Ptot - g * Pg), pbeg + per);      // (the last group of a sharded batch norm may be short)
   const float* xg = x + (int64_t)g * Pg * cs;
   f4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
   if (L.active) {
@@ -107,7 +113,7 @@ __global__ __launch_bounds__(256) void norm_fwd_finalize_kernel(const float* __r
                                                                 float* __restrict__ save_mean, float* __restrict__ save_rstd,
                                                                 float* __restrict__ running_mean, float* __restrict__ running_var,
                                                                 float* __restrict__ scale, float* __restrict__ shift, int G, int Pg,
-                                                                int C, int cs, int nb, float eps, float momentum,
+                                                                int Ptot, int C, int cs, int nb, float eps, float momentum,
                                                                 int64_t* __restrict__ num_batches) {
   // grid (cdiv(cs,4), G); one WAVE per channel: 64 lanes stride over the nb partial blocks, wave-shuffle reduce (the serial
   // 64-channels x 4-lanes version cost 55 us at nb = 1024 -- more than the stats pass it finishes)
@@ -131,7 +137,8 @@ __global__ __launch_bounds__(256) void norm_fwd_finalize_kernel(const float* __r
   s0 = cat::wave_sum(s0);
   s1 = cat::wave_sum(s1);
   if (lane != 0) return;
-  const float inv = 1.f / (float)Pg;
+  const int Pn = min(Pg, Ptot - g * Pg);      // this group's pixels
+  const float inv = 1.f / (float)Pn;
   const float d = s0 * inv;
   const float mean = x[(int64_t)g * Pg * cs + c] + d;
   float var = s1 * inv - d * d;
@@ -139,9 +146,9 @@ __global__ __launch_bounds__(256) void norm_fwd_finalize_kernel(const float* __r
   const float rstd = rsqrtf(var + eps);
   save_mean[g * C + c] = mean;
   save_rstd[g * C + c] = rstd;
-  if (running_mean) {  // batch norm only (G == 1)
+  if (running_mean && g == 0) {  // batch norm only; of a sharded one group 0 alone (replica 0 shares its buffers with the module)
     running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-    const float unb = Pg > 1 ? var * (float)Pg / (float)(Pg - 1) : var;
+    const float unb = Pn > 1 ? var * (float)Pn / (float)(Pn - 1) : var;
     running_var[c] = (1.f - momentum) * running_var[c] + momentum * unb;
   }
   const float ga = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
@@ -169,8 +176,8 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict
 
 __global__ __launch_bounds__(256) void norm_bwd_finalize_kernel(const float* __restrict__ part, const float* __restrict__ gamma,
                                                                 const float* __restrict__ rstd, float* __restrict__ c1,
-                                                                float* __restrict__ c2, float* __restrict__ scale, int Pg, int C, int cs,
-                                                                int nb, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                float* __restrict__ c2, float* __restrict__ scale, int Pg, int Ptot, int C,
+                                                                int cs, int nb, float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                                 int accumulate) {
   // grid (cdiv(cs,4), G); one wave per channel (see norm_fwd_finalize_kernel): per-(group, channel) means of g and g*xhat
   const int g = blockIdx.y, c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -186,7 +193,7 @@ __global__ __launch_bounds__(256) void norm_bwd_finalize_kernel(const float* __r
   s0 = cat::wave_sum(s0);
   s1 = cat::wave_sum(s1);
   if (lane != 0) return;
-  const float inv = 1.f / (float)Pg;
+  const float inv = 1.f / (float)min(Pg, Ptot - g * Pg);
   c1[g * cs + c] = s0 * inv;
   c2[g * cs + c] = s1 * inv;
   scale[g * cs + c] = c < C ? (gamma ? gamma[c] : 1.f) * rstd[g * C + c] : 0.f;
@@ -220,17 +227,25 @@ __global__ __launch_bounds__(256) void in_running_kernel(const float* __restrict
 
 // dgamma[c] (+)= sum_g sum(g*xhat), dbeta[c] (+)= sum_g sum(g)  (sums recovered from the per-group means)
 __global__ __launch_bounds__(256) void norm_bwd_param_kernel(const float* __restrict__ c1, const float* __restrict__ c2,
-                                                             float* __restrict__ dgamma, float* __restrict__ dbeta, int G, int Pg, int C,
-                                                             int cs, int accumulate) {
+                                                             float* __restrict__ dgamma, float* __restrict__ dbeta, int G, int Pg, int Ptot,
+                                                             int C, int cs, int accumulate) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
   float tb = 0.f, tg = 0.f;
-  for (int g = 0; g < G; ++g) {
-    tb += c1[g * cs + c];
-    tg += c2[g * cs + c];
+  if (Ptot - (G - 1) * Pg == Pg) {      // equal groups: the sum of the means, scaled once
+    for (int g = 0; g < G; ++g) {
+      tb += c1[g * cs + c];
+      tg += c2[g * cs + c];
+    }
+    tb *= (float)Pg;
+    tg *= (float)Pg;
+  } else {                             // a short last group (sharded batch norm): every mean weighs its own pixel count
+    for (int g = 0; g < G; ++g) {
+      const float pn = (float)min(Pg, Ptot - g * Pg);
+      tb += c1[g * cs + c] * pn;
+      tg += c2[g * cs + c] * pn;
+    }
   }
-  tb *= (float)Pg;
-  tg *= (float)Pg;
   if (dgamma) dgamma[c] = accumulate ? dgamma[c] + tg : tg;
   if (dbeta) dbeta[c] = accumulate ? dbeta[c] + tb : tb;
 }
@@ -272,13 +287,13 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const float* __rest
 // whole walk) and strides over the pixels of its block, four independent pixels per iteration -- no per-element index division and no
 // per-element coefficient loads (the element-walk kernels issue 5 - 13 loads per float4 of payload), more loads in flight per wave.
 __global__ __launch_bounds__(256) void norm_apply_walk_kernel(const float* __restrict__ x, const float* __restrict__ scale,
-                                                              const float* __restrict__ shift, float* __restrict__ y, int Pg, int cs, int zq,
-                                                              int ppl, int nb, int act, float slope) {
+                                                              const float* __restrict__ shift, float* __restrict__ y, int Pg, int Ptot, int cs,
+                                                              int zq, int ppl, int nb, int act, float slope) {
   const int g = blockIdx.y, b = blockIdx.x, z = blockIdx.z;
   const int cq = z * zq + threadIdx.x % zq, pl = threadIdx.x / zq;
   if (pl >= ppl || cq * 4 >= cs) return;
   const int per = (Pg + nb - 1) / nb;
-  const int pbeg = b * per, pend = min(Pg, pbeg + per);
+  const int pbeg = b * per, pend = min(min(Pg, Ptot - g * Pg), pbeg + per);
   const int c = cq * 4;
   const f4 sc = *reinterpret_cast<const f4*>(scale + g * cs + c), sh = *reinterpret_cast<const f4*>(shift + g * cs + c);
   const float* xg = x + (int64_t)g * Pg * cs + c;
@@ -305,13 +320,13 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_walk_kernel(const float* _
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                   const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                   const float* __restrict__ c1, const float* __restrict__ c2,
-                                                                  const float* __restrict__ scale, float* __restrict__ dx, int Pg, int C, int cs,
-                                                                  int zq, int ppl, int nb, int act, float slope) {
+                                                                  const float* __restrict__ scale, float* __restrict__ dx, int Pg, int Ptot, int C,
+                                                                  int cs, int zq, int ppl, int nb, int act, float slope) {
   const int g = blockIdx.y, b = blockIdx.x, z = blockIdx.z;
   const int cq = z * zq + threadIdx.x % zq, pl = threadIdx.x / zq;
   if (pl >= ppl || cq * 4 >= cs) return;
   const int per = (Pg + nb - 1) / nb;
-  const int pbeg = b * per, pend = min(Pg, pbeg + per);
+  const int pbeg = b * per, pend = min(min(Pg, Ptot - g * Pg), pbeg + per);
   const int c = cq * 4;
   const f4 m1 = *reinterpret_cast<const f4*>(c1 + g * cs + c), m2 = *reinterpret_cast<const f4*>(c2 + g * cs + c);
   const f4 sc = *reinterpret_cast<const f4*>(scale + g * cs + c);
@@ -399,11 +414,11 @@ int cat_norm_fwd(const cat_norm_t* g, const float* x, const float* gamma, const 
   float* w = (float*)ws;
   hipStream_t s = (hipStream_t)stream;
   norm_stats_kernel<0><<<dim3(p.nb, p.G, p.nz), 256, 0, s>>>(x, nullptr, nullptr, nullptr, nullptr, nullptr, w + p.part_off, p.Pg,
-                                                              g->C, g->cs, p.zq, p.ppl, p.nb, 0, 0.f);
+                                                              p.Ptot, g->C, g->cs, p.zq, p.ppl, p.nb, 0, 0.f);
   norm_fwd_finalize_kernel<<<dim3(cdiv(g->cs, 4), p.G), 256, 0, s>>>(x, w + p.part_off, gamma, beta, save_mean, save_rstd,
                                                                    g->mode == CAT_NORM_BATCH ? running_mean : nullptr,
                                                                    g->mode == CAT_NORM_BATCH ? running_var : nullptr, w + p.scale_off,
-                                                                   w + p.shift_off, p.G, p.Pg, g->C, g->cs, p.nb, g->eps, g->momentum,
+                                                                   w + p.shift_off, p.G, p.Pg, p.Ptot, g->C, g->cs, p.nb, g->eps, g->momentum,
                                                                    g->mode == CAT_NORM_BATCH ? num_batches_tracked : nullptr);
   if (g->mode == CAT_NORM_INSTANCE && running_mean && running_var)
     in_running_kernel<<<cdiv(g->C, 256), 256, 0, s>>>(save_mean, save_rstd, running_mean, running_var, p.G, p.Pg, g->C, g->eps, g->momentum,
@@ -411,7 +426,7 @@ int cat_norm_fwd(const cat_norm_t* g, const float* x, const float* gamma, const 
   const int64_t nquads = (int64_t)g->N * g->HW * p.nq;
   if (walk_on()) {
     const int nbw = walk_blocks(p);
-    norm_apply_walk_kernel<<<dim3(nbw, p.G, p.nz), 256, 0, s>>>(x, w + p.scale_off, w + p.shift_off, y, p.Pg, g->cs, p.zq, p.ppl, nbw, g->act, g->slope);
+    norm_apply_walk_kernel<<<dim3(nbw, p.G, p.nz), 256, 0, s>>>(x, w + p.scale_off, w + p.shift_off, y, p.Pg, p.Ptot, g->cs, p.zq, p.ppl, nbw, g->act, g->slope);
     return cat::check_launch("norm_fwd");
   }
   norm_apply_kernel<<<cat::ew_grid(nquads, kEwCap), 256, 0, s>>>(x, w + p.scale_off, w + p.shift_off, y, nquads, p.nq, (int64_t)p.Pg * p.nq, g->cs,
@@ -427,19 +442,19 @@ int cat_norm_bwd(const cat_norm_t* g, const float* x, const float* dy, const flo
   const NormPlan p = plan(g);
   float* w = (float*)ws;
   hipStream_t s = (hipStream_t)stream;
-  norm_stats_kernel<1><<<dim3(p.nb, p.G, p.nz), 256, 0, s>>>(x, dy, gamma, beta, save_mean, save_rstd, w + p.part_off, p.Pg, g->C, g->cs,
+  norm_stats_kernel<1><<<dim3(p.nb, p.G, p.nz), 256, 0, s>>>(x, dy, gamma, beta, save_mean, save_rstd, w + p.part_off, p.Pg, p.Ptot, g->C, g->cs,
                                                               p.zq, p.ppl, p.nb, g->act, g->slope);
   const bool one_group = p.G == 1;
   norm_bwd_finalize_kernel<<<dim3(cdiv(g->cs, 4), p.G), 256, 0, s>>>(w + p.part_off, gamma, save_rstd, w + p.c1_off, w + p.c2_off,
-                                                                        w + p.scale_off, p.Pg, g->C, g->cs, p.nb, one_group ? dgamma : nullptr,
+                                                                        w + p.scale_off, p.Pg, p.Ptot, g->C, g->cs, p.nb, one_group ? dgamma : nullptr,
                                                                         one_group ? dbeta : nullptr, accumulate);
   if (!one_group && (dgamma || dbeta))
-    norm_bwd_param_kernel<<<cdiv(g->C, 256), 256, 0, s>>>(w + p.c1_off, w + p.c2_off, dgamma, dbeta, p.G, p.Pg, g->C, g->cs, accumulate);
+    norm_bwd_param_kernel<<<cdiv(g->C, 256), 256, 0, s>>>(w + p.c1_off, w + p.c2_off, dgamma, dbeta, p.G, p.Pg, p.Ptot, g->C, g->cs, accumulate);
   const int64_t nquads = (int64_t)g->N * g->HW * p.nq;
   if (walk_on()) {
     const int nbw = walk_blocks(p);
     norm_bwd_apply_walk_kernel<<<dim3(nbw, p.G, p.nz), 256, 0, s>>>(x, dy, gamma, beta, save_mean, save_rstd, w + p.c1_off, w + p.c2_off,
-                                                                     w + p.scale_off, dx, p.Pg, g->C, g->cs, p.zq, p.ppl, nbw, g->act, g->slope);
+                                                                     w + p.scale_off, dx, p.Pg, p.Ptot, g->C, g->cs, p.zq, p.ppl, nbw, g->act, g->slope);
     return cat::check_launch("norm_bwd");
   }
   norm_bwd_apply_kernel<<<cat::ew_grid(nquads, kEwCap), 256, 0, s>>>(x, dy, gamma, beta, save_mean, save_rstd, w + p.c1_off, w + p.c2_off,

@@ -33,6 +33,7 @@ class BaseInceptionDistiller(host.StepHost):
         ('--lambda_gan', dict(type=float, default=1)),
         ('--teacher_dropout_rate', dict(type=float, default=0)),
         ('--student_dropout_rate', dict(type=float, default=0)),
+        ('--virtual_replicas', dict(type=int, default=1)),      # the arithmetic of that many nn.DataParallel GPUs on this one (host.set_virtual_replicas)
     ]
 
     @staticmethod

@@ -37,6 +37,7 @@ class BaseSPADEDistiller(SPADEStep, host.StepHost):
         ('--no_TTUR', dict(action='store_true')),
         ('--no_fid', dict(action='store_true')),
         ('--no_mIoU', dict(action='store_true')),
+        ('--virtual_replicas', dict(type=int, default=1)),      # the arithmetic of that many reference GPUs on this one (host.set_virtual_replicas)
     ]
 
     @staticmethod
@@ -106,6 +107,7 @@ class BaseSPADEDistiller(SPADEStep, host.StepHost):
         m = self.modules_on_one_gpu
         reducer.broadcast_parameters([m.netG_teacher, m.netG_student, m.netD] + list(m.netAs))
         ops.set_bn_sync(reducer)
+        self.set_virtual_replicas(self.virtual_replicas)      # (a one-rank reducer installs nothing: virtual replicas keep their own exchange)
 
     # -- bookkeeping (the rest is host.StepHost's) ---------------------------------------------------------------------------
     def _networks(self):

@@ -7,7 +7,7 @@ import torch
 from torch import nn
 
 from .. import host, ops
-from ..loss import KA
+from ..loss import KA, KA_sharded
 from ..lossvalue import LossValue
 from ..prune import model_profiling
 from .base_inception_distiller import BaseInceptionDistiller
@@ -70,22 +70,31 @@ class InceptionDistiller(BaseInceptionDistiller):
 
     def calc_distill_loss(self):
         """sum_i -KA(Sact_i, Tact_i) (inception_distiller.py:106-157, 'ka' branch).  Returns the per-layer terms; the
-        weighted total is a LossValue (no torch arithmetic on the hot path)."""
+        weighted total is a LossValue (no torch arithmetic on the hot path).  With virtual replicas every term is the SUM over the
+        replicas' shards (:136-148 gathers the per-device terms and sums them): one sharded-KA launch sequence, or one MSE per shard."""
         kind = self.opt.distill_G_loss_type
         if kind not in ('ka', 'mse'):
             raise NotImplementedError(kind)
+        S = self.virtual_replicas
+        shards = 1.0      # 'mse': the per-device mean, summed -- with equal shards the whole-batch mean times their number (a seed factor)
+        if kind == 'mse' and S > 1:
+            bounds = ops.shard_bounds(self.real_A.shape[0], S)
+            if len({e - b for b, e in bounds}) != 1:
+                raise NotImplementedError('--distill_G_loss_type mse with virtual replicas needs a batch that splits into equal shards')
+            shards = float(len(bounds))
         terms = []
         for i, netA in enumerate(self.netAs):
             assert isinstance(netA, nn.Conv2d)
             n = self.mapping_layers[i]
             key = n + str(self.device)
             if kind == 'ka':
-                term = KA(self.Sacts[key], self.Tacts[key])
+                term = KA(self.Sacts[key], self.Tacts[key]) if S == 1 else KA_sharded(self.Sacts[key], self.Tacts[key], S)
                 setattr(self, 'loss_G_distill%d' % i, LossValue([(-1.0, term)]))
+                terms.append((1.0, term))
             else:       # 'mse' (:113-132): the student activation goes through the 1x1 adaptor netA first
                 term = self.criterionMSE(netA(self.Sacts[key]), self.Tacts[key])
-                setattr(self, 'loss_G_distill%d' % i, LossValue([(1.0, term)]))
-            terms.append(term)
+                setattr(self, 'loss_G_distill%d' % i, LossValue([(shards, term)]))
+                terms.append((shards, term))
         return terms
 
     def backward_G(self, steps):
@@ -106,10 +115,10 @@ class InceptionDistiller(BaseInceptionDistiller):
         if opt.lambda_distill > 0:
             kas = self.calc_distill_loss()
             sign = -1.0 if opt.distill_G_loss_type == 'ka' else 1.0
-            self.loss_G_distill = LossValue([(sign * opt.lambda_distill, k) for k in kas])
+            self.loss_G_distill = LossValue([(sign * opt.lambda_distill * f, k) for f, k in kas])
             # DataParallel sums the per-shard distillation terms (KA, or the per-device MSE) while every other term is a mean over
             # the gathered batch: with gradient AVERAGING across ranks their seed therefore carries a factor world_size
-            terms += [(sign * opt.lambda_distill * ws, k) for k in kas]
+            terms += [(sign * opt.lambda_distill * ws * f, k) for f, k in kas]
         else:
             self.loss_G_distill = 0
         self.loss_G = self.loss_G_gan + self.loss_G_recon + self.loss_G_distill

@@ -96,6 +96,8 @@ def applicable(block, x):
         kind = cnn.BatchNorm2d
     if kind is cnn.BatchNorm2d and any(m.momentum is None or not m.track_running_stats for m in norms):
         return False
+    if kind is cnn.BatchNorm2d and any(m.virtual_replicas != norms[0].virtual_replicas for m in norms):
+        return False      # one shard count per block (networks.set_virtual_replicas stamps a whole network): otherwise layer by layer
     if kind is cnn.InstanceNorm2d and any(m.track_running_stats for m in norms):
         return False
     if not block.training and (kind is not cnn.InstanceNorm2d or any(m.training for m in norms) or _dropout(block)[0] != 0):
@@ -135,6 +137,12 @@ class _Plan(U.Plan):
         super().__init__(res, dws, block.input_dim, block.input_dim, dev, list(block.parameters()))
         self.C, self.cs = self.Cin, self.csi
 
+    def live_shards(self):
+        """virtual replicas as stamped on the closing norm NOW (networks.set_virtual_replicas may change it between steps).  forward() copies
+        it into self.shards, which every stage reads; the backward pass restores the value ITS forward ran with (the saved tables have that
+        shape), whatever was stamped or run in between."""
+        return 1 if self.instance else int(self.block.pw_bn.virtual_replicas)
+
     wgrad_batch = True      # one stream (the inception distillers' default): the weight-gradient partial sums are reduced by ONE launch
 
     def _merges_dw_dgrad(self):
@@ -173,6 +181,7 @@ def forward(block, x, save=None):
     """The block's forward on the fused path.  `save`: dict that receives what the backward pass needs (None under no_grad)."""
     p = plan_for(block, x)
     p.prepare()
+    p.shards = p.live_shards()
     n, c, h, w = x.shape
     dev = x.device
     pdrop, djs = _dropout(block)
@@ -186,8 +195,8 @@ def forward(block, x, save=None):
     stp = _run(U.finalize_g(p, partp, p.cs, n, h, w, pw.weight, pw.bias, [(0, c, pw)], sync=None, mstride=c))
     # ---- out = x + pw_bn(T)
     y = ops.empty_act(n, c, h, w, dev)
-    G = n if p.instance else 1
-    L.call('cat_affine_res_fwd', ops._p(t), p.cs, ops._p(stp[0][0]), ops._p(stp[0][1]), p.cs if p.instance else 0, ops._p(x), ops.act_cs(x), ops._p(y), p.cs,
+    G = n if p.per_sample else 1
+    L.call('cat_affine_res_fwd', ops._p(t), p.cs, ops._p(stp[0][0]), ops._p(stp[0][1]), p.cs if p.per_sample else 0, ops._p(x), ops.act_cs(x), ops._p(y), p.cs,
            G, (n // G) * h * w, p.cs, L.ACT_NONE, 0.0, ops._stream())
     if save is not None:
         save.update(plan=p, z1=z1, zd=zd, t=t, st1=st1, std=std, stp=stp, drop=(pdrop, djs, ticket))
@@ -201,6 +210,7 @@ class _BlockFn(torch.autograd.Function):
         save = {}
         y = forward(block, x, save)
         ctx.block, ctx.plan = block, save['plan']
+        ctx.shards = ctx.plan.shards
         ctx.has_dw = save['zd'] is not None
         ctx.pdrop, ctx.djs, ticket = save['drop']
         tensors = [x, save['z1'], save['t'], save['st1'][0], save['st1'][1], save['stp'][0], save['stp'][1]]
@@ -219,6 +229,7 @@ class _BlockFn(torch.autograd.Function):
         zd, ssd, mrd = saved[7:10] if ctx.has_dw else (None, None, None)
         dy = ops.conform(dy)
         p.prepare(backward=True)
+        p.shards = ctx.shards
         n, c, h, w = x.shape
         # ---- the closing pw_bn: dT from dy (the skip connection's share of dy is added by the pipeline's last launch)
         pw = block.pw_bn

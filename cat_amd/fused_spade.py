@@ -99,6 +99,8 @@ def applicable(res_ops, dw_ops, x, training):
         norms = [b['bn1']] + ([b['bn2']] if dw else [])
         if any(not isinstance(nm, cnn.BatchNorm2d) or nm.training != training or not nm.track_running_stats or nm.momentum is None for nm in norms):
             return False
+        if training and any(nm.virtual_replicas > 1 for nm in norms):
+            return False      # a BatchNorm2d stamped with virtual replicas takes its statistics per shard of the batch: the per-layer path
         # under a multi-rank reducer the fused stage finalize all-reduces the statistics and uses the clamp(var, eps) formula: that is
         # SynchronizedBatchNorm2d's arithmetic (sync_batchnorm/batchnorm.py:103-140).  A plain nn.BatchNorm2d (norm_G = 'spadebatch3x3') stays
         # per-replica in the reference (local statistics, var + eps): such units take the per-layer path, whose BatchNorm2d is never synced

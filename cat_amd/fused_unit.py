@@ -14,6 +14,9 @@ each a plan property or an argument, never "which caller":
 
     p.reflect         reflect padding (block) instead of 'same' zero padding
     p.instance        per-sample statistics (InstanceNorm) instead of batch statistics; p.affine: the norms have gamma / beta
+    p.shards          virtual replicas of a BatchNorm plan (1: one group over the batch): statistics per torch.chunk(batch, shards) shard;
+                      p.per_sample: the scale / shift tables are one row per sample (InstanceNorm, or shards > 1: the rows of a shard's
+                      samples are equal), the form every apply / staging kernel takes through its `sstride`
     statistics        collected and finalized (train mode), or `folded`: the eval form on cached scale / shift, no statistics, no finalize
     sync              the finalize (and norm backward) to use: local, or with one statistics exchange over ranks per stage (the pipeline is
                       a generator over those exchanges; whoever drives it performs them)
@@ -62,6 +65,11 @@ class Plan:
     what = 'fused unit'
     GAMMA0 = 0.0
     reflect = instance = False
+    shards = 1
+
+    @property
+    def per_sample(self):
+        return self.instance or self.shards > 1
     affine = True
     s1d = None
     wgrad_batch = False
@@ -418,9 +426,20 @@ def finalize_g(p, part, scs, n, h, w, gamma, beta, pairs, *, sync, mstride=None)
     has happened; without `sync` it yields nothing."""
     G = n if p.instance else 1
     mstride = scs if mstride is None else mstride
+    gp, bp = (ops._p(gamma), ops._p(beta)) if p.affine else (None, None)
+    if p.shards > 1 and not p.instance:
+        # virtual replicas: one launch reduces per GROUP of samples (mr: [groups][mstride], what cat_norm_bwd with `shards` reads) and
+        # writes the scale / shift rows per SAMPLE (ss: [n][scs]); running statistics from group 0
+        if sync is not None:
+            raise RuntimeError('fused unit: virtual replicas with a statistics exchange over ranks')
+        per = ops.shard_bounds(n, p.shards)[0][1]
+        ss = torch.empty((2, n, scs), device=part.device, dtype=torch.float32)
+        mr = torch.empty((2, -(-n // per), mstride), device=part.device, dtype=torch.float32)
+        L.call('cat_tnorm_finalize_groups', ops._p(part), scs, per, n, h, w, 8, 16, 1, gp, bp, len(pairs), slices(pairs), p.eps, p.momentum,
+               ops._p(ss[0]), ops._p(ss[1]), ops._p(mr[0]), ops._p(mr[1]), mstride, ops._stream())
+        return ss, mr
     ss = torch.empty((2, G, scs), device=part.device, dtype=torch.float32)
     mr = torch.empty((2, G, mstride), device=part.device, dtype=torch.float32)
-    gp, bp = (ops._p(gamma), ops._p(beta)) if p.affine else (None, None)
     if sync is None:
         L.call('cat_tnorm_finalize', ops._p(part), scs, G, n, h, w, gp, bp, len(pairs), slices(pairs), p.eps, p.momentum, ops._p(ss[0]), ops._p(ss[1]),
                ops._p(mr[0]), ops._p(mr[1]), mstride, ops._stream())
@@ -446,7 +465,7 @@ def materialise(p, z1, ss1, zd, ssd, drop, dw_slices):
     pdrop, djs, ticket = drop
     n, h, w, _ = z1.shape
     dev, npix = z1.device, n * h * w
-    sstride_of = lambda scs: scs if p.instance else 0
+    sstride_of = lambda scs: scs if p.per_sample else 0
     a1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
     rest = dw_slices or any(b['j'] not in djs for b in p.res)      # (res slices whose Dropout is off are written too)
     g = ops.dropout_geom(npix, p.hc1, p.hc1, p.hc1, pdrop, drop_segs(p, djs, 'res'), mode=L.DROP_NORM, rest=int(rest), hw=h * w,
@@ -489,7 +508,7 @@ def forward_g(p, x, *, sync=None, folded=None, drop=None):
     if p.dws:
         zd = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
         partd = part_of(p.hcd)
-        dwm_fwd(p, z1, st1[0][0], st1[0][1], zd, partd, p.reflect, p.instance)
+        dwm_fwd(p, z1, st1[0][0], st1[0][1], zd, partd, p.reflect, p.per_sample)
         if folded is None:
             std = yield from finalize_g(p, partd, p.hcd, n, h, w, p.gammad, p.betad, [(b['od'], b['m'], b['bn2']) for b in p.dws], sync=sync)
         else:
@@ -498,7 +517,7 @@ def forward_g(p, x, *, sync=None, folded=None, drop=None):
     if drop is not None:
         a1, ad = materialise(p, z1, st1[0], zd, std[0] if std is not None else None, drop, dw_slices=False)
     # ---- stage 2: the branch sum, K-concatenated, normalise + activation applied while staging
-    segs = stage2_segs(p, z1, st1[0], zd, std[0] if std is not None else None, p.reflect, p.instance, a1, ad)
+    segs = stage2_segs(p, z1, st1[0], zd, std[0] if std is not None else None, p.reflect, p.per_sample, a1, ad)
     return z1, st1, zd, std, segs
 
 
@@ -531,7 +550,7 @@ def norm_bwd_g(p, n, hw, c, cs, x, dy, gamma, beta, mr, act, slope, dgamma, dbet
         L.call('cat_bn_apply_bwd', ops._p(x), ops._p(dy), ops._p(gamma), ops._p(beta), ops._p(mr[0]), ops._p(mr[1]), ops._p(sums),
                float(m * sync.world_size), ops._p(local), ops._p(dx), ops._p(dgamma), ops._p(dbeta), accumulate, m, c, cs, act, slope, st)
         return dx
-    g = L.NormGeom(n, hw, c, cs, L.NORM_INSTANCE if p.instance else L.NORM_BATCH, p.eps, p.momentum, act, slope)
+    g = L.NormGeom(n, hw, c, cs, L.NORM_INSTANCE if p.instance else L.NORM_BATCH, p.eps, p.momentum, act, slope, 0 if p.instance else p.shards)
     ws = ops.workspace(L.query('cat_norm_ws_bytes', C.byref(g)), x.device)
     L.call('cat_norm_bwd', C.byref(g), ops._p(x), ops._p(dy), ops._p(gamma), ops._p(beta), ops._p(mr[0]), ops._p(mr[1]), ops._p(dx), ops._p(dgamma),
            ops._p(dbeta), accumulate, ops._p(ws), ops._stream())
@@ -644,12 +663,12 @@ def backward_g(p, dt, x, z1, ss1, mr1, zd, ssd, mrd, *, need_dx, skip_grad=None,
 
     # ---- 1. re-materialise the hidden activations (inputs of the second convs / of the depthwise convs); with dropout the forward's
     # masks are re-derived from its ticket: res slices of A1 and all of Ad dropped, the dw slices of A1 (depthwise inputs) not
-    a1, ad = materialise(p, z1, ss1, zd, ssd, drop, dw_slices=True) if drop is not None else (rematerialise(p, z1, ss1, p.instance), None)
+    a1, ad = materialise(p, z1, ss1, zd, ssd, drop, dw_slices=True) if drop is not None else (rematerialise(p, z1, ss1, p.per_sample), None)
     da1 = torch.empty((n, h, w, p.hc1), device=dev, dtype=torch.float32)
     dad = None
     if p.dws:
         if drop is None:
-            ad = rematerialise(p, zd, ssd, p.instance)
+            ad = rematerialise(p, zd, ssd, p.per_sample)
         dad = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
     # ---- 2. / 3. second convs: weight gradients from (hidden activation slice, dT); input gradients into slices of dA1 / dAd
     side.fork()

@@ -60,6 +60,7 @@ class StepHost:
         self.save_dir = os.path.join(getattr(opt, 'log_dir', '.'), 'checkpoints')
         self.image_paths = []
         self.dp = None     # cat_amd.parallel.DataParallelReducer when world_size > 1
+        self.virtual_replicas = 1      # set_virtual_replicas
 
     def seed(self, value):
         """Constant 0-d device tensors used as backward seeds (d total / d term)."""
@@ -67,7 +68,35 @@ class StepHost:
 
     backward_terms = staticmethod(lossvalue.backward_terms)
 
+    def set_virtual_replicas(self, replicas):
+        """Compute, on this one GPU, what `replicas` reference GPUs under nn.DataParallel compute on the same batch (a recipe written for k
+        GPUs: --virtual_replicas k): every training BatchNorm of every network this host owns takes its statistics per
+        torch.chunk(batch, replicas) shard (networks.set_virtual_replicas), and the steps read self.virtual_replicas for their per-replica
+        distillation terms.  Under a DataParallelReducer with W ranks the result is that of W * replicas reference GPUs.  1 = as built.
+        The SPADE family's SynchronizedBatchNorm layers are truly synchronised: their statistics stay whole-batch, but with more than one
+        replica the reference takes its multi-replica arm (clamp(var, eps), sync_batchnorm/batchnorm.py:103-140).  A host that owns such
+        layers and has no multi-rank reducer installs ops.ReplicaSync -- the same kernels as under a reducer, the exchange an identity --
+        while replicas > 1, and removes it again at 1 (ops.set_bn_sync is process-wide, as under enable_data_parallel)."""
+        from . import nn as cnn
+        from . import ops
+        replicas = int(replicas)
+        if replicas < 1:
+            raise ValueError('virtual_replicas must be >= 1, got %d' % replicas)
+        nets = [net for v in list(vars(self).values()) for net in (v if isinstance(v, (list, tuple)) else [v]) if isinstance(net, torch.nn.Module)]
+        self.virtual_replicas = replicas
+        for net in nets:
+            networks.set_virtual_replicas(net, replicas)
+            if hasattr(net, 'calc_distill_loss'):      # the SPADE family keeps its loss terms on the module that owns the networks
+                net.virtual_replicas = replicas
+        if any(cnn._exchanges(m) for net in nets for m in net.modules()):
+            cur = ops.bn_sync()
+            if replicas > 1 and cur is None:
+                ops.set_bn_sync(ops.ReplicaSync())
+            elif replicas == 1 and isinstance(cur, ops.ReplicaSync):
+                ops.set_bn_sync(None)
+
     def setup(self, opt, verbose=True):
+        self.set_virtual_replicas(getattr(opt, 'virtual_replicas', 1))
         if self.isTrain:
             self.schedulers = [networks.get_scheduler(optimizer, opt) for optimizer in self.optimizers]
         self.load_networks(verbose)

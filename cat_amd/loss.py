@@ -84,6 +84,11 @@ def KA(X, Y):
     return ops.ka(X, Y)
 
 
+def KA_sharded(X, Y, shards, mean=False):
+    """sum (or mean) over the torch.chunk(batch, shards) shards of KA(X_g, Y_g): the term of `shards` data-parallel replicas"""
+    return ops.ka_sharded(X, Y, shards, mean)
+
+
 class VGG19(nn.Module):
     """torchvision vgg19().features[0:30] cut into the reference's five slices (models/modules/loss.py:151-186), same
     `slice{k}.{idx}.weight` state_dict keys, every layer a gfx950 kernel (3x3 conv + fused ReLU, 2x2 max-pool).

@@ -26,6 +26,7 @@ class CycleGANModel(BaseModel):
         ('--lambda_identity', dict(type=float, default=0.5)),
         ('--real_stat_A_path', dict(type=str, required=False, default=None)),
         ('--real_stat_B_path', dict(type=str, required=False, default=None)),
+        ('--virtual_replicas', dict(type=int, default=1)),      # the arithmetic of that many reference GPUs on this one (host.set_virtual_replicas)
     ]
 
     @staticmethod

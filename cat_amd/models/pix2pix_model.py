@@ -20,6 +20,7 @@ class Pix2PixModel(BaseModel):
         ('--lambda_comp_cost', dict(type=float, default=0)),
         ('--comp_cost', dict(type=str, default='l1', choices=['l1'])),
         ('--l1_renorm', dict(action='store_true')),
+        ('--virtual_replicas', dict(type=int, default=1)),      # the arithmetic of that many reference GPUs on this one (host.set_virtual_replicas)
     ]
 
     @staticmethod

@@ -29,6 +29,7 @@ class SPADEModel(SPADEStep, BaseModel):
         ('--no_TTUR', dict(action='store_true', help='Use TTUR training scheme')),
         ('--no_fid', dict(action='store_true', help='No FID evaluation during training')),
         ('--no_mIoU', dict(action='store_true', help='No mIoU evaluation during training')),
+        ('--virtual_replicas', dict(type=int, default=1)),      # the arithmetic of that many reference GPUs on this one (host.set_virtual_replicas)
     ]
 
     @staticmethod

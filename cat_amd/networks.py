@@ -27,6 +27,23 @@ def get_norm_layer(norm_type='instance', affine=True, track_running_stats=True):
     raise NotImplementedError('normalization layer [%s] is not found' % norm_type)
 
 
+def set_virtual_replicas(net, replicas):
+    """Stamp the statistic-group count of `replicas` virtual data-parallel replicas on every BatchNorm of `net` that takes per-replica
+    statistics under the reference's nn.DataParallel (models/networks.py:157-161): cnn.BatchNorm2d and the replica-local
+    SynchronizedBatchNorm2d.  In training mode such a layer then normalises every torch.chunk(batch, replicas) shard with the shard's own
+    statistics and updates its running statistics from shard 0, as replica 0 does.  InstanceNorm2d, eval-mode layers and a
+    SynchronizedBatchNorm2d that exchanges its statistics (the SPADE family: truly synchronised) are left alone.  -> the layers stamped."""
+    replicas = int(replicas)
+    if replicas < 1:
+        raise ValueError('virtual_replicas must be >= 1, got %d' % replicas)
+    n = 0
+    for m in net.modules():
+        if isinstance(m, cnn.BatchNorm2d) and not cnn._exchanges(m):
+            m.virtual_replicas = replicas
+            n += 1
+    return n
+
+
 def get_scheduler(optimizer, opt):
     """reference networks.py:67-103 ('linear' is what every distillation script uses)."""
     if opt.lr_policy == 'linear':

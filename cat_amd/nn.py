@@ -252,6 +252,10 @@ class ConvTranspose2d(nn.ConvTranspose2d):
 
 
 class _NormMixin:
+    # virtual replicas (networks.set_virtual_replicas stamps it on BatchNorm layers): S > 1 = batch statistics per torch.chunk(batch, S) shard,
+    # as S nn.DataParallel replicas take them, running statistics from shard 0.  Never read by InstanceNorm2d or in eval mode.
+    virtual_replicas = 1
+
     def _run(self, x, mode, use_batch_stats, fuse_act, count_batches=True):
         if isinstance(x, Padded):
             raise NotImplementedError('padding in front of a norm layer')
@@ -266,7 +270,8 @@ class _NormMixin:
                     # _InstanceNorm.forward never touches num_batches_tracked)
                     nbt = self.num_batches_tracked
             return ops.NormActFn.apply(x, self.weight, self.bias, rm, rv, mode, float(self.eps),
-                                       float(self.momentum if self.momentum is not None else 0.0), act, slope, nbt)
+                                       float(self.momentum if self.momentum is not None else 0.0), act, slope, nbt, None,
+                                       int(self.virtual_replicas) if mode == L.NORM_BATCH else 1)
         scale, shift = ops.bn_fold(self.weight, self.bias, self.running_mean, self.running_var, float(self.eps))
         return ops.affine_act(x, scale, shift, act, slope)
 
@@ -381,6 +386,8 @@ def _edge_conv(m, nxt, x):
     measured 175 + 105 us against 223 + 108 us for the im2col kernels + 30 us of separate statistics passes, profiles/r04_qconv_layers.txt)"""
     if not _QCONV or not isinstance(m, Conv2d) or not isinstance(nxt, _NORMS) or _exchanges(nxt):
         return False
+    if isinstance(nxt, BatchNorm2d) and nxt.virtual_replicas > 1:
+        return False      # sharded statistics: the tile table is finalized per batch or per sample only -- layer by layer (cat_norm_t.shards)
     if _hooked(m):      # the edge path never calls m.forward: a forward (pre-)hook registered on the conv would silently stop firing
         return False
     if m.groups != 1 or 'weight_orig' in m._parameters or m.dilation != (1, 1) or m.padding_mode != 'zeros' or m.stride[0] != m.stride[1]:

@@ -696,16 +696,21 @@ class NormActFn(torch.autograd.Function):
     """InstanceNorm2d / BatchNorm2d with batch statistics, fused with the activation behind it."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, mode, eps, momentum, act, slope, num_batches=None, tiles=None):
+    def forward(ctx, x, gamma, beta, running_mean, running_var, mode, eps, momentum, act, slope, num_batches=None, tiles=None, shards=1):
         """tiles (optional): the producing conv's per-tile statistics {'table', 'plan', 'scs', 'lat': (h, w), 'ncls'} (cat_qconv_fwd `stats`):
-        the statistics pass is skipped -- cat_tnorm_finalize2 + one apply pass."""
+        the statistics pass is skipped -- cat_tnorm_finalize2 + one apply pass.
+        shards > 1 (batch norm only): the statistics of that many data-parallel replicas -- one group per torch.chunk shard, running
+        statistics from shard 0 -- in the same three launches (cat_norm_t.shards)."""
         _require_cuda(x)
         x = conform(x)
         n, c, h, w = x.shape
         cs = act_cs(x)
         y = empty_act(n, c, h, w, x.device, cs)
-        g = NormGeom(n, h * w, c, cs, mode, eps, momentum, act, slope)
-        groups = n if mode == L.NORM_INSTANCE else 1
+        shards = int(shards) if mode == L.NORM_BATCH and int(shards) > 1 else 0
+        if shards and tiles is not None:
+            raise RuntimeError('norm: a conv\'s tile statistics cannot feed a sharded batch norm (the caller declines that path)')
+        g = NormGeom(n, h * w, c, cs, mode, eps, momentum, act, slope, shards)
+        groups = n if mode == L.NORM_INSTANCE else norm_groups(n, shards)
         mean = torch.empty((groups, c), device=x.device, dtype=torch.float32)
         rstd = torch.empty((groups, c), device=x.device, dtype=torch.float32)
         if tiles is not None:
@@ -717,7 +722,7 @@ class NormActFn(torch.autograd.Function):
             optim.note_stats_written(running_mean, running_var)
             L.call('cat_norm_fwd', C.byref(g), _p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), _p(running_mean), _p(running_var),
                    _p(num_batches), _p(ws), _stream())
-        ctx.geom = (n, h * w, c, cs, mode, eps, momentum, act, slope)
+        ctx.geom = (n, h * w, c, cs, mode, eps, momentum, act, slope, shards)
         ctx.gamma, ctx.beta = gamma, beta
         ctx.save_for_backward(x, mean, rstd, gamma, beta)
         return y
@@ -740,7 +745,7 @@ class NormActFn(torch.autograd.Function):
         dbeta = torch.empty_like(beta) if need_b and sink is None else None
         (pg, pb), acc = sink or ((dgamma, dbeta), 0)
         L.call('cat_norm_bwd', C.byref(g), _p(x), _p(dy), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx), _p(pg), _p(pb), acc, _p(ws), st)
-        return dx, optim.deliver(ctx.gamma, dgamma), optim.deliver(ctx.beta, dbeta), None, None, None, None, None, None, None, None, None
+        return dx, optim.deliver(ctx.gamma, dgamma), optim.deliver(ctx.beta, dbeta), None, None, None, None, None, None, None, None, None, None
 
 
 def norm_from_tiles(tiles, n, c, groups, gamma, beta, running_mean, running_var, num_batches, eps, momentum, mean=None, rstd=None):
@@ -973,10 +978,13 @@ class Concat2Fn(torch.autograd.Function):
 
 # ---------------------------------------------------------------------------------------------- losses
 class KAFn(torch.autograd.Function):
-    """Kernel alignment between two activation stacks (utils/common.py:38-46); gradient flows to X only."""
+    """Kernel alignment between two activation stacks (utils/common.py:38-46); gradient flows to X only.  shards > 1: the term as that many
+    data-parallel replicas compute it -- the KA of every torch.chunk(batch, shards) shard, summed (or averaged: mean) -- in the same number
+    of launches; the 64-sample limit then holds per shard."""
 
     @staticmethod
-    def forward(ctx, x, y):
+    def forward(ctx, x, y, shards=0, mean=False):
+        """shards 0: the plain entry points (ops.ka); >= 1: the sharded ones (ops.ka_sharded; 1 shard computes the same bits)"""
         _require_cuda(x)
         x, y = conform(x), conform(y)
         n = x.shape[0]
@@ -984,11 +992,18 @@ class KAFn(torch.autograd.Function):
             raise AssertionError(f'X_ and Y_ must have the same shape on dim 0, but got {n} for X_ and {y.shape[0]} for Y_.')
         dx_len = x.shape[2] * x.shape[3] * act_cs(x)
         dy_len = y.shape[2] * y.shape[3] * act_cs(y)
-        ws = torch.empty(L.query('cat_ka_ws_bytes', n) // 4, device=x.device, dtype=torch.float32)
         out = torch.empty((), device=x.device, dtype=torch.float32)
-        L.call('cat_ka_fwd', _p(x), dx_len, _p(y), dy_len, n, _p(out), _p(ws), _stream())
+        shards = int(shards)
+        if shards < 0:
+            raise ValueError(f'ka: shards must be >= 1, got {shards}')
+        if shards == 0:
+            ws = torch.empty(L.query('cat_ka_ws_bytes', n) // 4, device=x.device, dtype=torch.float32)
+            L.call('cat_ka_fwd', _p(x), dx_len, _p(y), dy_len, n, _p(out), _p(ws), _stream())
+        else:
+            ws = torch.empty(L.query('cat_ka_sharded_ws_bytes', n, shards) // 4, device=x.device, dtype=torch.float32)
+            L.call('cat_ka_sharded_fwd', _p(x), dx_len, _p(y), dy_len, n, shards, int(bool(mean)), _p(out), _p(ws), _stream())
         ctx.save_for_backward(x, ws)
-        ctx.dx_len = dx_len
+        ctx.dx_len, ctx.shards, ctx.mean = dx_len, shards, int(bool(mean))
         return out
 
     @staticmethod
@@ -997,8 +1012,11 @@ class KAFn(torch.autograd.Function):
         n, c, h, w = x.shape
         dx = empty_act(n, c, h, w, x.device, act_cs(x))
         gout = gout.contiguous()
-        L.call('cat_ka_bwd', _p(x), ctx.dx_len, n, _p(gout), _p(ws), _p(dx), _stream())
-        return dx, None
+        if ctx.shards == 0:
+            L.call('cat_ka_bwd', _p(x), ctx.dx_len, n, _p(gout), _p(ws), _p(dx), _stream())
+        else:
+            L.call('cat_ka_sharded_bwd', _p(x), ctx.dx_len, n, ctx.shards, ctx.mean, _p(gout), _p(ws), _p(dx), _stream())
+        return dx, None, None, None
 
 
 class LossFn(torch.autograd.Function):
@@ -1091,6 +1109,29 @@ def ka(x, y):
     return KAFn.apply(x, y)
 
 
+def ka_sharded(x, y, shards, mean=False):
+    """sum (mean=False) or mean over the torch.chunk(batch, shards) shards of ka(x_g, y_g): the distillation term of `shards` data-parallel
+    replicas (inception family: the sum; SPADE: the mean).  shards = 1 is ka(x, y), bit for bit."""
+    if int(shards) < 1:
+        raise ValueError(f'ka_sharded: shards must be >= 1, got {shards}')
+    return KAFn.apply(x, y, int(shards), mean)
+
+
+def shard_bounds(n, shards):
+    """torch.chunk(batch of n, shards, 0) as (begin, end) sample ranges: ceil(n / shards) samples per shard, the last may be short, and
+    there may be fewer than `shards` of them.  The one rule every virtual-replica kernel follows (csrc/norm.hip plan, ka_shards)."""
+    n, shards = int(n), int(shards)
+    if n < 1 or shards < 1:
+        raise ValueError(f'shard_bounds: n={n}, shards={shards}')
+    per = -(-n // shards)
+    return [(b, min(n, b + per)) for b in range(0, n, per)]
+
+
+def norm_groups(n, shards):
+    """statistic groups of a train-mode BatchNorm over a batch of n under `shards` virtual replicas"""
+    return len(shard_bounds(n, shards)) if shards > 1 else 1
+
+
 def fill_(t, value):
     """In-place fill of a dense fp32 buffer with the library's kernel."""
     L.call('cat_fill', _p(t), t.numel(), float(value), _stream())
@@ -1105,7 +1146,21 @@ def set_bn_sync(sync):
     """`sync`: object with `.world_size` and `.all_reduce_sum_(tensor)` (cat_amd.parallel.DataParallelReducer) or None.  While set,
     training-mode SynchronizedBatchNorm2d layers all-reduce their [sum x | sum x^2] (and backward sums) over the ranks."""
     global _BN_SYNC
-    _BN_SYNC = sync if (sync is not None and sync.world_size > 1) else None
+    _BN_SYNC = sync if (sync is not None and (sync.world_size > 1 or getattr(sync, 'virtual', False))) else None
+
+
+class ReplicaSync:
+    """The statistics exchange of several data-parallel replicas that all live in THIS process (virtual replicas): the local sums already
+    run over every replica's samples, so the all-reduce is the identity -- but the layers take the reference's multi-replica arm, whose
+    arithmetic differs from F.batch_norm (clamp(var, eps), sync_batchnorm/batchnorm.py:103-140).  world_size counts ranks: 1."""
+    world_size = 1
+    virtual = True
+
+    def all_reduce_sum_(self, t):
+        return t
+
+    def all_reduce_sum_many_(self, tensors):
+        return tensors
 
 
 def bn_sync():

@@ -63,6 +63,8 @@ def applicable(module, x):
                 return False
             if norm.training and norm.track_running_stats and norm.momentum is None:
                 return False
+            if norm.virtual_replicas > 1:      # statistics per shard of the batch: layer by layer (the kernels' tables are per batch or per sample)
+                return False
         else:
             return False
         return norm.num_features == 2 * ndf

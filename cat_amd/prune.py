@@ -468,6 +468,7 @@ def shrink(model, opt):
     """reference utils/common.py:872-878."""
     target_flops = getattr(opt, 'target_flops', 0.0)
     assert target_flops > 0
-    if 'spade' in getattr(opt, 'distiller', 'inception'):
-        return shrink_spade_model(model, target_flops, opt)
-    return shrink_model(model, target_flops, opt)
+    out = shrink_spade_model(model, target_flops, opt) if 'spade' in getattr(opt, 'distiller', 'inception') else shrink_model(model, target_flops, opt)
+    if getattr(model, 'virtual_replicas', 1) != 1:      # the rebuilt student's norm layers are new objects: stamp them like the ones they replace
+        model.set_virtual_replicas(model.virtual_replicas)
+    return out

@@ -182,16 +182,24 @@ class SPADEDistillerModules(SPADEModules):
         raise NotImplementedError('The distiller is only for training!!!')
 
     # -- losses -------------------------------------------------------------------------------------------------------------
+    virtual_replicas = 1      # host.StepHost.set_virtual_replicas
+
     def calc_distill_loss(self, Tacts, Sacts):
-        """spade_distiller_modules.py:17-31."""
+        """spade_distiller_modules.py:17-31.  With virtual replicas every replica returns its own term and backward_G takes the MEAN over
+        replicas (spade_model.py:191): one sharded-KA launch sequence; the MSE's mean of equal shards' means is the whole-batch mean."""
         kind = self.opt.distill_G_loss_type
         if kind not in ('ka', 'mse'):
             raise NotImplementedError(kind)
+        S = int(self.virtual_replicas)
         losses = {}
         for i, netA in enumerate(self.netAs):
             layer = self.mapping_layers[i]
             if kind == 'mse':
+                if S > 1 and len({e - b for b, e in ops.shard_bounds(Sacts[layer].shape[0], S)}) != 1:
+                    raise NotImplementedError('--distill_G_loss_type mse with virtual replicas needs a batch that splits into equal shards')
                 losses['G_distill%d' % i] = LossValue([(1.0, self.criterionMSE(netA(Sacts[layer]), Tacts[layer]))])
+            elif S > 1:
+                losses['G_distill%d' % i] = LossValue([(-1.0, closs.KA_sharded(Sacts[layer], Tacts[layer], S, mean=True))])
             else:
                 losses['G_distill%d' % i] = LossValue([(-1.0, closs.KA(Sacts[layer], Tacts[layer]))])
         total = LossValue([(w * self.opt.lambda_distill, t) for lv in losses.values() for w, t in lv.terms])

@@ -147,6 +147,9 @@ typedef struct {
   float eps, momentum;
   int act;           /* CAT_ACT_* applied after the affine */
   float slope;
+  int shards;        /* CAT_NORM_BATCH only: 0 / 1 = one group over the batch; S > 1 = the statistics of S data-parallel replicas on one device:
+                      * groups of ceil(N / S) consecutive samples (torch.chunk; the last may be short, there may be fewer than S), save_mean /
+                      * save_rstd [groups][C], dgamma / dbeta summed over the groups, running statistics and num_batches_tracked from group 0 only */
 } cat_norm_t;
 size_t cat_norm_ws_bytes(const cat_norm_t* g);
 int cat_norm_fwd(const cat_norm_t* g, const float* x, const float* gamma, const float* beta, float* y,
@@ -185,6 +188,15 @@ size_t cat_ka_ws_bytes(int N);
 int cat_ka_fwd(const float* X, int64_t Dx, const float* Y, int64_t Dy, int N, float* out, void* ws,
                cat_stream_t stream);
 int cat_ka_bwd(const float* X, int64_t Dx, int N, const float* gout, const void* ws, float* dX, cat_stream_t stream);
+/* The distillation term as S data-parallel replicas compute it (distillers/inception_distiller.py:136-148): the batch is cut like
+ * torch.chunk(batch, S, 0) -- shards of P = ceil(N / S) consecutive rows, the last may be short, G = ceil(N / P) <= S of them -- and
+ * out[0] = the SUM (mean = 0) or the MEAN (mean = 1) over the shards of KA(X_g, Y_g).  P <= 64; N is not limited.  The launch count does
+ * not depend on S (the shard is a grid dimension); S = 1 is cat_ka_fwd / cat_ka_bwd bit for bit.  ws >= cat_ka_sharded_ws_bytes(N, S). */
+size_t cat_ka_sharded_ws_bytes(int N, int S);
+int cat_ka_sharded_fwd(const float* X, int64_t Dx, const float* Y, int64_t Dy, int N, int S, int mean, float* out, void* ws,
+                       cat_stream_t stream);
+int cat_ka_sharded_bwd(const float* X, int64_t Dx, int N, int S, int mean, const float* gout, const void* ws, float* dX,
+                       cat_stream_t stream);
 
 /* Scalar losses with their gradients (models/modules/loss.py:52-99, nn.L1Loss / nn.MSELoss):
  *   kind 0: mean |a-b|      (L1, b tensor)          kind 1: mean (a-t)^2  (lsgan; t scalar target)
@@ -647,6 +659,13 @@ int cat_qconv_fwd(const cat_qconv_t* g, const float* pack, const float* bias, fl
 int cat_tnorm_finalize2(const float* part, int scs, int G, int N, int Ho, int Wo, int th, int tw, int ncls, const float* gamma,
                         const float* beta, int nslices, const cat_nslice_t* slices, float eps, float momentum, float* scale, float* shift,
                         float* mean, float* rstd, int mstride, cat_stream_t stream);
+/* The case between G = 1 and G = N: train-mode BatchNorm over groups of P consecutive samples (the last may be short), i.e. the statistics of
+ * ceil(N / P) data-parallel replicas on one device.  mean / rstd: [groups][mstride], as cat_norm_bwd with `shards` reads them; scale / shift:
+ * one row per SAMPLE, [N][scs] (sstride = scs at the consumers, the form they take for InstanceNorm); the running statistics and
+ * num_batches of the slices are updated from group 0 only. */
+int cat_tnorm_finalize_groups(const float* part, int scs, int P, int N, int Ho, int Wo, int th, int tw, int ncls, const float* gamma,
+                              const float* beta, int nslices, const cat_nslice_t* slices, float eps, float momentum, float* scale,
+                              float* shift, float* mean, float* rstd, int mstride, cat_stream_t stream);
 
 /* Dropout (dropout.hip).  Replaces the nn.Dropout(dropout_rate) of every InvertedResidualChannels branch, models/modules/inception_modules.py:144
  * (res branch, after the first ConvBNReLU) and :174 (dw branch, after the depthwise ConvBNReLU).  Masks come from Philox4x32-10; element
