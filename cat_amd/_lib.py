@@ -62,6 +62,14 @@ class KSum(C.Structure):
     _fields_ = [(n, c_i) for n in ('N', 'H', 'W', 'Cout', 'ycs', 'ycw', 'rcs', 'act')] + [('slope', c_f), ('nseg', c_i), ('seg', KSeg * KSUM_MAXSEG)]
 
 
+class KNormSeg(C.Structure):
+    _fields_ = [('scale', c_p), ('shift', c_p), ('sstride', c_i), ('act', c_i), ('slope', c_f)]
+
+
+class KSumNorm(C.Structure):
+    _fields_ = [('stats', c_p), ('scs', c_i), ('seg', KNormSeg * KSUM_MAXSEG)]
+
+
 QCONV_MAXSEG = 8
 
 
@@ -200,6 +208,8 @@ SIGNATURES = {
     'cat_tconv_fwd': (c_i, [_TG, c_p, c_p, c_p, c_p]),
     'cat_conv2d_ksum_supported': (c_i, [C.POINTER(KSum)]),
     'cat_conv2d_ksum_fwd': (c_i, [C.POINTER(KSum), c_p, c_p, c_p, c_p]),
+    'cat_conv2d_ksum_norm_supported': (c_i, [C.POINTER(KSum), C.POINTER(KSumNorm)]),
+    'cat_conv2d_ksum_norm_fwd': (c_i, [C.POINTER(KSum), C.POINTER(KSumNorm), c_p, c_p, c_p, c_p]),
     'cat_tstage1_supported': (c_i, [c_i, c_i, c_i]),
     'cat_tstage1_fwd': (c_i, [C.POINTER(Stage1Geom), c_p, c_p, c_p, c_p, c_p, c_p]),
     'cat_tstage1_dgrad_supported': (c_i, [c_i, c_i, c_i]),

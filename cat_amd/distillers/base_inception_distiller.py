@@ -6,6 +6,7 @@ import itertools
 
 import torch
 
+from .. import frozen_in
 from .. import host
 from .. import loss as closs
 from .. import networks, ops
@@ -65,6 +66,8 @@ class BaseInceptionDistiller(host.StepHost):
         self.netD = networks.define_D(d_in, opt.ndf, opt.netD, opt.n_layers_D, opt.norm, opt.init_type, opt.init_gain, dev, opt=opt)
 
         self.netG_teacher.eval()
+        # an InstanceNorm teacher (CycleGAN configs) folds nothing: its eval-mode blocks take the forward-only fused pipeline (frozen_in)
+        frozen_in.own_network(self.netG_teacher)
         self.criterionGAN = closs.GANLoss(opt.gan_mode)
         self.criterionRecon = closs.recon_criterion(opt.recon_loss_type)
 

@@ -18,7 +18,8 @@ collapses algebraically -- same values, different evaluation order -- into
 
 instead of 12 convs + 3 activations + add_n(6) + affine + add_n(2): the 42->256 1x1 layers were epilogue-bound (K = 44: 27 TFLOP/s),
 and 10 of 18 full-size tensor passes disappear.  One-time weight folding is cached per block (invalidated when a tensor changes).
-InstanceNorm teachers (CycleGAN configs) cannot be folded and take the general path."""
+InstanceNorm teachers (CycleGAN configs) cannot be folded: the blocks a distiller owns take the forward-only fused pipeline of
+cat_amd/frozen_in.py, every other eval-mode InstanceNorm block the general path."""
 import ctypes as C
 
 import torch

@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 from . import frozen
+from . import frozen_in
 from . import fused_block
 from . import nn as cnn
 from . import ops
@@ -154,6 +155,8 @@ class InvertedResidualChannels(nn.Module):
             return x
         if frozen.applicable(self, x):      # eval + no_grad + BatchNorm: the frozen teacher's algebraically fused block
             return frozen.block_forward(self, x)
+        if frozen_in.applicable(self, x):       # eval + no_grad + InstanceNorm, owned by a distiller: the forward-only fused pipeline, wide tail
+            return frozen_in.block_forward(self, x)
         if fused_block.applicable(self, x):     # train-mode norms: 9 launches per block, norms folded into producers / consumers
             return fused_block.apply(self, x)
         # dropout: ONE draw per block forward, before any side-stream fork; Dropout module j (res branches first, then dw branches) masks

@@ -476,6 +476,32 @@ typedef struct {
 } cat_ksum_t;
 int cat_conv2d_ksum_supported(const cat_ksum_t* g);
 int cat_conv2d_ksum_fwd(const cat_ksum_t* g, const float* bias, const float* res, float* y, cat_stream_t stream);
+/* The same tile with a staging function per segment and statistics for a norm layer behind it -- the branch sum of a WIDE block whose norms
+ * keep no running statistics (the eval-mode InstanceNorm teacher of the CycleGAN configs, cat_amd/frozen_in.py):
+ *   y[m][co] = act(bias[co] + sum_s sum_taps sum_c f_s(src_s[pixel(m, tap)][c]) * w_s[co][tap][c]) + res[m][co]
+ *   f_s(v)   = act_s(v * scale_s[n(m)][c] + shift_s[n(m)][c])          (scale_s NULL: f_s(v) = v, act_s is not applied)
+ *   stats[(tile*2 + 0)*scs + co] = sum of bias + sum over the tile's 128 pixels, [(tile*2 + 1)*scs + co] = sum of squared deviations from the
+ *   tile mean; tile = m / 128.  Deterministic (no atomics); channels [Cout, max(ycw, Cout)) get 0 / 0.
+ * Domain (cat_conv2d_ksum_norm_supported; outside it the caller launches cat_tconv_fwd): every 128-pixel row tile lies inside one sample and
+ * is a th x tw lattice tile of cat_tnorm_finalize2 -- 128 % W == 0 and H % (128 / W) == 0 (th = 128 / W, tw = W), or W % 128 == 0 (th = 1,
+ * tw = 128); a normalised segment with ks > 1 has reflect padding (mirrored pixels commute with f_s, the zero padding does not: f_s(0) != 0);
+ * act_s is CAT_ACT_NONE / RELU / LRELU with a slope in [0, 1] (applied as max(v, slope * v)); with `stats` the epilogue activation is CAT_ACT_NONE and there is no residual; the normalised
+ * segments have at most 1024 channels together.  Padding channels of a normalised segment (cat_ksum_seg_t c4 > cin) must read as 0 after
+ * f_s, as cat_tseg_t states it: scale = shift = 0 there. */
+typedef struct {
+  const float* scale;  /* [c4] per-channel staging affine of the segment, NULL = the segment is read as it is */
+  const float* shift;
+  int sstride;         /* floats between per-image rows of scale / shift; 0 = one row for the batch */
+  int act;             /* CAT_ACT_* applied after the affine */
+  float slope;
+} cat_ksum_nseg_t;
+typedef struct {
+  float* stats;        /* optional per-tile statistics table, pointing at this launch's first column */
+  int scs;             /* floats per statistics row (>= max(ycw, Cout)) */
+  cat_ksum_nseg_t seg[CAT_KSUM_MAXSEG];
+} cat_ksum_norm_t;
+int cat_conv2d_ksum_norm_supported(const cat_ksum_t* g, const cat_ksum_norm_t* nm);
+int cat_conv2d_ksum_norm_fwd(const cat_ksum_t* g, const cat_ksum_norm_t* nm, const float* bias, const float* res, float* y, cat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Train-mode norm layers of an InvertedResidualChannels block without their own passes (csrc/block_norm.hip): the producing
