@@ -215,6 +215,8 @@ SIGNATURES = {
     'cat_tstage1_dgrad_supported': (c_i, [c_i, c_i, c_i]),
     'cat_tstage1w_supported': (c_i, [c_i, c_i, c_i]),
     'cat_tstage1w_fwd': (c_i, [C.POINTER(Stage1WGeom), c_p, c_p, c_p, c_p, c_p]),
+    'cat_tstage1ws_supported': (c_i, [c_i, c_i, c_i]),
+    'cat_tstage1ws_fwd': (c_i, [C.POINTER(Stage1Geom), c_p, c_p, c_p, c_p, c_p, c_p]),
     'cat_tstage1_dgrad': (c_i, [C.POINTER(Stage1Geom), c_p, c_p, c_p, c_p, c_p]),
     'cat_tnorm_finalize': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_p]),
     'cat_tnorm_finalize2': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_p]),

@@ -24,12 +24,13 @@
 // [lane][4]: one coalesced 1 KB global_load_dwordx4 per wave, no address arithmetic on the vector ALU, which on gfx950 shares
 // its issue slots with the fp32 MFMA).  Filters of trainable layers are re-packed once per optimizer step.
 #include "common.h"
+#include "conv_pk_tile.h"
 #include <stdio.h>
 #include <stdlib.h>
 
 namespace cat_pk {
 
-constexpr int TH = 8, PITCH = 20, TABN = 128;
+// TH, PITCH, TABN, bload, mma_groups, wload, wmma: conv_pk_tile.h
 
 __device__ __attribute__((aligned(16))) float g_zero[4] = {0.f, 0.f, 0.f, 0.f};
 
@@ -41,66 +42,6 @@ struct Launch {
                            // (L1 hits), 2 every A fragment reads LDS offset 0, 4 staging loads hit one cached line, 8 no staging / barrier after
                            // the first chunk.  The production kernels read `abl`, a compile-time 0
 };
-
-__device__ __forceinline__ f4 bload(const __amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff_) {
-  const auto r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff_, 0);
-  static_assert(sizeof(r) == sizeof(f4), "buffer load width");
-  return __builtin_bit_cast(f4, r);
-}
-
-// MFMA stream of one staged chunk: ngr groups of 4 (tap, quad) pairs, MT x NT accumulator tiles.  Two operand register sets in
-// ping-pong (no copies); the operands of group g+1 and the A offset of group g+2 are requested BEFORE the 4*MT*NT MFMAs of group g are
-// issued, so no load is waited for in the group that issued it.  tab = this lane quarter's A-offset table, so = byte offset of the
-// chunk's first group in the packed filter stream, gbytes = bytes per group.
-template <int MT, int NT>
-__device__ __forceinline__ void mma_groups(f4 (&acc)[MT][NT], const float* tile, const int* tab, const int (&abase)[MT],
-                                           const __amdgpu_buffer_rsrc_t rsrc, const unsigned (&jb)[NT], unsigned so, unsigned gbytes, int ngr) {
-  const int last = ngr - 1;
-  f4 a0[MT], a1[MT], b0[NT], b1[NT];
-  int off = tab[0];
-  int offn = tab[4 * min(1, last)];
-#pragma unroll
-  for (int i = 0; i < MT; ++i) a0[i] = *reinterpret_cast<const f4*>(tile + abase[i] + off);
-#pragma unroll
-  for (int j = 0; j < NT; ++j) b0[j] = bload(rsrc, jb[j], so);
-  int gi = 0;
-  while (true) {
-    {
-      const int g1 = min(gi + 1, last), g2 = min(gi + 2, last);
-#pragma unroll
-      for (int i = 0; i < MT; ++i) a1[i] = *reinterpret_cast<const f4*>(tile + abase[i] + offn);
-#pragma unroll
-      for (int j = 0; j < NT; ++j) b1[j] = bload(rsrc, jb[j], so + (unsigned)g1 * gbytes);
-      offn = tab[4 * g2];
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int tq = 0; tq < 4; ++tq)
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i][tq], b0[j][tq], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (++gi >= ngr) break;
-    {
-      const int g1 = min(gi + 1, last), g2 = min(gi + 2, last);
-#pragma unroll
-      for (int i = 0; i < MT; ++i) a0[i] = *reinterpret_cast<const f4*>(tile + abase[i] + offn);
-#pragma unroll
-      for (int j = 0; j < NT; ++j) b0[j] = bload(rsrc, jb[j], so + (unsigned)g1 * gbytes);
-      offn = tab[4 * g2];
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int tq = 0; tq < 4; ++tq)
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i][tq], b1[j][tq], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (++gi >= ngr) break;
-  }
-}
 
 template <int NT, int TW>
 __global__ __launch_bounds__(256) void tconv_kernel(const cat_tconv_t g, const float* __restrict__ pack, const float* __restrict__ bias,
@@ -614,163 +555,9 @@ __device__ __forceinline__ void s1w_store(const f4 (&acc)[2][NT], const S1WArgs&
   }
 }
 
-template <int NT>
-__device__ __forceinline__ void wload(f4 (&b)[3], const __amdgpu_buffer_rsrc_t rsrc, const unsigned (&jb)[3], unsigned so) {
-#pragma unroll
-  for (int j = 0; j < NT; ++j) b[j] = bload(rsrc, jb[j], so);
-}
-
-template <int MT, int NT>
-__device__ __forceinline__ void wmma(f4 (&acc)[MT][3], const f4 (&a)[MT], const f4 (&b)[3]) {
-#pragma unroll
-  for (int tq = 0; tq < 4; ++tq)
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][tq], b[j][tq], acc[i][j], 0, 0, 0);
-}
-
 template <int N5, int N3, int N1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void tstage1w_kernel(const S1WArgs p) {
-  constexpr int MT = 2, TW = 16, MAXIT = ((TH + 4) * (TW + 4) * 4 + 255) / 256;
-  constexpr int P1 = (N1 + 2) / 3, R1 = N1 - 3 * (P1 - 1);      // passes over the 1 x 1 slot, tiles of the last one (1..3)
-  static_assert(N1 >= 1 && N1 <= 12 && N5 >= 1 && N5 <= 3 && N3 >= 1 && N3 <= 3, "tile counts");
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int tile_floats = p.tr * p.tc * PITCH;
-  float* tile0 = smem;
-  int* tab0 = reinterpret_cast<int*>(smem + 2 * tile_floats);      // [buf][3][TABN]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lr = lane & 15, lq = lane >> 4;
-  const int tt = cat::xcd_remap(blockIdx.x, gridDim.x);
-  const int n = tt / p.tiles, t = tt - n * p.tiles;
-  const int oy0 = (t / p.tiles_x) * TH, ox0 = (t % p.tiles_x) * TW;
-  const int slots = p.tr * p.tc * 4, quad = tid & 3;
-  unsigned soff[MAXIT], smask = 0;
-#pragma unroll
-  for (int it = 0; it < MAXIT; ++it) {
-    const int pix = (tid + it * 256) >> 2;
-    const int r = pix / p.tc;
-    int iy = oy0 - p.hl + r, ix = ox0 - p.hl + (pix - r * p.tc);
-    bool v = tid + it * 256 < slots;
-    if (p.reflect) {
-      v = v && iy > -p.H && iy < 2 * p.H - 1 && ix > -p.W && ix < 2 * p.W - 1;
-      iy = cat::reflect_idx(iy, p.H);
-      ix = cat::reflect_idx(ix, p.W);
-    } else {
-      v = v && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-    }
-    smask |= v ? (1u << it) : 0u;
-    soff[it] = v ? ((unsigned)(n * p.H + iy) * (unsigned)p.W + (unsigned)ix) * (unsigned)p.xcs + quad * 4 : 0u;
-  }
-  f4 sreg[MAXIT];
-  auto gload = [&](int c0) {
-    const bool qv = c0 + quad * 4 < p.c4;
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) sreg[it] = *reinterpret_cast<const f4*>((((smask >> it) & 1u) && qv) ? p.x + soff[it] + c0 : g_zero);
-  };
-  auto sstore = [&](int buf, int c0) {
-    float* tile = tile0 + buf * tile_floats;
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) {
-      const int idx = tid + it * 256;
-      if (idx < slots) *reinterpret_cast<f4*>(tile + (idx >> 2) * PITCH + quad * 4) = sreg[it];
-    }
-    const int nq = min(4, (p.c4 - c0) >> 2);
-    if (tid < TABN) {
-      const int tap = tid / nq, qd = tid - tap * nq;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int ks = k == 0 ? 5 : (k == 1 ? 3 : 1), taps = ks * ks;
-        int off = 0;
-        if (tid < ((taps * nq + 3) >> 2) * 4 && tap < taps) {
-          const int ky = tap / ks, kx = tap - ky * ks, d = p.hl - (ks >> 1);
-          off = ((d + ky) * p.tc + d + kx) * PITCH + qd * 4;
-        }
-        tab0[(buf * 3 + k) * TABN + tid] = off;
-      }
-    }
-  };
-  const f4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f4 acc5[MT][N5], acc3[MT][N3], accA[MT][3], accB[MT][3], accC[MT][3], accD[MT][3];      // the 1 x 1 slot: passes A..D of up to 3 tiles
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-#pragma unroll
-    for (int j = 0; j < N5; ++j) acc5[i][j] = zero4;
-#pragma unroll
-    for (int j = 0; j < N3; ++j) acc3[i][j] = zero4;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) accA[i][j] = accB[i][j] = accC[i][j] = accD[i][j] = zero4;
-  }
-  int abase[MT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i) abase[i] = ((2 * wave + i) * p.tc + lr) * PITCH;
-  const __amdgpu_buffer_rsrc_t r5 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.pack[0]), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.pack[1]), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.pack[2]), 0, 0x7fffffff, 0x00020000);
-  unsigned jb5[N5], jb3[N3], jb1[4][3];
-#pragma unroll
-  for (int j = 0; j < N5; ++j) jb5[j] = (unsigned)(j * 64 + lane) * 16u;
-#pragma unroll
-  for (int j = 0; j < N3; ++j) jb3[j] = (unsigned)(j * 64 + lane) * 16u;
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) jb1[q][j] = (unsigned)(min(3 * q + j, N1 - 1) * 64 + lane) * 16u;
-  unsigned so5 = 0, so3 = 0, so1 = 0;     // byte offsets of the current chunk in the three streams
-  gload(0);
-  sstore(0, 0);
-  __syncthreads();
-  int buf = 0;
-  for (int c0 = 0; c0 < p.c4; c0 += 16) {
-    const bool more = c0 + 16 < p.c4;
-    if (more) gload(c0 + 16);
-    const int nq = min(4, (p.c4 - c0) >> 2);
-    const float* tile = tile0 + buf * tile_floats;
-    const int* tab = tab0 + buf * 3 * TABN + lq;
-    f4 bw[3];
-    wload<(P1 == 1 ? R1 : 3)>(bw, r1, jb1[0], so1);
-    {
-      const int ngr = (25 * nq + 3) >> 2;
-      mma_groups<MT, N5>(acc5, tile, tab, abase, r5, jb5, so5, (unsigned)N5 * 1024u, ngr);
-      so5 += (unsigned)ngr * N5 * 1024u;
-    }
-    {
-      const int ngr = (9 * nq + 3) >> 2;
-      mma_groups<MT, N3>(acc3, tile, tab + TABN, abase, r3, jb3, so3, (unsigned)N3 * 1024u, ngr);
-      so3 += (unsigned)ngr * N3 * 1024u;
-    }
-    {
-      // the 1 x 1 slot: ONE group per chunk (the centre tap's four quads), N1 tiles wide -- the A fragments are read once, the filter
-      // blocks of pass q + 1 are in flight behind the MFMAs of pass q, those of pass 0 were requested at the top of the chunk
-      f4 aw[MT], bx[3];
-      const int off = tab[2 * TABN];
-#pragma unroll
-      for (int i = 0; i < MT; ++i) aw[i] = *reinterpret_cast<const f4*>(tile + abase[i] + off);
-      if constexpr (P1 > 1) wload<(P1 == 2 ? R1 : 3)>(bx, r1, jb1[1], so1);
-      __builtin_amdgcn_sched_barrier(0);
-      wmma<MT, (P1 == 1 ? R1 : 3)>(accA, aw, bw);
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (P1 > 1) {
-        if constexpr (P1 > 2) wload<(P1 == 3 ? R1 : 3)>(bw, r1, jb1[2], so1);
-        __builtin_amdgcn_sched_barrier(0);
-        wmma<MT, (P1 == 2 ? R1 : 3)>(accB, aw, bx);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if constexpr (P1 > 2) {
-        if constexpr (P1 > 3) wload<R1>(bx, r1, jb1[3], so1);
-        __builtin_amdgcn_sched_barrier(0);
-        wmma<MT, (P1 == 3 ? R1 : 3)>(accC, aw, bw);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if constexpr (P1 > 3) wmma<MT, R1>(accD, aw, bx);
-    }
-    so1 += (unsigned)N1 * 1024u;
-    if (more) {
-      sstore(buf ^ 1, c0 + 16);
-      __syncthreads();
-      buf ^= 1;
-    }
-  }
+#include "conv_pk_s1w_main.h"      // the main loop, shared with tstage1ws_kernel (conv_s1ws.hip)
   s1w_store<N5>(acc5, p, 0, 0, n, oy0, ox0, wave, lr, lq);
   s1w_store<N3>(acc3, p, 1, 0, n, oy0, ox0, wave, lr, lq);
   s1w_store<3>(accA, p, 2, 0, n, oy0, ox0, wave, lr, lq);

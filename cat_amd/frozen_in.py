@@ -3,10 +3,12 @@
 The CycleGAN-style distillation runs an InstanceNorm teacher in eval mode under no_grad (base_inception_distiller.py:168,
 inception_distiller.py:100-104).  An InstanceNorm2d without running statistics computes the same function in eval() as in train(), so
 nothing folds (cat_amd/frozen.py folds BatchNorm only) -- but the block is exactly the forward of the fused training pipeline
-(cat_amd/fused_unit.py, per-sample statistics), which the fused block path refuses for the teacher's widths because its BACKWARD kernels
-hold 4 * CAT_DWM_MAXQ_BWD channels.  This module is the forward-only plan for such blocks, about ten launches instead of ~55:
+(cat_amd/fused_unit.py, per-sample statistics), which in eval mode serves only blocks an inference runner owns (fused_block.own_eval).
+This module is the forward-only plan of a frozen teacher's blocks, eight launches instead of ~55; its depthwise launches take
+CAT_DWM_MAXQ quads (a plan that trains groups by CAT_DWM_MAXQ_BWD, the width of the backward kernel's argument arrays; one workgroup of
+either kernel stages one quad group, so LDS bounds neither):
 
-    stage 1   first convs of all branches -> Z1 + tile statistics                 (fused_unit.stage1: cat_tconv_fwd / cat_tstage1_fwd)
+    stage 1   first convs of all branches -> Z1 + tile statistics                 (fused_unit.stage1: cat_tstage1ws_fwd; CAT_STAGE1WS=0: cat_tconv_fwd)
     finalize  per-sample scale / shift of every stage-1 norm                      (cat_tnorm_finalize, G = N)
     dw        the depthwise convs, normalise + activation applied while staging, in BRANCH-ALIGNED launches of at most CAT_DWM_MAXQ
               channel quads (the teacher's 3 x 11 quads: 22 + 11)                 (cat_dwm_fwd)
@@ -93,19 +95,8 @@ def own_network(net, min_tiles=None):
 
 
 def dw_launches(quads, maxq=L.DWM_MAXQ):
-    """Branch-aligned grouping of the depthwise branches (quads[i] = channel quads of branch i) into launches of at most `maxq` quads:
-    -> [(first branch, one past the last)], or None when a single branch is wider than a launch."""
-    out, b0, acc = [], 0, 0
-    for i, q in enumerate(quads):
-        if q > maxq:
-            return None
-        if acc + q > maxq:
-            out.append((b0, i))
-            b0, acc = i, 0
-        acc += q
-    if quads:
-        out.append((b0, len(quads)))
-    return out
+    """fused_unit.dw_launches with the forward kernel's launch width: this forward-only path's grouping (the teacher's 3 x 11 quads: 22 + 11)."""
+    return U.dw_launches(quads, maxq)
 
 
 def applicable(block, x):
@@ -149,31 +140,6 @@ def _dw_filters(block, p):
     return derived.lookup(block, FROZEN_IN, key, lambda prev: dw_filter_segment(p.dws, p.Cout, p.dev))
 
 
-def _dw_stage(p, z1, ss1, zd, partd):
-    """cat_dwm_fwd per branch-aligned launch: channel slices of Z1 / Zd / the statistics table, and the slice of the 5 x 5 filter frame
-    (the kernel reads it with the launch's own row width) re-cut whenever the plan's operands were refreshed."""
-    n, h, w, _ = z1.shape
-    launches = dw_launches([U.cs4(b['m']) // 4 for b in p.dws])
-    frames = getattr(p, '_fin_frames', None)
-    if frames is None or frames[0] != p.key:
-        full = p.w25[:25 * p.hcd].view(25, p.hcd)
-        cut = [full if (b0, b1) == (0, len(p.dws)) else full[:, p.dws[b0]['od']:p.dws[b1 - 1]['od'] + U.cs4(p.dws[b1 - 1]['m'])].contiguous()
-               for b0, b1 in launches]
-        frames = p._fin_frames = (p.key, cut)
-    for (b0, b1), frame in zip(launches, frames[1]):
-        o, end = p.dws[b0]['od'], p.dws[b1 - 1]['od'] + U.cs4(p.dws[b1 - 1]['m'])
-        gd = L.DwmGeom()
-        gd.N, gd.H, gd.W, gd.nq, gd.xcs, gd.ycs, gd.scs, gd.reflect = n, h, w, (end - o) // 4, p.hc1, p.hcd, p.hcd, int(p.reflect)
-        gd.sstride, gd.act, gd.slope = p.hc1, p.act, p.slope
-        for b in p.dws[b0:b1]:
-            for q in range((b['od'] - o) // 4, (b['od'] - o + U.cs4(b['m'])) // 4):
-                gd.ks[q] = b['kd']
-        i = 4 * (p.dw_in0 + o)
-        L.call('cat_dwm_fwd', C.byref(gd), C.c_void_p(z1.data_ptr() + i), C.c_void_p(ss1[0].data_ptr() + i), C.c_void_p(ss1[1].data_ptr() + i), ops._p(frame),
-               C.c_void_p(p.biasd.data_ptr() + 4 * o) if p.has_biasd else None, C.c_void_p(zd.data_ptr() + 4 * o), C.c_void_p(partd.data_ptr() + 4 * o),
-               ops._stream())
-
-
 def _wide_segs(block, p, z1, ss1, zd, ssd):
     """Stage 2 for the wide tile: one segment per residual branch (its slice of Z1), all depthwise slices of Zd as one."""
     slab = lambda buf, o, c: buf[..., o:o + c].permute(0, 3, 1, 2)
@@ -188,7 +154,7 @@ def _wide_segs(block, p, z1, ss1, zd, ssd):
 
 def block_forward(block, x):
     x = ops.conform(x)
-    p = fused_block.plan_for(block, x)
+    p = fused_block.plan_for(block, x, L.DWM_MAXQ)      # forward only: launches of up to CAT_DWM_MAXQ quads, their filter frames cut by the plan
     p.prepare()
     p.shards = 1
     n, c, h, w = x.shape
@@ -205,7 +171,7 @@ def block_forward(block, x):
     if p.dws:
         zd = torch.empty((n, h, w, p.hcd), device=dev, dtype=torch.float32)
         partd = torch.empty((tiles, 2, p.hcd), device=dev, dtype=torch.float32)
-        _dw_stage(p, z1, ss1, zd, partd)
+        U.dwm_fwd(p, z1, ss1[0], ss1[1], zd, partd, p.reflect, True)
         ssd = run(U.finalize_g(p, partd, p.hcd, n, h, w, p.gammad, p.betad, [(b['od'], b['m'], b['bn2']) for b in p.dws], sync=None))[0]
     # ---- stage 2: T = the branch sum, + pw_bn's statistics
     t = ops.empty_act(n, c, h, w, dev)

@@ -37,6 +37,11 @@ from . import fused_unit as U
 from .fused_unit import prepare_many, prepare_plans      # noqa: F401  (the generator's per-step preparation: inception_generator.py)
 
 _ENABLED = os.environ.get('CAT_FUSED_BLOCK', '1') != '0'
+# Blocks whose depthwise branches sum to more than CAT_DWM_MAXQ_BWD channel quads (the full-width teachers: 3 x 11) take this path with the
+# depthwise stage as branch-aligned launches of at most that many quads (fused_unit.dw_launches) with CAT_FUSED_WIDE=1 / set_wide(True).
+# Off by default (such blocks run layer by layer, as they always did): the graphed CycleGAN teacher step at batch 4 measured 134.1 ms on
+# this path against 126.1 ms layer by layer; launched eagerly it is 146.8 against 207.5 ms (profiles/wide_block_bench.txt)
+_WIDE = os.environ.get('CAT_FUSED_WIDE', '0') != '0'
 # Per-block opt-in to this path in eval() mode: cat_amd.infer.StudentRunner registers the blocks of the network it owns.  An InstanceNorm2d
 # without running statistics computes the same function in eval() as in train(), so forward(block, x, save=None) is the block's eval
 # forward as it stands: per-sample statistics collected and finalized, no running statistics to touch (fused_unit.slices passes none).
@@ -61,6 +66,16 @@ def eval_owned(block):
 def set_enabled(on):
     global _ENABLED
     _ENABLED = bool(on)
+
+
+def set_wide(on):
+    global _WIDE
+    old, _WIDE = _WIDE, bool(on)
+    return old
+
+
+def _dw_quads(block):
+    return [U.cs4(op[0][0].out_channels) // 4 for op in block.dw_ops]
 
 
 def _dropout(block):
@@ -108,8 +123,11 @@ def applicable(block, x):
     ks = [op[1][0].kernel_size[0] for op in block.res_ops] + [op[2][0].kernel_size[0] for op in block.dw_ops]
     if any(k not in (1, 3, 5) for k in ks):
         return False
-    if sum(U.cs4(op[0][0].out_channels) for op in block.dw_ops) > 4 * L.DWM_MAXQ_BWD or len(block.res_ops) + len(block.dw_ops) > L.TCONV_MAXSEG:
+    if len(block.res_ops) + len(block.dw_ops) > L.TCONV_MAXSEG:
         return False
+    quads = _dw_quads(block)
+    if sum(quads) > L.DWM_MAXQ_BWD and (not _WIDE or U.dw_launches(quads, L.DWM_MAXQ_BWD) is None):
+        return False      # more quads than one depthwise launch takes: several branch-aligned launches, unless one branch alone is too wide
     return not U.has_hooks(block.children())
 
 
@@ -117,7 +135,7 @@ class _Plan(U.Plan):
     """The layout of one block (C_in = C_out = C) + what its closing pw_bn, padding and norm kind add."""
     what = 'fused block'
 
-    def __init__(self, block, dev):
+    def __init__(self, block, dev, dw_maxq=L.DWM_MAXQ_BWD):
         self.block = block
         for m in block.modules():       # conv weights into the kernels' [O][kh][kw][round_up(I, 4)] storage (as Conv2d.forward does lazily)
             if isinstance(m, cnn.Conv2d) and m.groups == 1:
@@ -134,7 +152,7 @@ class _Plan(U.Plan):
                for i, op in enumerate(block.res_ops)]
         dws = [dict(kind='dw', j=len(res) + i, k=1, kd=op[2][0].kernel_size[0], m=op[0][0].out_channels, conv1=op[0][0], bn1=op[0][1],
                     dconv=op[2][0], bn2=op[2][1], conv2=op[4]) for i, op in enumerate(block.dw_ops)]
-        super().__init__(res, dws, block.input_dim, block.input_dim, dev, list(block.parameters()))
+        super().__init__(res, dws, block.input_dim, block.input_dim, dev, list(block.parameters()), dw_maxq)
         self.C, self.cs = self.Cin, self.csi
 
     def live_shards(self):
@@ -156,13 +174,16 @@ class _Plan(U.Plan):
         self._prepare_own(backward)
 
 
-def plan_for(block, x):
+def plan_for(block, x, dw_maxq=L.DWM_MAXQ_BWD):
+    """The block's plan.  dw_maxq: the widest depthwise launch the caller's kernels take -- the backward kernel's for a plan that trains (also
+    its forward), CAT_DWM_MAXQ for the forward-only frozen teacher (cat_amd/frozen_in.py); a plan built for another grouping is rebuilt."""
     p = getattr(block, U.PLAN, None)
     # the plan holds Parameter OBJECTS (gradient targets are keyed by identity): a parameter replaced by one of the same shape
     # (module.weight = nn.Parameter(...), weight transfer) invalidates it like a shape change does
     if p is None or p.dev != x.device or p.shapes != tuple(tuple(q.shape) for q in block.parameters()) or \
-            p.ids != tuple(id(q) for q in block.parameters()):
-        p = _Plan(block, x.device)
+            p.ids != tuple(id(q) for q in block.parameters()) or \
+            (p.dw_maxq != dw_maxq and p.dw_spans != tuple(U.dw_launches(_dw_quads(block), dw_maxq) or ())):
+        p = _Plan(block, x.device, dw_maxq)
         setattr(block, U.PLAN, p)
     return p
 

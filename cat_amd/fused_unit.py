@@ -1,8 +1,8 @@
 """The fused inception block (cat_amd/fused_block.py) and the fused six-branch SPADE unit (cat_amd/fused_spade.py) are ONE pipeline
 
-    stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tconv_fwd)
+    stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tstage1ws_fwd / cat_tconv_fwd)
     finalize  scale / shift of all stage-1 norms + their running statistics                               (cat_tnorm_finalize)
-    dw        all depthwise convs as one launch, norm + activation of stage 1 applied while staging      (cat_dwm_fwd)
+    dw        all depthwise convs (one launch per <= 18 / 24 channel quads), norm + activation of stage 1 applied while staging   (cat_dwm_fwd)
     finalize
     stage 2   the branch sum: the second convs K-concatenated, norm + activation applied while staging   (cat_tconv_fwd)
 
@@ -27,6 +27,7 @@ partials reduced by one launch when there are no branch streams) and `skip_grad`
 callers keep their stage-2 launch and tail (the block's closing pw_bn and residual; the unit's epilogue addend), their plan subclass and
 the autograd Functions."""
 import ctypes as C
+import os
 
 import torch
 
@@ -38,10 +39,38 @@ from . import optim
 from . import tconv
 
 PLAN = derived.slot('_cat_fused_plan')      # R7: a fused block's plan (the slot holds the Plan itself, which keeps its own keys)
+# Stage 1 of a block whose widths cat_tstage1_fwd does not take (the full-width teacher: 42 / 42 / 176) as ONE statistics-writing launch
+# (cat_tstage1ws_fwd, csrc/conv_s1ws.hip) instead of one cat_tconv_fwd per kernel size, each staging the same input.  CAT_STAGE1WS=0 /
+# set_stage1_wide(False): the three launches (measurements: profiles/wide_block_bench.txt)
+_STAGE1WS = os.environ.get('CAT_STAGE1WS', '1') != '0'
+
+
+def set_stage1_wide(on):
+    global _STAGE1WS
+    old, _STAGE1WS = _STAGE1WS, bool(on)
+    return old
 
 
 def cs4(c):
     return (c + 3) // 4 * 4
+
+
+def dw_launches(quads, maxq):
+    """Branch-aligned grouping of the depthwise branches (quads[i] = channel quads of branch i) into launches of at most `maxq` quads, in
+    order and greedily: -> [(first branch, one past the last)], or None when a single branch is wider than a launch.  The quads of a
+    depthwise conv are independent and one workgroup of cat_dwm_fwd / cat_dwm_bwd stages one group of at most kDwGroup of them, so a
+    launch's width is bounded only by the kernels' argument arrays (CAT_DWM_MAXQ forward, CAT_DWM_MAXQ_BWD backward)."""
+    out, b0, acc = [], 0, 0
+    for i, q in enumerate(quads):
+        if q > maxq:
+            return None
+        if acc + q > maxq:
+            out.append((b0, i))
+            b0, acc = i, 0
+        acc += q
+    if quads:
+        out.append((b0, len(quads)))
+    return out
 
 
 def has_hooks(mods):
@@ -74,7 +103,7 @@ class Plan:
     s1d = None
     wgrad_batch = False
 
-    def __init__(self, res, dws, cin, cout, dev, params):
+    def __init__(self, res, dws, cin, cout, dev, params, dw_maxq=L.DWM_MAXQ_BWD):
         self.dev = dev
         self.params = params
         self.Cin, self.csi = cin, cs4(cin)
@@ -93,6 +122,17 @@ class Plan:
             off += cs4(b['m'])
         self.hcd = off
         self.dw_in0 = dws[0]['o1'] if dws else 0
+        # depthwise launches: branch-aligned groups of at most dw_maxq quads, ONE grouping for both directions of a training plan (the
+        # backward one; a forward-only plan may ask for CAT_DWM_MAXQ).  Each launch reads its own contiguous 5 x 5 filter frame
+        # [25][launch width] at float offset 25 * (its first channel) of w25 -- one launch: the frame [25][hcd] at offset 0.  A branch wider
+        # than a launch is refused by the callers' `applicable`; such a plan keeps one launch, which the kernel refuses
+        self.dw_maxq = dw_maxq
+        spans = dw_launches([cs4(b['m']) // 4 for b in dws], dw_maxq) or ([(0, len(dws))] if dws else [])
+        self.dw_spans = tuple(spans)
+        self.dw_groups = [(dws[b0:b1], dws[b0]['od'], dws[b1 - 1]['od'] + cs4(dws[b1 - 1]['m'])) for b0, b1 in spans]      # (branches, first channel, end)
+        for bs, o, end in self.dw_groups:
+            for b in bs:
+                b['f0'], b['fcs'] = o, end - o
         self.branches, self.res, self.dws = order, res, dws
         # stage-1 launches: one per first-conv kernel size
         self.groups = []
@@ -234,7 +274,7 @@ class Plan:
             wd = b['dconv'].weight
             if not wd.is_contiguous():
                 raise RuntimeError(f'{self.what}: depthwise weights must be contiguous')
-            fwd.append(dict(kind=2, srcs=[wd.data_ptr()], dst=self.w25.data_ptr(), Nn=b['m'], ks=kd, col0=b['od'], cs=self.hcd, threads=b['m'] * kd * kd))
+            fwd.append(dict(kind=2, srcs=[wd.data_ptr()], dst=self.w25.data_ptr() + 4 * 25 * b['f0'], Nn=b['m'], ks=kd, col0=b['od'] - b['f0'], cs=b['fcs'], threads=b['m'] * kd * kd))
         b2 = [b['conv2'].bias for b in self.branches if b['conv2'].bias is not None]
         if b2:
             fwd.append(vec(self.bias2, 0, b2, self.Cout))
@@ -328,7 +368,13 @@ def stage1(p, x, z1, part1, reflect=False):
     statistics (always one launch per kernel size)."""
     n, c, h, w = x.shape
     by_k = {g['k']: g for g in p.groups}
-    if part1 is not None and len(p.groups) == 3 and L.query('cat_tstage1_supported', by_k[5]['width'], by_k[3]['width'], by_k[1]['width']):
+    widths = [by_k[k]['width'] for k in (5, 3, 1)] if part1 is not None and len(p.groups) == 3 else None
+    entry = None
+    if widths is not None and L.query('cat_tstage1_supported', *widths):
+        entry = 'cat_tstage1_fwd'
+    elif widths is not None and _STAGE1WS and L.query('cat_tstage1ws_supported', *widths):
+        entry = 'cat_tstage1ws_fwd'      # the wide block's widths: the same arguments and output contract
+    if entry is not None:
         # one launch: the three kernel sizes share every staged input tile
         gs = L.Stage1Geom()
         gs.N, gs.H, gs.W, gs.xcs, gs.cin, gs.reflect, gs.ycs, gs.scs = n, h, w, ops.act_cs(x), c, int(reflect), p.hc1, p.hc1
@@ -337,7 +383,7 @@ def stage1(p, x, z1, part1, reflect=False):
             g = by_k[k]
             gs.col0[slot], gs.width[slot], gs.nvalid[slot] = g['off'], g['width'], sum(b['m'] for b in g['branches'])
             packs[slot] = g['pack'].data_ptr()
-        L.call('cat_tstage1_fwd', C.byref(gs), ops._p(x), packs, ops._p(p.bias1) if p.has_bias1 else None, ops._p(z1), ops._p(part1), ops._stream())
+        L.call(entry, C.byref(gs), ops._p(x), packs, ops._p(p.bias1) if p.has_bias1 else None, ops._p(z1), ops._p(part1), ops._stream())
         return
     for g in p.groups:
         pad = (g['k'] - 1) // 2
@@ -347,24 +393,30 @@ def stage1(p, x, z1, part1, reflect=False):
                   ycw=g['width'], yptr=z1.data_ptr() + 4 * g['off'], nvalid=sum(b['m'] for b in g['branches']), **stats)
 
 
-def dwm_geom(p, n, h, w, reflect):
+def dwm_geom(p, n, h, w, reflect, group):
+    """Geometry of ONE depthwise launch: group = (branches, first channel, end) of p.dw_groups; quads relative to the launch's first."""
+    bs, o, end = group
     gd = L.DwmGeom()
-    gd.N, gd.H, gd.W, gd.nq, gd.xcs, gd.ycs, gd.scs, gd.reflect = n, h, w, p.hcd // 4, p.hc1, p.hcd, p.hcd, int(reflect)
-    for b in p.dws:
-        for q in range(b['od'] // 4, (b['od'] + cs4(b['m'])) // 4):
+    gd.N, gd.H, gd.W, gd.nq, gd.xcs, gd.ycs, gd.scs, gd.reflect = n, h, w, (end - o) // 4, p.hc1, p.hcd, p.hcd, int(reflect)
+    for b in bs:
+        for q in range((b['od'] - o) // 4, (b['od'] - o + cs4(b['m'])) // 4):
             gd.ks[q] = b['kd']
     return gd
 
 
 def dwm_fwd(p, z1, scale, shift, zd, partd, reflect=False, per_sample=False):
-    """All depthwise convs as one launch: act(Z1 * scale + shift) of the dw slices, applied while staging, -> Zd (+ tile statistics into
-    partd unless None).  per_sample: scale / shift are [n][hc1] (InstanceNorm) instead of one row."""
+    """All depthwise convs, one launch per group of the plan (one for up to dw_maxq quads): act(Z1 * scale + shift) of the dw slices,
+    applied while staging, -> Zd (+ tile statistics into partd unless None).  A launch works on channel slices of Z1 / scale / shift /
+    Zd / the statistics table and on its own filter frame.  per_sample: scale / shift are [n][hc1] (InstanceNorm) instead of one row."""
     n, h, w, _ = z1.shape
-    gd = dwm_geom(p, n, h, w, reflect)
-    gd.sstride, gd.act, gd.slope = (p.hc1 if per_sample else 0), p.act, p.slope
-    o = 4 * p.dw_in0
-    L.call('cat_dwm_fwd', C.byref(gd), C.c_void_p(z1.data_ptr() + o), C.c_void_p(scale.data_ptr() + o), C.c_void_p(shift.data_ptr() + o), ops._p(p.w25),
-           ops._p(p.biasd) if p.has_biasd else None, ops._p(zd), ops._p(partd), ops._stream())
+    at = lambda t, off: C.c_void_p(t.data_ptr() + 4 * off)
+    for group in p.dw_groups:
+        o = group[1]
+        gd = dwm_geom(p, n, h, w, reflect, group)
+        gd.sstride, gd.act, gd.slope = (p.hc1 if per_sample else 0), p.act, p.slope
+        i = p.dw_in0 + o
+        L.call('cat_dwm_fwd', C.byref(gd), at(z1, i), at(scale, i), at(shift, i), at(p.w25, 25 * o), at(p.biasd, o) if p.has_biasd else None,
+               at(zd, o), at(partd, o) if partd is not None else None, ops._stream())
 
 
 def stage2_segs(p, z1, ss1, zd, ssd, reflect=False, per_sample=False, a1=None, ad=None):
@@ -569,19 +621,25 @@ def wgrad(gw, xp, dyp, dst, acc, stream):
 
 
 def dw_bwd(p, a1, da1, dzd, grads, reflect=False):
-    """All depthwise convs at once: input gradient (reflect padding folded in the kernel) into the dw slices of dA1, filter gradients reduced
-    straight into the parameters' gradient buffers (FusedAdam-owned) or into fresh tensors recorded in `grads`."""
+    """All depthwise convs, one launch per group of the plan: input gradient (reflect padding folded in the kernel) into the dw slices of
+    dA1, filter gradients reduced straight into the parameters' gradient buffers (FusedAdam-owned) or into fresh tensors recorded in
+    `grads`.  The sink is claimed ONCE for all branches; a launch gets its own branches' destinations, so every parameter is written
+    (or accumulated into) by exactly one launch."""
     n, h, w, _ = a1.shape
-    nb = len(p.dws)
-    gd = dwm_geom(p, n, h, w, reflect)
     wts = [b['dconv'].weight for b in p.dws]
     sink = optim.claim(wts, f'{p.what} backward (depthwise)')
     dsts, acc_dw = sink or ([torch.empty_like(q) for q in wts], 0)
-    IA = C.c_int * nb
-    wsd = ops.workspace(L.query('cat_dwm_bwd_ws_bytes', C.byref(gd)), a1.device)
-    L.call('cat_dwm_bwd', C.byref(gd), C.c_void_p(a1.data_ptr() + 4 * p.dw_in0), ops._p(dzd), ops._p(p.w25),
-           C.c_void_p(da1.data_ptr() + 4 * p.dw_in0), p.hc1, nb, IA(*[b['od'] for b in p.dws]), IA(*[b['m'] for b in p.dws]),
-           IA(*[b['kd'] for b in p.dws]), (C.c_void_p * nb)(*[d_.data_ptr() for d_ in dsts]), acc_dw, ops._p(wsd), ops._stream())
+    dst_of = {id(b): d_ for b, d_ in zip(p.dws, dsts)}
+    at = lambda t, off: C.c_void_p(t.data_ptr() + 4 * off)
+    for group in p.dw_groups:
+        bs, o, _ = group
+        nb = len(bs)
+        gd = dwm_geom(p, n, h, w, reflect, group)
+        IA = C.c_int * nb
+        wsd = ops.workspace(L.query('cat_dwm_bwd_ws_bytes', C.byref(gd)), a1.device)
+        L.call('cat_dwm_bwd', C.byref(gd), at(a1, p.dw_in0 + o), at(dzd, o), at(p.w25, 25 * o), at(da1, p.dw_in0 + o), p.hc1, nb,
+               IA(*[b['od'] - o for b in bs]), IA(*[b['m'] for b in bs]), IA(*[b['kd'] for b in bs]),
+               (C.c_void_p * nb)(*[dst_of[id(b)].data_ptr() for b in bs]), acc_dw, ops._p(wsd), ops._stream())
     for q, d_ in zip(wts, dsts):          # not all owned (tests): fresh tensors, copied / added into the views of those that are
         grads[id(q)] = None if sink is not None else optim.deliver(q, d_)
 

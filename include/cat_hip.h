@@ -541,8 +541,11 @@ int cat_affine_res_fwd(const float* x, int xcs, const float* scale, const float*
 /* All depthwise convs of a block (the groups=midp ConvBNReLU convs, inception_modules.py:166-173; k = 1 / 3 / 5 per channel quad) as one
  * launch over channel slices: input = first-stage pre-norm buffer with that stage's scale / shift + activation applied while staging,
  * output = concatenated pre-norm buffer + its per-tile statistics.  w25: [25][4*nq] filters embedded in a 5 x 5 frame (cat_prep_run). */
-#define CAT_DWM_MAXQ 24      /* channel quads of the fused depthwise stage, forward (96 channels: 101 KB of LDS) */
-#define CAT_DWM_MAXQ_BWD 18  /* ... and of cat_dwm_bwd (two patches in LDS: 72 channels = 142 KB -- the unpruned gamma|beta nets, 3 x 21 -> 72) */
+/* Channel quads of ONE launch: the sizes of ks[] below and of the kernels' quad-group argument arrays.  One workgroup stages one group of at
+ * most kDwGroup quads of one kernel size (csrc/block_norm.hip), so LDS does not bound a launch; a block with more quads runs the stage as
+ * several branch-aligned launches on channel slices, each with its own [25][4*nq] filter frame (cat_amd/fused_unit.py dw_launches). */
+#define CAT_DWM_MAXQ 24      /* forward (96 channels) */
+#define CAT_DWM_MAXQ_BWD 18  /* cat_dwm_bwd (72 channels: the unpruned gamma|beta nets, 3 x 21 -> 72) */
 typedef struct {
   int N, H, W;
   int nq;               /* channel quads */
@@ -617,6 +620,15 @@ int cat_tstage1w_supported(int w5, int w3, int w1);
 int cat_tstage1w_fwd(const cat_tstage1w_t* g, const float* x, const float* const* packs, const float* const* biases, float* const* ys,
                      cat_stream_t stream);
 int cat_tstage1_dgrad(const cat_tstage1_t* g, const float* dy, const float* const* packs, float* const* dxs, const int* dxcs,
+                      cat_stream_t stream);
+/* cat_tstage1_fwd for the WIDE block (csrc/conv_s1ws.hip): the computation of cat_tstage1w_fwd -- one staging of the input tile per 16-channel
+ * chunk for the 5 x 5 conv, the 3 x 3 conv and the N-concatenated 1 x 1 convs, the teacher's widths -- with cat_tstage1_fwd's arguments and
+ * output contract: slot k writes columns [col0[k], col0[k] + width[k]) of the pre-norm buffer y (pixel stride g->ycs; bias added, no
+ * activation; the slice's padding columns, whose filters and bias are zero, come out as 0) and its per-tile statistics (sum, squared
+ * deviations from the tile mean) into the same columns of `stats` (rows of g->scs floats, the table cat_tnorm_finalize reads).  Zero and
+ * reflect padding.  cat_tstage1ws_supported(slot widths): 33..48 / 33..48 / 161..176 columns (3 + 3 + 11 N tiles). */
+int cat_tstage1ws_supported(int w5, int w3, int w1);
+int cat_tstage1ws_fwd(const cat_tstage1_t* g, const float* x, const float* const* packs, const float* bias, float* y, float* stats,
                       cat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,9 @@ the figure.  One JSON line per batch size, printed and written to --out (appende
 
     python tools/cyclegan_teacher_bench.py [--batches 1 4] [--steps 10] [--rounds 3] [--only eager|graph] [--label TEXT] [--out FILE] [--append]
 
-`--only eager` touches nothing but create_model / set_input / optimize_parameters: it measures any revision of the package."""
+`--only eager` touches nothing but create_model / set_input / optimize_parameters: it measures any revision of the package.
+The generators' 256-channel blocks take the fused block path with CAT_FUSED_WIDE=1 in the environment (off by default; the comparison:
+profiles/wide_block_bench.txt)."""
 import argparse
 import json
 import os

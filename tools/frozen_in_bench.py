@@ -3,12 +3,15 @@ InstanceNorm without running statistics, eval mode under no_grad) at batch 8, 25
 
     general      nobody owns the blocks: layer by layer, the launches of the parent revision
     fused-tconv  cat_amd/frozen_in.py with stage 2 on the LDS-tile kernel (cat_tconv_fwd with f_s and stats)
+    fused-s1x3   ... and stage 1 as one cat_tconv_fwd per kernel size instead of ONE cat_tstage1ws_fwd (CAT_STAGE1WS=0)
     fused-ksum   ... with stage 2 on the normalising wide DMA tile (cat_conv2d_ksum_norm_fwd)
 
 timed by HIP events around `--iters` eager forwards, `--rounds` alternating rounds after a warm-up of every path; the median round is the
 figure and the spread of the rounds stands next to it.  Then one profiled forward per fused path (cat_prof_enable: an event pair per entry
 point): the time per launch of the block tail on either kernel (families `conv_ksum_norm` and `conv_tconv_multi`: the multi-segment launches of
-cat_tconv_fwd are the tails and nothing else), both as a share of the fp32 MFMA peak from the algorithmic FLOPs the entry points report.  One JSON line, printed and written to --out.
+cat_tconv_fwd are the tails and nothing else), both as a share of the fp32 MFMA peak from the algorithmic FLOPs the entry points report; and
+stage 1 per block on either form (family `conv_tstage1ws` against the single-segment `conv_tconv` launches it replaces: 64 x 64 planes at
+the default size).  One JSON line, printed and written to --out.
 
     python tools/frozen_in_bench.py [--batch 8] [--size 256] [--iters 10] [--rounds 3] [--out profiles/frozen_in_teacher.json]"""
 import argparse
@@ -24,7 +27,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 MFMA_F32_PEAK_TFLOPS = 157.3      # v_mfma_f32_16x16x4_f32, 256 CUs at 2.4 GHz (bench.py's constant)
-PATHS = ('general', 'fused-tconv', 'fused-ksum')
+PATHS = ('general', 'fused-tconv', 'fused-s1x3', 'fused-ksum')
 
 
 def teacher():
@@ -36,12 +39,13 @@ def teacher():
 
 
 def select(net, path):
-    from cat_amd import frozen_in
+    from cat_amd import frozen_in, fused_unit
     for b in net.features:
         frozen_in.disown(b)
+    fused_unit.set_stage1_wide(path != 'fused-s1x3')
     if path != 'general':
         frozen_in.own_network(net)
-        frozen_in.set_tail(path.split('-')[1])
+        frozen_in.set_tail('ksum' if path == 'fused-ksum' else 'tconv')
 
 
 def forward(net, x):
@@ -123,6 +127,13 @@ def main():
     row['tail'] = {'launches': int(kc), 'ksum_norm_us_per_launch': round(1e3 * kms / max(kc, 1), 1), 'ksum_norm_share_of_fp32_mfma_peak': share(kfl, kms),
                    'tconv_launches': int(tc), 'tconv_us_per_launch': round(1e3 * tms / max(tc, 1), 1), 'tconv_share_of_fp32_mfma_peak': share(tfl, tms)}
     assert kc == nb and tc == nb, (kc, tc, nb)
+    # stage 1: ONE cat_tstage1ws_fwd per block against the three single-segment cat_tconv_fwd launches it replaces
+    wc, wms, wfl = fam['fused-tconv'].get('conv_tstage1ws', (0, 0.0, 0.0))
+    c1, ms1, fl1 = fam['fused-tconv'].get('conv_tconv', (0, 0.0, 0.0))      # (single-segment launches that are not stage 1, if any)
+    c3, ms3, fl3 = fam['fused-s1x3'].get('conv_tconv', (0, 0.0, 0.0))
+    assert wc == nb and c3 - c1 == 3 * nb and 'conv_tstage1ws' not in fam['fused-s1x3'], (wc, c1, c3, nb)
+    row['stage1'] = {'one_launch_us_per_block': round(1e3 * wms / nb, 1), 'one_launch_share_of_fp32_mfma_peak': share(wfl, wms),
+                     'three_launches_us_per_block': round(1e3 * (ms3 - ms1) / nb, 1), 'three_launches_share_of_fp32_mfma_peak': share(fl3 - fl1, ms3 - ms1)}
     for path in PATHS[1:]:
         row['families_' + path.replace('-', '_')] = {k: [v[0], round(v[1], 3)] for k, v in sorted(fam[path].items())}
     line = json.dumps(row)
