@@ -247,7 +247,10 @@ __global__ __launch_bounds__(256) void reflect_fold_kernel(const float* __restri
 // size (common.h: dw_quad_groups); thread = (pixel, quad parity within the group).  The groups of a tile share nothing: the patch of a group
 // is 15 KB, so several workgroups share a CU and one's staging overlaps another's taps.  Per channel the arithmetic does not depend on the
 // grouping: taps in (ky, kx) order, tile sums by wave_sum over the same 64 pixels, lower + upper half tile, two passes (sum, then M2).
-constexpr int DWM_PS = (TH + 4) * (TW + 4) + 2;      // f4 per quad plane of a patch: + 2 spreads the staging stores of a pixel's 4 quads over the banks
+// Every kernel of the stage is templated on the halo M: M = 2 is the 5 x 5 frame of cat_dwm_fwd / cat_dwm_bwd (k <= 5, a 12 x 20 patch),
+// M = 3 the 7 x 7 frame of cat_dwm7_fwd / cat_dwm7_bwd (k <= 7, a 14 x 22 patch of 19.8 KB per group).  Frame side = 2 M + 1.
+template <int M> constexpr int DWM_PS = (TH + 2 * M) * (TW + 2 * M) + 2;      // f4 per quad plane of a patch: + 2 spreads the staging stores of a pixel's 4 quads over the banks
+template <int M> constexpr int DWM_FT = (2 * M + 1) * (2 * M + 1);            // taps of the frame
 constexpr int DWM_GCS = cat::kDwGroup * 4;           // floats per tap / per wave row of a group
 
 struct DwmArgs {
@@ -260,24 +263,25 @@ struct DwmArgs {
   unsigned char gq0[CAT_DWM_MAXQ], gnq[CAT_DWM_MAXQ], gks[CAT_DWM_MAXQ];      // first quad, quad count, kernel size of each group
 };
 
-// the k x k taps of one pixel of one quad, fully unrolled; pl = the quad's plane of the patch, sw = its column of the [25][DWM_GCS] frame
-template <int K>
+// the k x k taps of one pixel of one quad, fully unrolled; pl = the quad's plane of the patch, sw = its column of the [taps][DWM_GCS] frame
+template <int M, int K>
 __device__ __forceinline__ f4 dwm_taps(const f4* pl, const float* sw, int py, int pxx, f4 a) {
-  constexpr int TC = TW + 4, O = 2 - K / 2;
+  constexpr int TC = TW + 2 * M, O = M - K / 2;
 #pragma unroll
   for (int ky = 0; ky < K; ++ky)
 #pragma unroll
     for (int kx = 0; kx < K; ++kx)
-      a += pl[(py + O + ky) * TC + pxx + O + kx] * *reinterpret_cast<const f4*>(sw + ((O + ky) * 5 + O + kx) * DWM_GCS);
+      a += pl[(py + O + ky) * TC + pxx + O + kx] * *reinterpret_cast<const f4*>(sw + ((O + ky) * (2 * M + 1) + O + kx) * DWM_GCS);
   return a;
 }
 
+template <int M>
 __global__ __launch_bounds__(256) void dwm_fwd_kernel(DwmArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int TR = TH + 4, TC = TW + 4, G = cat::kDwGroup;
-  f4* tile = reinterpret_cast<f4*>(smem);      // [G][DWM_PS] one plane per quad of the group
-  float* sw = smem + G * DWM_PS * 4;           // [25][DWM_GCS] filters in a 5 x 5 frame
-  float* red = sw + 25 * DWM_GCS;              // [4 waves][DWM_GCS]
+  constexpr int TR = TH + 2 * M, TC = TW + 2 * M, G = cat::kDwGroup, PS = DWM_PS<M>, FT = DWM_FT<M>;
+  f4* tile = reinterpret_cast<f4*>(smem);      // [G][PS] one plane per quad of the group
+  float* sw = smem + G * PS * 4;               // [FT][DWM_GCS] filters in a (2 M + 1)^2 frame
+  float* red = sw + FT * DWM_GCS;              // [4 waves][DWM_GCS]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int tt, grp;
   cat::dw_tile_group(blockIdx.x, p.N * p.tiles, p.ng, tt, grp);
@@ -286,7 +290,7 @@ __global__ __launch_bounds__(256) void dwm_fwd_kernel(DwmArgs p) {
   const int oy0 = (t / p.tiles_x) * TH, ox0 = (t % p.tiles_x) * TW;
   const int g = p.sstride ? n : 0;       // per-image statistics (InstanceNorm) or one group
   const int cs = p.nq * 4;
-  for (int i = tid; i < 25 * gn; i += 256) {
+  for (int i = tid; i < FT * gn; i += 256) {
     const int tap = i / gn, ql = i - tap * gn;
     *reinterpret_cast<f4*>(sw + tap * DWM_GCS + ql * 4) = *reinterpret_cast<const f4*>(p.w + tap * cs + (q0 + ql) * 4);
   }
@@ -302,7 +306,7 @@ __global__ __launch_bounds__(256) void dwm_fwd_kernel(DwmArgs p) {
       if (i < TR * TC * gn) {
         const int pix = i / gn, q = q0 + i - pix * gn;
         const int r = pix / TC, c = pix - r * TC;
-        int iy = oy0 - 2 + r, ix = ox0 - 2 + c;
+        int iy = oy0 - M + r, ix = ox0 - M + c;
         bool v;
         if (p.reflect) {
           v = iy > -p.H && iy < 2 * p.H - 1 && ix > -p.W && ix < 2 * p.W - 1;
@@ -325,7 +329,7 @@ __global__ __launch_bounds__(256) void dwm_fwd_kernel(DwmArgs p) {
 #pragma unroll
     for (int it = 0; it < SIT; ++it) {
       const int i = tid + it * 256;
-      if (i < TR * TC * gn) tile[(i % gn) * DWM_PS + i / gn] = xv[it];
+      if (i < TR * TC * gn) tile[(i % gn) * PS + i / gn] = xv[it];
     }
   }
   __syncthreads();
@@ -341,9 +345,10 @@ __global__ __launch_bounds__(256) void dwm_fwd_kernel(DwmArgs p) {
     out[k] = f4{0.f, 0.f, 0.f, 0.f};
     if (ql < gn) {
       f4 a = p.bias ? *reinterpret_cast<const f4*>(p.bias + q * 4) : f4{0.f, 0.f, 0.f, 0.f};
-      if (ks == 5) a = dwm_taps<5>(tile + ql * DWM_PS, sw + ql * 4, py, pxx, a);
-      else if (ks == 3) a = dwm_taps<3>(tile + ql * DWM_PS, sw + ql * 4, py, pxx, a);
-      else a = dwm_taps<1>(tile + ql * DWM_PS, sw + ql * 4, py, pxx, a);
+      if (M >= 3 && ks == 7) a = dwm_taps<M, M >= 3 ? 7 : 5>(tile + ql * PS, sw + ql * 4, py, pxx, a);
+      else if (ks == 5) a = dwm_taps<M, 5>(tile + ql * PS, sw + ql * 4, py, pxx, a);
+      else if (ks == 3) a = dwm_taps<M, 3>(tile + ql * PS, sw + ql * 4, py, pxx, a);
+      else a = dwm_taps<M, 1>(tile + ql * PS, sw + ql * 4, py, pxx, a);
       out[k] = a;
       if (pv) *reinterpret_cast<f4*>(p.y + (((int64_t)n * p.H + oy0 + py) * p.W + ox0 + pxx) * p.ycs + q * 4) = a;
     }
@@ -484,27 +489,48 @@ int cat_reflect_pad_bwd(const float* dxp, float* dx, int N, int H, int W, int C,
   return cat::check_launch("reflect_pad_bwd");
 }
 
-int cat_dwm_fwd(const cat_dwm_t* g, const float* x, const float* scale, const float* shift, const float* w25, const float* bias, float* y,
-                float* stats, cat_stream_t stream) {
+}  // extern "C"
+
+namespace {
+
+// M = 2: cat_dwm_fwd (w = [25][4 nq]); M = 3: cat_dwm7_fwd (w = [49][4 nq])
+template <int M>
+int dwm_fwd_launch(const cat_dwm_t* g, const float* x, const float* scale, const float* shift, const float* w25, const float* bias, float* y,
+                   float* stats, cat_stream_t stream) {
   CAT_REQUIRE(g->nq >= 1 && g->nq <= CAT_DWM_MAXQ, "dwm: %d channel quads (max %d)", g->nq, CAT_DWM_MAXQ);
   CAT_REQUIRE((g->xcs & 3) == 0 && (g->ycs & 3) == 0 && g->xcs >= 4 * g->nq && g->ycs >= 4 * g->nq, "dwm: channel layout");
-  CAT_REQUIRE(!g->reflect || (g->H > 2 && g->W > 2), "dwm: reflect padding wider than the plane");
+  CAT_REQUIRE(!g->reflect || (g->H > M && g->W > M), "dwm: reflect padding wider than the plane");
   DwmArgs a{};
   a.x = x; a.scale = scale; a.shift = shift; a.w = w25; a.bias = bias; a.y = y; a.stats = stats;
   a.xcs = g->xcs; a.sstride = g->sstride; a.ycs = g->ycs; a.scs = g->scs;
   a.N = g->N; a.H = g->H; a.W = g->W; a.nq = g->nq; a.reflect = g->reflect; a.act = g->act; a.slope = g->slope;
   a.tiles_x = cdiv(g->W, TW);
   a.tiles = a.tiles_x * cdiv(g->H, TH);
-  for (int q = 0; q < g->nq; ++q) CAT_REQUIRE(g->ks[q] == 1 || g->ks[q] == 3 || g->ks[q] == 5, "dwm: kernel size %d", g->ks[q]);
+  for (int q = 0; q < g->nq; ++q) CAT_REQUIRE(g->ks[q] == 1 || g->ks[q] == 3 || g->ks[q] == 5 || (M >= 3 && g->ks[q] == 7), "dwm: kernel size %d", g->ks[q]);
   a.ng = cat::dw_quad_groups(g->ks, g->nq, a.gq0, a.gnq);
   for (int k = 0; k < a.ng; ++k) a.gks[k] = (unsigned char)g->ks[a.gq0[k]];
-  constexpr size_t lds = (size_t)(cat::kDwGroup * DWM_PS * 4 + 25 * DWM_GCS + 4 * DWM_GCS) * sizeof(float);
+  constexpr size_t lds = (size_t)(cat::kDwGroup * DWM_PS<M> * 4 + DWM_FT<M> * DWM_GCS + 4 * DWM_GCS) * sizeof(float);
   static_assert(4 * lds <= 160 * 1024, "dwm: four workgroups per CU by LDS");
+  static_assert(lds <= 64 * 1024, "dwm: no LDS opt-in");
   double taps = 0.0;
   for (int q = 0; q < g->nq; ++q) taps += 4.0 * g->ks[q] * g->ks[q];
   cat::ProfScope prof("dwconv_fwd", 2.0 * (double)g->N * g->H * g->W * taps, 0.0, stream);
-  dwm_fwd_kernel<<<g->N * a.tiles * a.ng, 256, lds, (hipStream_t)stream>>>(a);
-  return cat::check_launch("dwm_fwd");
+  dwm_fwd_kernel<M><<<g->N * a.tiles * a.ng, 256, lds, (hipStream_t)stream>>>(a);
+  return cat::check_launch(M == 2 ? "dwm_fwd" : "dwm7_fwd");
+}
+
+}  // namespace
+
+extern "C" {
+
+int cat_dwm_fwd(const cat_dwm_t* g, const float* x, const float* scale, const float* shift, const float* w25, const float* bias, float* y,
+                float* stats, cat_stream_t stream) {
+  return dwm_fwd_launch<2>(g, x, scale, shift, w25, bias, y, stats, stream);
+}
+
+int cat_dwm7_fwd(const cat_dwm_t* g, const float* x, const float* scale, const float* shift, const float* w49, const float* bias, float* y,
+                 float* stats, cat_stream_t stream) {
+  return dwm_fwd_launch<3>(g, x, scale, shift, w49, bias, y, stats, stream);
 }
 
 }  // extern "C"
@@ -563,6 +589,12 @@ __global__ __launch_bounds__(256) void prep_kernel(const cat_prep_job_t* __restr
     const int c = (int)(e / taps), tp = (int)(e - (int64_t)c * taps);
     const int ky = tp / J.ks, kx = tp - ky * J.ks, o = 2 - (J.ks >> 1);
     J.dst[((o + ky) * 5 + o + kx) * J.cs + J.col0 + c] = J.srcs[0][e];
+  } else if (J.kind == 5) {   // depthwise filter into the 7 x 7 frame (cat_dwm7_fwd / cat_dwm7_bwd)
+    const int taps = J.ks * J.ks;
+    if (e >= (int64_t)J.Nn * taps) return;
+    const int c = (int)(e / taps), tp = (int)(e - (int64_t)c * taps);
+    const int ky = tp / J.ks, kx = tp - ky * J.ks, o = 3 - (J.ks >> 1);
+    J.dst[((o + ky) * 7 + o + kx) * J.cs + J.col0 + c] = J.srcs[0][e];
   } else if (J.kind == 3) {   // scatter a slice of a concatenated gradient vector to its parameter
     if (e >= J.n) return;
     float* d = const_cast<float*>(J.srcs[1]);
@@ -608,34 +640,36 @@ struct DwmBwdArgs {
 };
 
 // dA of one pixel of one quad: (mirror position, ky, kx) order, the k x k loops fully unrolled
-template <int K>
+template <int M, int K>
 __device__ __forceinline__ f4 dwm_dgrad_taps(const f4* tz, const float* sw, const int* ys, int ny, const int* xs, int nx, int oy0, int ox0) {
-  constexpr int TR = TH + 4, TC = TW + 4, pd = K / 2, o = 2 - pd;
+  constexpr int TR = TH + 2 * M, TC = TW + 2 * M, pd = K / 2, o = M - pd;
   f4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int a = 0; a < ny; ++a)
     for (int b = 0; b < nx; ++b) {
       const int jy = ys[a], jx = xs[b];
 #pragma unroll
       for (int ky = 0; ky < K; ++ky) {
-        const int zy = jy + pd - ky - (oy0 - 2);          // row of dZ in the patch
+        const int zy = jy + pd - ky - (oy0 - M);          // row of dZ in the patch
         if ((unsigned)zy >= (unsigned)TR) continue;
 #pragma unroll
         for (int kx = 0; kx < K; ++kx) {
-          const int zx = jx + pd - kx - (ox0 - 2);
+          const int zx = jx + pd - kx - (ox0 - M);
           if ((unsigned)zx >= (unsigned)TC) continue;
-          acc += tz[zy * TC + zx] * *reinterpret_cast<const f4*>(sw + ((o + ky) * 5 + o + kx) * DWM_GCS);
+          acc += tz[zy * TC + zx] * *reinterpret_cast<const f4*>(sw + ((o + ky) * (2 * M + 1) + o + kx) * DWM_GCS);
         }
       }
     }
   return acc;
 }
 
+template <int M>
 __global__ __launch_bounds__(256) void dwm_bwd_kernel(DwmBwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int TR = TH + 4, TC = TW + 4, G = cat::kDwGroup;
-  f4* ta = reinterpret_cast<f4*>(smem);   // [G][DWM_PS]   input activation patch (reflect- or zero-padded), one plane per quad
-  f4* tz = ta + G * DWM_PS;               // [G][DWM_PS]   dZ patch (zero outside the plane)
-  float* sw = reinterpret_cast<float*>(tz + G * DWM_PS);      // [25][DWM_GCS]
+  constexpr int TR = TH + 2 * M, TC = TW + 2 * M, G = cat::kDwGroup, PS = DWM_PS<M>, FT = DWM_FT<M>, FS = 2 * M + 1;
+  static_assert(FT * G <= 256, "one thread per (tap, quad) of a group's filter gradient");
+  f4* ta = reinterpret_cast<f4*>(smem);   // [G][PS]   input activation patch (reflect- or zero-padded), one plane per quad
+  f4* tz = ta + G * PS;                   // [G][PS]   dZ patch (zero outside the plane)
+  float* sw = reinterpret_cast<float*>(tz + G * PS);      // [FT][DWM_GCS]
   const int tid = threadIdx.x;
   int tt, grp;
   cat::dw_tile_group(blockIdx.x, p.N * p.tiles, p.ng, tt, grp);
@@ -643,7 +677,7 @@ __global__ __launch_bounds__(256) void dwm_bwd_kernel(DwmBwdArgs p) {
   const int n = tt / p.tiles, t = tt - n * p.tiles;
   const int oy0 = (t / p.tiles_x) * TH, ox0 = (t % p.tiles_x) * TW;
   const int cs = p.nq * 4;
-  for (int i = tid; i < 25 * gn; i += 256) {
+  for (int i = tid; i < FT * gn; i += 256) {
     const int tap = i / gn, ql = i - tap * gn;
     *reinterpret_cast<f4*>(sw + tap * DWM_GCS + ql * 4) = *reinterpret_cast<const f4*>(p.w + tap * cs + (q0 + ql) * 4);
   }
@@ -657,7 +691,7 @@ __global__ __launch_bounds__(256) void dwm_bwd_kernel(DwmBwdArgs p) {
     if (i < TR * TC * gn) {
       const int pix = i / gn, q = q0 + i - pix * gn;
       const int r = pix / TC, c = pix - r * TC;
-      const int iy = oy0 - 2 + r, ix = ox0 - 2 + c;
+      const int iy = oy0 - M + r, ix = ox0 - M + c;
       const bool in = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
       if (in) zv[it] = *reinterpret_cast<const f4*>(p.dz + (((int64_t)n * p.H + iy) * p.W + ix) * p.zcs + q * 4);
       int ay = iy, ax = ix;
@@ -675,8 +709,8 @@ __global__ __launch_bounds__(256) void dwm_bwd_kernel(DwmBwdArgs p) {
     const int i = tid + it * 256;
     if (i < TR * TC * gn) {
       const int pix = i / gn, ql = i - pix * gn;
-      tz[ql * DWM_PS + pix] = zv[it];
-      ta[ql * DWM_PS + pix] = av[it];
+      tz[ql * PS + pix] = zv[it];
+      ta[ql * PS + pix] = av[it];
     }
   }
   __syncthreads();
@@ -699,37 +733,38 @@ __global__ __launch_bounds__(256) void dwm_bwd_kernel(DwmBwdArgs p) {
       }
       for (int ql = half; ql < gn; ql += 2) {
         f4 acc;
-        if (ks == 5) acc = dwm_dgrad_taps<5>(tz + ql * DWM_PS, sw + ql * 4, ys, ny, xs, nx, oy0, ox0);
-        else if (ks == 3) acc = dwm_dgrad_taps<3>(tz + ql * DWM_PS, sw + ql * 4, ys, ny, xs, nx, oy0, ox0);
-        else acc = dwm_dgrad_taps<1>(tz + ql * DWM_PS, sw + ql * 4, ys, ny, xs, nx, oy0, ox0);
+        if (M >= 3 && ks == 7) acc = dwm_dgrad_taps<M, M >= 3 ? 7 : 5>(tz + ql * PS, sw + ql * 4, ys, ny, xs, nx, oy0, ox0);
+        else if (ks == 5) acc = dwm_dgrad_taps<M, 5>(tz + ql * PS, sw + ql * 4, ys, ny, xs, nx, oy0, ox0);
+        else if (ks == 3) acc = dwm_dgrad_taps<M, 3>(tz + ql * PS, sw + ql * 4, ys, ny, xs, nx, oy0, ox0);
+        else acc = dwm_dgrad_taps<M, 1>(tz + ql * PS, sw + ql * 4, ys, ny, xs, nx, oy0, ox0);
         *reinterpret_cast<f4*>(p.da + (((int64_t)n * p.H + iy) * p.W + ix) * p.dacs + (q0 + ql) * 4) = acc;
       }
     }
   }
-  // ---- filter gradient partials of the tile: [25][cs] frame, zero outside the k x k window.  Work item = (tap of the window, quad), summed
+  // ---- filter gradient partials of the tile: [FT][cs] frame, zero outside the k x k window.  Work item = (tap of the window, quad), summed
   // over the tile's output pixels in row-major order by ONE thread: the sum of a (tap, channel) keeps the order it always had, whatever the
   // grouping (a training step's parameters stay bit-comparable).  The 16 columns of a row are unrolled: their 32 LDS reads are in flight
   // together, and the other workgroups of the CU cover the dependent adds
-  float* part = p.part + (int64_t)tt * 25 * cs;
-  const int o = 2 - (ks >> 1), items = ks * ks * gn;
-  for (int i = tid; i < 25 * gn; i += 256) {
+  float* part = p.part + (int64_t)tt * FT * cs;
+  const int o = M - (ks >> 1), items = ks * ks * gn;
+  for (int i = tid; i < FT * gn; i += 256) {
     const int tap = i / gn, ql = i - tap * gn;
-    const int fy = tap / 5, fx = tap - fy * 5;
+    const int fy = tap / FS, fx = tap - fy * FS;
     if (fy < o || fy >= o + ks || fx < o || fx >= o + ks) *reinterpret_cast<f4*>(part + tap * cs + (q0 + ql) * 4) = f4{0.f, 0.f, 0.f, 0.f};
   }
   if (tid < items) {
     const int wt = tid / gn, ql = tid - wt * gn;
     const int fy = o + wt / ks, fx = o + wt % ks;           // frame coordinates; the filter occupies [o, o + ks)
     const int nrow = min(TH, p.H - oy0), ncol = min(TW, p.W - ox0);
-    const f4* zq = tz + ql * DWM_PS + 2 * TC + 2;
-    const f4* aq = ta + ql * DWM_PS + fy * TC + fx;
+    const f4* zq = tz + ql * PS + M * TC + M;
+    const f4* aq = ta + ql * PS + fy * TC + fx;
     f4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int py = 0; py < nrow; ++py) {
 #pragma unroll
       for (int pxx = 0; pxx < TW; ++pxx)
         if (pxx < ncol) acc += zq[py * TC + pxx] * aq[py * TC + pxx];
     }
-    *reinterpret_cast<f4*>(part + (fy * 5 + fx) * cs + (q0 + ql) * 4) = acc;
+    *reinterpret_cast<f4*>(part + (fy * FS + fx) * cs + (q0 + ql) * 4) = acc;
   }
 }
 
@@ -740,33 +775,35 @@ struct DwmFinArgs {
 };
 
 // dst_b[c][ky][kx] (+)= sum over tiles of part[tile][frame tap][c0_b + c]
+template <int M>
 __global__ __launch_bounds__(256) void dwm_wgrad_final_kernel(const float* __restrict__ part, int ntiles, int cs, DwmFinArgs fa, int accumulate) {
+  constexpr int FS = 2 * M + 1;
   const int b = blockIdx.y;
-  const int ks = fa.ks[b], taps = ks * ks, o = 2 - (ks >> 1);
+  const int ks = fa.ks[b], taps = ks * ks, o = M - (ks >> 1);
   const int e = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;      // one wave per (channel, tap)
   if (e >= fa.c[b] * taps) return;
   const int c = e / taps, tp = e - c * taps;
   const int ky = tp / ks, kx = tp - ky * ks;
-  const float* src = part + ((o + ky) * 5 + o + kx) * cs + fa.c0[b] + c;
+  const float* src = part + ((o + ky) * FS + o + kx) * cs + fa.c0[b] + c;
   float s = 0.f;
-  for (int t = lane; t < ntiles; t += 64) s += src[(int64_t)t * 25 * cs];
+  for (int t = lane; t < ntiles; t += 64) s += src[(int64_t)t * FS * FS * cs];
   s = cat::wave_sum(s);
   if (lane == 0) fa.dst[b][e] = accumulate ? fa.dst[b][e] + s : s;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t cat_dwm_bwd_ws_bytes(const cat_dwm_t* g) {
-  return (size_t)g->N * cdiv(g->H, TH) * cdiv(g->W, TW) * 25 * g->nq * 4 * sizeof(float);
+template <int M>
+size_t dwm_bwd_ws(const cat_dwm_t* g) {
+  return (size_t)g->N * cdiv(g->H, TH) * cdiv(g->W, TW) * DWM_FT<M> * g->nq * 4 * sizeof(float);
 }
 
-int cat_dwm_bwd(const cat_dwm_t* g, const float* a, const float* dz, const float* w25, float* da, int dacs, int nbranch, const int* c0,
-                const int* c, const int* ks, float* const* dw, int accumulate, void* ws, cat_stream_t stream) {
+// M = 2: cat_dwm_bwd; M = 3: cat_dwm7_bwd
+template <int M>
+int dwm_bwd_launch(const cat_dwm_t* g, const float* a, const float* dz, const float* w25, float* da, int dacs, int nbranch, const int* c0,
+                   const int* c, const int* ks, float* const* dw, int accumulate, void* ws, cat_stream_t stream) {
   CAT_REQUIRE(g->nq >= 1 && g->nq <= CAT_DWM_MAXQ_BWD && nbranch >= 1 && nbranch <= CAT_TNORM_MAXSLICE && ws, "dwm bwd: bad arguments");
   CAT_REQUIRE((g->xcs & 3) == 0 && (g->ycs & 3) == 0 && (dacs & 3) == 0 && g->xcs >= 4 * g->nq && g->ycs >= 4 * g->nq && dacs >= 4 * g->nq,
               "dwm bwd: channel layout");
+  CAT_REQUIRE(M == 2 || !g->reflect || (g->H > M && g->W > M), "dwm bwd: reflect padding wider than the plane");
   DwmBwdArgs p{};
   p.a = a; p.dz = dz; p.w = w25; p.da = da; p.part = (float*)ws;
   p.acs = g->xcs; p.zcs = g->ycs; p.dacs = dacs;
@@ -775,22 +812,23 @@ int cat_dwm_bwd(const cat_dwm_t* g, const float* a, const float* dz, const float
   p.tiles = p.tiles_x * cdiv(g->H, TH);
   double taps = 0.0;
   for (int q = 0; q < g->nq; ++q) {
-    CAT_REQUIRE(g->ks[q] == 1 || g->ks[q] == 3 || g->ks[q] == 5, "dwm bwd: kernel size %d", g->ks[q]);
+    CAT_REQUIRE(g->ks[q] == 1 || g->ks[q] == 3 || g->ks[q] == 5 || (M >= 3 && g->ks[q] == 7), "dwm bwd: kernel size %d", g->ks[q]);
     taps += 4.0 * g->ks[q] * g->ks[q];
   }
   p.ng = cat::dw_quad_groups(g->ks, g->nq, p.gq0, p.gnq);
   for (int k = 0; k < p.ng; ++k) p.gks[k] = (unsigned char)g->ks[p.gq0[k]];
   const int cs = g->nq * 4, ntiles = g->N * p.tiles;
-  constexpr size_t lds = (size_t)(2 * cat::kDwGroup * DWM_PS * 4 + 25 * DWM_GCS) * sizeof(float);
-  static_assert(4 * lds <= 160 * 1024 || cat::kDwGroup > 4, "dwm bwd: four workgroups per CU by LDS");
+  constexpr size_t lds = (size_t)(2 * cat::kDwGroup * DWM_PS<M> * 4 + DWM_FT<M> * DWM_GCS) * sizeof(float);
+  static_assert(M > 2 || 4 * lds <= 160 * 1024 || cat::kDwGroup > 4, "dwm bwd: four workgroups per CU by LDS");      // M = 3: 42.7 KB, three
+  static_assert(lds <= 160 * 1024, "dwm bwd: LDS");
   hipStream_t s = (hipStream_t)stream;
   cat::ProfScope prof("dwconv_bwd", 4.0 * (double)g->N * g->H * g->W * taps, 0.0, stream);
   if (lds > 64 * 1024) {
     static cat::LdsOptIn optin;
-    cat::lds_optin(optin, (const void*)dwm_bwd_kernel, (int)lds);
+    cat::lds_optin(optin, (const void*)dwm_bwd_kernel<M>, (int)lds);
   }
-  dwm_bwd_kernel<<<ntiles * p.ng, 256, lds, s>>>(p);
-  if (int e = cat::check_launch("dwm_bwd")) return e;
+  dwm_bwd_kernel<M><<<ntiles * p.ng, 256, lds, s>>>(p);
+  if (int e = cat::check_launch(M == 2 ? "dwm_bwd" : "dwm7_bwd")) return e;
   DwmFinArgs fa{};
   fa.nbr = nbranch;
   int maxe = 0;
@@ -798,8 +836,26 @@ int cat_dwm_bwd(const cat_dwm_t* g, const float* a, const float* dz, const float
     fa.dst[b] = dw[b]; fa.c0[b] = c0[b]; fa.c[b] = c[b]; fa.ks[b] = ks[b];
     maxe = c[b] * ks[b] * ks[b] > maxe ? c[b] * ks[b] * ks[b] : maxe;
   }
-  dwm_wgrad_final_kernel<<<dim3(cdiv(maxe, 4), nbranch), 256, 0, s>>>((const float*)ws, ntiles, cs, fa, accumulate);
+  dwm_wgrad_final_kernel<M><<<dim3(cdiv(maxe, 4), nbranch), 256, 0, s>>>((const float*)ws, ntiles, cs, fa, accumulate);
   return cat::check_launch("dwm_wgrad_final");
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t cat_dwm_bwd_ws_bytes(const cat_dwm_t* g) { return dwm_bwd_ws<2>(g); }
+
+int cat_dwm_bwd(const cat_dwm_t* g, const float* a, const float* dz, const float* w25, float* da, int dacs, int nbranch, const int* c0,
+                const int* c, const int* ks, float* const* dw, int accumulate, void* ws, cat_stream_t stream) {
+  return dwm_bwd_launch<2>(g, a, dz, w25, da, dacs, nbranch, c0, c, ks, dw, accumulate, ws, stream);
+}
+
+size_t cat_dwm7_bwd_ws_bytes(const cat_dwm_t* g) { return dwm_bwd_ws<3>(g); }
+
+int cat_dwm7_bwd(const cat_dwm_t* g, const float* a, const float* dz, const float* w49, float* da, int dacs, int nbranch, const int* c0,
+                 const int* c, const int* ks, float* const* dw, int accumulate, void* ws, cat_stream_t stream) {
+  return dwm_bwd_launch<3>(g, a, dz, w49, da, dacs, nbranch, c0, c, ks, dw, accumulate, ws, stream);
 }
 
 }  // extern "C"

@@ -8,6 +8,19 @@ namespace cat_pk {
 
 constexpr int TH = 8, PITCH = 20, TABN = 128;
 
+// launch geometry of tconv_kernel (conv_pk.hip) and tconv7_kernel (conv_pk7.hip); their shared body is conv_pk_tconv_main.h
+struct Launch {
+  int hl, tr, tc;          // halo (left / top), staged rows / columns
+  int tiles_x, tiles;      // output tiles per row / per image
+  int nt_total, nblk;      // 16-wide N tiles of the output, N blocks (gridDim.x = N * tiles * nblk)
+  int ablate;              // DIAGNOSTIC BUILD ONLY (cat::kDiag; CAT_PK_ABLATE, results become wrong): 1 every group reads the SAME filter block
+                           // (L1 hits), 2 every A fragment reads LDS offset 0, 4 staging loads hit one cached line, 8 no staging / barrier after
+                           // the first chunk.  The production kernels read `abl`, a compile-time 0
+};
+
+// cat_tconv_fwd launches that need the wider patch (a 7 x 7 segment, or hl + hr > 4): conv_pk7.hip
+int tconv7_launch(const cat_tconv_t* g, const float* pack, const float* bias, float* y, cat_stream_t stream);
+
 __device__ __forceinline__ f4 bload(const __amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff_) {
   const auto r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff_, 0);
   static_assert(sizeof(r) == sizeof(f4), "buffer load width");

@@ -8,7 +8,8 @@ x 3, add_n, ...), most of them a few microseconds of HBM-bound work between depe
     stage 1   one LDS-tile conv launch per first-conv kernel size (the 1x1 convs of all branches as ONE N-concatenated GEMM) writing
               channel slices of one pre-norm buffer Z1 and the per-tile statistics of every branch           (cat_tconv_fwd + stats)
     finalize  scale / shift of all stage-1 norms + their running statistics                                   (cat_tnorm_finalize)
-    dw        all depthwise convs as one launch; normalise + ReLU of stage 1 applied while staging            (cat_dwm_fwd)
+    dw        all depthwise convs as one launch; normalise + ReLU of stage 1 applied while staging            (cat_dwm_fwd; cat_dwm7_fwd
+              when a depthwise branch is 7 x 7: kernel sizes from {1, 3, 5, 7}, CAT_FUSED_K7)
     finalize
     stage 2   the branch sum: six second convs K-concatenated into one launch, normalise + ReLU applied while staging, output
               written once, statistics for pw_bn                                                              (cat_tconv_fwd)
@@ -42,6 +43,11 @@ _ENABLED = os.environ.get('CAT_FUSED_BLOCK', '1') != '0'
 # Off by default (such blocks run layer by layer, as they always did): the graphed CycleGAN teacher step at batch 4 measured 134.1 ms on
 # this path against 126.1 ms layer by layer; launched eagerly it is 146.8 against 207.5 ms (profiles/wide_block_bench.txt)
 _WIDE = os.environ.get('CAT_FUSED_WIDE', '0') != '0'
+# Blocks with a 7 x 7 branch (the reference's parser default --kernel_sizes 3 5 7) take this path unless CAT_FUSED_K7=0 / set_k7(False): their
+# 7 x 7 convs on the wide-patch LDS-tile kernels (csrc/conv_pk7.hip), their depthwise stage on the 7 x 7 frame (cat_dwm7_fwd / cat_dwm7_bwd).
+# With it off such blocks run layer by layer, as they always did.  On by default: the graphed pix2pix distillation step with kernel sizes
+# 3 5 7 at batch 16 measured 64.05 ms on this path against 71.58 ms layer by layer, spread 0.17 ms (profiles/k7_block_bench.txt)
+_K7 = os.environ.get('CAT_FUSED_K7', '1') != '0'
 # Per-block opt-in to this path in eval() mode: cat_amd.infer.StudentRunner registers the blocks of the network it owns.  An InstanceNorm2d
 # without running statistics computes the same function in eval() as in train(), so forward(block, x, save=None) is the block's eval
 # forward as it stands: per-sample statistics collected and finalized, no running statistics to touch (fused_unit.slices passes none).
@@ -66,6 +72,12 @@ def eval_owned(block):
 def set_enabled(on):
     global _ENABLED
     _ENABLED = bool(on)
+
+
+def set_k7(on):
+    global _K7
+    old, _K7 = _K7, bool(on)
+    return old
 
 
 def set_wide(on):
@@ -121,7 +133,7 @@ def applicable(block, x):
     if cnn._act_code(first_act)[0] not in (L.ACT_RELU, L.ACT_LRELU):     # the staging paths apply ReLU / LeakyReLU only (nn.ReLU6: general path)
         return False
     ks = [op[1][0].kernel_size[0] for op in block.res_ops] + [op[2][0].kernel_size[0] for op in block.dw_ops]
-    if any(k not in (1, 3, 5) for k in ks):
+    if any(k not in ((1, 3, 5, 7) if _K7 else (1, 3, 5)) for k in ks):
         return False
     if len(block.res_ops) + len(block.dw_ops) > L.TCONV_MAXSEG:
         return False

@@ -2,7 +2,8 @@
 
     stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tstage1ws_fwd / cat_tconv_fwd)
     finalize  scale / shift of all stage-1 norms + their running statistics                               (cat_tnorm_finalize)
-    dw        all depthwise convs (one launch per <= 18 / 24 channel quads), norm + activation of stage 1 applied while staging   (cat_dwm_fwd)
+    dw        all depthwise convs (one launch per <= 18 / 24 channel quads), norm + activation of stage 1 applied while staging   (cat_dwm_fwd;
+              cat_dwm7_fwd for a plan with a 7 x 7 depthwise branch)
     finalize
     stage 2   the branch sum: the second convs K-concatenated, norm + activation applied while staging   (cat_tconv_fwd)
 
@@ -108,9 +109,10 @@ class Plan:
         self.params = params
         self.Cin, self.csi = cin, cs4(cin)
         self.Cout, self.cso = cout, cs4(cout)
-        # stage-1 channel order: [res k=1 | dw ... | res k=3 | res k=5] so that same-kernel first convs are adjacent (N concat) and the
-        # depthwise inputs are one contiguous slice range
-        order = [b for b in res if b['k'] == 1] + dws + [b for b in res if b['k'] == 3] + [b for b in res if b['k'] == 5]
+        # stage-1 channel order: [res k=1 | dw ... | res k=3 | res k=5 | res k=7] so that same-kernel first convs are adjacent (N concat) and
+        # the depthwise inputs are one contiguous slice range
+        order = [b for b in res if b['k'] == 1] + dws + [b for b in res if b['k'] == 3] + [b for b in res if b['k'] == 5] + \
+                [b for b in res if b['k'] == 7]
         off = 0
         for b in order:
             b['o1'], b['w1'] = off, cs4(b['m'])
@@ -123,9 +125,15 @@ class Plan:
         self.hcd = off
         self.dw_in0 = dws[0]['o1'] if dws else 0
         # depthwise launches: branch-aligned groups of at most dw_maxq quads, ONE grouping for both directions of a training plan (the
-        # backward one; a forward-only plan may ask for CAT_DWM_MAXQ).  Each launch reads its own contiguous 5 x 5 filter frame
-        # [25][launch width] at float offset 25 * (its first channel) of w25 -- one launch: the frame [25][hcd] at offset 0.  A branch wider
-        # than a launch is refused by the callers' `applicable`; such a plan keeps one launch, which the kernel refuses
+        # backward one; a forward-only plan may ask for CAT_DWM_MAXQ).  Each launch reads its own contiguous filter frame
+        # [ft][launch width] at float offset ft * (its first channel) of w25 -- one launch: the frame [ft][hcd] at offset 0.  A branch wider
+        # than a launch is refused by the callers' `applicable`; such a plan keeps one launch, which the kernel refuses.
+        # ONE frame side per plan: 5 (ft = 25; cat_dwm_fwd / cat_dwm_bwd), or 7 (ft = 49; cat_dwm7_fwd / cat_dwm7_bwd) iff some depthwise
+        # branch is 7 x 7 -- a plan within {1, 3, 5} builds the buffers and issues the calls it always has
+        self.fs = 7 if any(b['kd'] == 7 for b in dws) else 5
+        self.ft = self.fs * self.fs
+        self.dw_fwd_entry, self.dw_bwd_entry, self.dw_ws_entry, self.dw_prep_kind = \
+            ('cat_dwm_fwd', 'cat_dwm_bwd', 'cat_dwm_bwd_ws_bytes', 2) if self.fs == 5 else ('cat_dwm7_fwd', 'cat_dwm7_bwd', 'cat_dwm7_bwd_ws_bytes', 5)
         self.dw_maxq = dw_maxq
         spans = dw_launches([cs4(b['m']) // 4 for b in dws], dw_maxq) or ([(0, len(dws))] if dws else [])
         self.dw_spans = tuple(spans)
@@ -136,7 +144,7 @@ class Plan:
         self.branches, self.res, self.dws = order, res, dws
         # stage-1 launches: one per first-conv kernel size
         self.groups = []
-        for k in (1, 3, 5):
+        for k in (1, 3, 5, 7):
             bs = [b for b in order if b['k'] == k]
             if bs:
                 g0, g1 = bs[0]['o1'], bs[-1]['o1'] + bs[-1]['w1']
@@ -148,7 +156,7 @@ class Plan:
         self.gamma1, self.beta1, self.bias1 = z(self.hc1, self.GAMMA0), z(self.hc1), z(self.hc1)
         self.gammad, self.betad, self.biasd = z(self.hcd, self.GAMMA0), z(self.hcd), z(self.hcd)
         self.bias2 = z(self.cso)
-        self.w25 = z(25 * max(self.hcd, 4))
+        self.w25 = z(self.ft * max(self.hcd, 4))
         self.has_bias1 = any(b['conv1'].bias is not None for b in order)
         self.has_biasd = any(b['dconv'].bias is not None for b in dws)
         self.has_bias2 = any(b['conv2'].bias is not None for b in order)
@@ -274,7 +282,8 @@ class Plan:
             wd = b['dconv'].weight
             if not wd.is_contiguous():
                 raise RuntimeError(f'{self.what}: depthwise weights must be contiguous')
-            fwd.append(dict(kind=2, srcs=[wd.data_ptr()], dst=self.w25.data_ptr() + 4 * 25 * b['f0'], Nn=b['m'], ks=kd, col0=b['od'] - b['f0'], cs=b['fcs'], threads=b['m'] * kd * kd))
+            fwd.append(dict(kind=self.dw_prep_kind, srcs=[wd.data_ptr()], dst=self.w25.data_ptr() + 4 * self.ft * b['f0'], Nn=b['m'], ks=kd,
+                            col0=b['od'] - b['f0'], cs=b['fcs'], threads=b['m'] * kd * kd))
         b2 = [b['conv2'].bias for b in self.branches if b['conv2'].bias is not None]
         if b2:
             fwd.append(vec(self.bias2, 0, b2, self.Cout))
@@ -365,10 +374,11 @@ def prepare_plans(plans, group, backward=False):
 # ---------------------------------------------------------------------------------------------------------------- forward stages
 def stage1(p, x, z1, part1, reflect=False):
     """First convs of all branches: x -> channel slices of Z1 (pre-norm) + tile statistics into part1.  part1 None: the eval form, no
-    statistics (always one launch per kernel size)."""
+    statistics (always one launch per kernel size).  The one-launch kernels take exactly the kernel sizes 5, 3 and 1: a plan with another
+    set (a 7 x 7 first conv, or fewer sizes) runs one launch per size."""
     n, c, h, w = x.shape
     by_k = {g['k']: g for g in p.groups}
-    widths = [by_k[k]['width'] for k in (5, 3, 1)] if part1 is not None and len(p.groups) == 3 else None
+    widths = [by_k[k]['width'] for k in (5, 3, 1)] if part1 is not None and set(by_k) == {1, 3, 5} else None
     entry = None
     if widths is not None and L.query('cat_tstage1_supported', *widths):
         entry = 'cat_tstage1_fwd'
@@ -415,7 +425,7 @@ def dwm_fwd(p, z1, scale, shift, zd, partd, reflect=False, per_sample=False):
         gd = dwm_geom(p, n, h, w, reflect, group)
         gd.sstride, gd.act, gd.slope = (p.hc1 if per_sample else 0), p.act, p.slope
         i = p.dw_in0 + o
-        L.call('cat_dwm_fwd', C.byref(gd), at(z1, i), at(scale, i), at(shift, i), at(p.w25, 25 * o), at(p.biasd, o) if p.has_biasd else None,
+        L.call(p.dw_fwd_entry, C.byref(gd), at(z1, i), at(scale, i), at(shift, i), at(p.w25, p.ft * o), at(p.biasd, o) if p.has_biasd else None,
                at(zd, o), at(partd, o) if partd is not None else None, ops._stream())
 
 
@@ -636,8 +646,8 @@ def dw_bwd(p, a1, da1, dzd, grads, reflect=False):
         nb = len(bs)
         gd = dwm_geom(p, n, h, w, reflect, group)
         IA = C.c_int * nb
-        wsd = ops.workspace(L.query('cat_dwm_bwd_ws_bytes', C.byref(gd)), a1.device)
-        L.call('cat_dwm_bwd', C.byref(gd), at(a1, p.dw_in0 + o), at(dzd, o), at(p.w25, 25 * o), at(da1, p.dw_in0 + o), p.hc1, nb,
+        wsd = ops.workspace(L.query(p.dw_ws_entry, C.byref(gd)), a1.device)
+        L.call(p.dw_bwd_entry, C.byref(gd), at(a1, p.dw_in0 + o), at(dzd, o), at(p.w25, p.ft * o), at(da1, p.dw_in0 + o), p.hc1, nb,
                IA(*[b['od'] - o for b in bs]), IA(*[b['m'] for b in bs]), IA(*[b['kd'] for b in bs]),
                (C.c_void_p * nb)(*[dst_of[id(b)].data_ptr() for b in bs]), acc_dw, ops._p(wsd), ops._stream())
     for q, d_ in zip(wts, dsts):          # not all owned (tests): fresh tensors, copied / added into the views of those that are

@@ -400,7 +400,8 @@ int cat_spectral_norm_bwd(const float* gw, const float* w_sn, const float* u, co
                           int O, int taps, int wcs, float* dw, int accumulate, void* ws, cat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
- * LDS-tile convolution with pre-packed filters, stride 1, k in {1,3,5} (csrc/conv_pk.hip):
+ * LDS-tile convolution with pre-packed filters, stride 1, k in {1,3,5,7} (csrc/conv_pk.hip; csrc/conv_pk7.hip for launches with a 7 x 7
+ * segment or taps more than 4 pixels apart):
  *   out[n][oy][ox][co] = act(bias[co] + sum_s sum_(ky,kx) sum_c f_s(src_s[n][oy-padv_s+ky][ox-padv_s+kx][c]) * W_s(tap,c,co))
  * One launch = a single nn.Conv2d (+ the nn.ReflectionPad2d in front of it), its input gradient, or the K-concatenated SUM of up to
  * 8 convolutions of different kernel sizes over different tensors: the branch sum of InvertedResidualChannels.forward
@@ -408,7 +409,10 @@ int cat_spectral_norm_bwd(const float* gw, const float* w_sn, const float* u, co
  * branches' first-conv input gradients.  f_s = optional per-channel affine + activation applied while the source tile is staged
  * (the normalise + ReLU of a train-mode norm_layer, inception_modules.py:43-44, folded into the conv that consumes it).
  * Filters are consumed from a packed stream (cat_tconv_pack) in the exact order of the kernel's MFMA groups; trainable layers
- * re-pack once per optimizer step. */
+ * re-pack once per optimizer step.
+ * Domain: ks in {1, 3, 5, 7}; 0 <= padv <= 6; hl + hr <= 6 with hl = max padv, hr = max (ks - 1 - padv) over the segments; reflect needs
+ * ks <= H, W.  A launch with every ks <= 5 and hl + hr <= 4 runs the (8 + 4) x (TW + 4) patch kernels (TW = 16 or 32), every other one the
+ * (8 + 6) x (16 + 6) patch kernels.  Outside the domain the call returns non-zero and writes nothing. */
 #define CAT_TCONV_MAXSEG 8
 typedef struct {
   const float* src;    /* [N][H][W][xcs], pointing at the segment's first channel (a channel slice of a wider buffer is fine) */
@@ -564,13 +568,22 @@ int cat_dwm_fwd(const cat_dwm_t* g, const float* x, const float* scale, const fl
 size_t cat_dwm_bwd_ws_bytes(const cat_dwm_t* g);
 int cat_dwm_bwd(const cat_dwm_t* g, const float* a, const float* dz, const float* w25, float* da, int dacs, int nbranch, const int* c0,
                 const int* c, const int* ks, float* const* dw, int accumulate, void* ws, cat_stream_t stream);
+/* The same stage with k = 1 / 3 / 5 / 7 per channel quad (the reference's default --kernel_sizes 3 5 7): arguments as above, but the filters
+ * lie in a 7 x 7 frame w49 = [49][4*nq] -- tap (ky, kx) of a k x k filter at row (ky + 3 - k/2) * 7 + kx + 3 - k/2 (cat_prep_run kind 5) --
+ * the staged patch is (8 + 6) x (16 + 6), reflect padding needs H, W > 3, and the workspace holds 49 floats per tap frame. */
+int cat_dwm7_fwd(const cat_dwm_t* g, const float* x, const float* scale, const float* shift, const float* w49, const float* bias, float* y,
+                 float* stats, cat_stream_t stream);
+size_t cat_dwm7_bwd_ws_bytes(const cat_dwm_t* g);
+int cat_dwm7_bwd(const cat_dwm_t* g, const float* a, const float* dz, const float* w49, float* da, int dacs, int nbranch, const int* c0,
+                 const int* c, const int* ks, float* const* dw, int accumulate, void* ws, cat_stream_t stream);
 /* Per-step preparation of a block's operands in ONE launch, driven by a job table resident in HBM (built once per network):
  *   kind 0  pack a conv weight for cat_tconv_fwd into columns [col0, col0 + Nn) of a stream with nt_total 16-wide N tiles (N-concatenated
  *           first convs; mode as cat_tconv_pack)
  *   kind 1  dst[i] = sum_k srcs[k][i], i < n     (concatenated gamma / beta / bias vectors; the summed bias of the branch sum)
  *   kind 2  depthwise filter [C][ks][ks] -> dst[tap25][cs] 5 x 5 frame, channels [col0, col0 + C)
  *   kind 3  srcs[1][i] (+)= srcs[0][i], i < n     (scatter a concatenated parameter gradient back; accumulate = cat_prep_run's flag)
- *   kind 4  srcs[1][r*wcs + i] (+)= srcs[0][r*wn + i], i < cs, r < n / cs   (columns of a K-concatenated weight gradient) */
+ *   kind 4  srcs[1][r*wcs + i] (+)= srcs[0][r*wn + i], i < cs, r < n / cs   (columns of a K-concatenated weight gradient)
+ *   kind 5  depthwise filter [C][ks][ks] -> dst[tap49][cs] 7 x 7 frame, channels [col0, col0 + C)   (cat_dwm7_fwd / cat_dwm7_bwd) */
 #define CAT_PREP_MAXSRC 8
 typedef struct {
   const float* srcs[CAT_PREP_MAXSRC];
