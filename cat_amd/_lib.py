@@ -104,6 +104,10 @@ class Stage1WGeom(C.Structure):
     _fields_ = [(n, c_i) for n in ('N', 'H', 'W', 'xcs', 'cin', 'reflect', 'act')] + [('slope', c_f), ('ycs', c_i * 3), ('nvalid', c_i * 3)]
 
 
+class Stage1W7Geom(C.Structure):
+    _fields_ = [(n, c_i) for n in ('N', 'H', 'W', 'xcs', 'cin', 'reflect', 'act')] + [('slope', c_f), ('ycs', c_i * 4), ('nvalid', c_i * 4)]
+
+
 class DwmGeom(C.Structure):
     _fields_ = [(n, c_i) for n in ('N', 'H', 'W', 'nq', 'xcs', 'ycs', 'scs', 'sstride', 'reflect', 'act')] + [('slope', c_f), ('ks', c_i * DWM_MAXQ)]
 
@@ -215,6 +219,8 @@ SIGNATURES = {
     'cat_tstage1_dgrad_supported': (c_i, [c_i, c_i, c_i]),
     'cat_tstage1w_supported': (c_i, [c_i, c_i, c_i]),
     'cat_tstage1w_fwd': (c_i, [C.POINTER(Stage1WGeom), c_p, c_p, c_p, c_p, c_p]),
+    'cat_tstage1w7_supported': (c_i, [c_i, c_i, c_i, c_i]),
+    'cat_tstage1w7_fwd': (c_i, [C.POINTER(Stage1W7Geom), c_p, c_p, c_p, c_p, c_p]),
     'cat_tstage1ws_supported': (c_i, [c_i, c_i, c_i]),
     'cat_tstage1ws_fwd': (c_i, [C.POINTER(Stage1Geom), c_p, c_p, c_p, c_p, c_p, c_p]),
     'cat_tstage1_dgrad': (c_i, [C.POINTER(Stage1Geom), c_p, c_p, c_p, c_p, c_p]),
@@ -238,6 +244,7 @@ SIGNATURES = {
     'cat_prep_run': (c_i, [c_p, c_i, c_i, c_i, c_p]),
     'cat_dwconv2d_fwd': (c_i, [_G, c_p, c_p, c_p, c_p, c_p]),
     'cat_dwconv2d_multi_fwd': (c_i, [C.POINTER(DwMulti), c_p, c_p, c_p, c_p, c_p]),
+    'cat_dwconv2d_multi7_fwd': (c_i, [C.POINTER(DwMulti), c_p, c_p, c_p, c_p, c_p]),
     'cat_dwconv2d_dgrad': (c_i, [_G, c_p, c_p, c_p, c_i, c_p]),
     'cat_dwconv2d_wgrad': (c_i, [_G, c_p, c_p, c_p, c_i, c_p, c_p]),
     'cat_dwconv2d_wgrad_ws_bytes': (C.c_size_t, [_G]),

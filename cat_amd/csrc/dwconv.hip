@@ -71,6 +71,8 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(DwArgs p) {
 // residual branch's hidden slice, were four launches of 10 - 32 us over the same 176-channel buffers).  Per channel quad a kernel size
 // k in {1, 3, 5}; the filters sit in a 5 x 5 frame [25][cs] (k < 5: centred, the rest zero -- only the k x k window is read), a quad that is
 // merely copied carries k = 1, centre weight 1, bias 0.  Lane = (pixel, quad): a pixel's quads are consecutive lanes (one coalesced row).
+// The kernels are templates on the frame side F: F = 5 is what is described here (cat_dwconv2d_multi_fwd), F = 7 serves cat_dwconv2d_multi7_fwd --
+// k in {1, 3, 5, 7}, a 7 x 7 frame [49][cs], the teacher of a distillation with the reference's default kernel sizes 3 5 7.
 // cat_dwconv2d_multi_fwd launches this 1-D walk for planes of fewer than DW_MULTI_TILE_MIN_WG tile workgroups (and under CAT_DWMULTI_TILE=0);
 // larger planes go to dw_multi_tile_kernel below.
 struct DwMultiArgs {
@@ -86,9 +88,10 @@ struct DwMultiArgs {
 
 __device__ __attribute__((aligned(16))) float g_zero[4] = {0.f, 0.f, 0.f, 0.f};      // global (not constant) address space: the loads stay global_load
 
-template <int K>
+// F: side of the filter frame (5: cat_dwconv2d_multi_fwd; 7: cat_dwconv2d_multi7_fwd), K <= F
+template <int K, int F>
 __device__ __forceinline__ f4 dw_multi_taps(const DwMultiArgs& p, const float* sw, const float* xn, int oy, int ox, int c, int cs, f4 acc) {
-  constexpr int R = K / 2, O = 2 - R;
+  constexpr int R = K / 2, O = F / 2 - R;
   int64_t offy[K];
   int offx[K];
   bool vy[K], vx[K];
@@ -112,19 +115,21 @@ __device__ __forceinline__ f4 dw_multi_taps(const DwMultiArgs& p, const float* s
   for (int ky = 0; ky < K; ++ky)
 #pragma unroll
     for (int kx = 0; kx < K; ++kx) {
-      const f4 wv = *reinterpret_cast<const f4*>(sw + ((O + ky) * 5 + O + kx) * cs + c);
+      const f4 wv = *reinterpret_cast<const f4*>(sw + ((O + ky) * F + O + kx) * cs + c);
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[e] = fmaf(xv[ky][kx][e], wv[e], acc[e]);
     }
   return acc;
 }
 
+template <int F>
 __global__ __launch_bounds__(256) void dw_multi_fwd_kernel(DwMultiArgs p) {
-  extern __shared__ __attribute__((aligned(16))) float sw[];      // [25][cs] frame, then [cs] bias
+  extern __shared__ __attribute__((aligned(16))) float sw[];      // [F * F][cs] frame, then [cs] bias
+  constexpr int FT = F * F;
   const int cs = p.nq * 4;
-  for (int i = threadIdx.x; i < 25 * p.nq; i += 256) *reinterpret_cast<f4*>(sw + i * 4) = *reinterpret_cast<const f4*>(p.w25 + i * 4);
+  for (int i = threadIdx.x; i < FT * p.nq; i += 256) *reinterpret_cast<f4*>(sw + i * 4) = *reinterpret_cast<const f4*>(p.w25 + i * 4);
   for (int i = threadIdx.x; i < p.nq; i += 256)
-    *reinterpret_cast<f4*>(sw + 25 * cs + i * 4) = p.bias ? *reinterpret_cast<const f4*>(p.bias + i * 4) : f4{0.f, 0.f, 0.f, 0.f};
+    *reinterpret_cast<f4*>(sw + FT * cs + i * 4) = p.bias ? *reinterpret_cast<const f4*>(p.bias + i * 4) : f4{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
   const int64_t total = p.run_base[p.nrun];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -140,11 +145,12 @@ __global__ __launch_bounds__(256) void dw_multi_fwd_kernel(DwMultiArgs p) {
     const int oy = (int)(pix % p.H);
     const int n = (int)(pix / p.H);
     const int c = cq * 4;
-    f4 acc = *reinterpret_cast<const f4*>(sw + 25 * cs + c);
+    f4 acc = *reinterpret_cast<const f4*>(sw + FT * cs + c);
     const float* xn = p.x + (int64_t)n * p.H * p.W * p.xcs + c;
-    if (k == 1) acc = dw_multi_taps<1>(p, sw, xn, oy, ox, c, cs, acc);
-    else if (k == 3) acc = dw_multi_taps<3>(p, sw, xn, oy, ox, c, cs, acc);
-    else acc = dw_multi_taps<5>(p, sw, xn, oy, ox, c, cs, acc);
+    if (k == 1) acc = dw_multi_taps<1, F>(p, sw, xn, oy, ox, c, cs, acc);
+    else if (k == 3) acc = dw_multi_taps<3, F>(p, sw, xn, oy, ox, c, cs, acc);
+    else if (F == 5 || k == 5) acc = dw_multi_taps<5, F>(p, sw, xn, oy, ox, c, cs, acc);
+    else acc = dw_multi_taps<F, F>(p, sw, xn, oy, ox, c, cs, acc);
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[e] = cat::apply_act(acc[e], p.act, p.slope);
     *reinterpret_cast<f4*>(p.y + opix * p.ycs + c) = acc;
@@ -158,9 +164,10 @@ __global__ __launch_bounds__(256) void dw_multi_fwd_kernel(DwMultiArgs p) {
 // the epilogue, no statistics.  Thread = (pixel, quad parity within the group), as in the fused block's dwm_fwd_kernel.  Per output the
 // arithmetic is dw_multi_taps': bias, then fmaf over the taps in (ky, kx) order.
 constexpr int DWT_TH = 8, DWT_TW = 16;
-constexpr int DWT_PS = (DWT_TH + 4) * (DWT_TW + 4) + 2;      // f4 per quad plane: + 2 spreads the staging stores of a pixel's 4 quads over the banks
+// f4 per quad plane of a frame of side F (halo F - 1): + 2 spreads the staging stores of a pixel's 4 quads over the banks
+template <int F> constexpr int DWT_PS = (DWT_TH + F - 1) * (DWT_TW + F - 1) + 2;
 constexpr int DWT_GCS = cat::kDwGroup * 4;
-constexpr size_t DWT_LDS = (size_t)(cat::kDwGroup * DWT_PS * 4 + 26 * DWT_GCS) * sizeof(float);      // 17 KB at 4 quads
+template <int F> constexpr size_t DWT_LDS = (size_t)(cat::kDwGroup * DWT_PS<F> * 4 + (F * F + 1) * DWT_GCS) * sizeof(float);      // 17 KB at 4 quads, F = 5; 23 KB, F = 7
 
 struct DwTileArgs {
   const float* x; const float* w25; const float* bias; float* y;
@@ -170,9 +177,9 @@ struct DwTileArgs {
   unsigned char gq0[CAT_DWMULTI_MAXQ], gnq[CAT_DWMULTI_MAXQ], gks[CAT_DWMULTI_MAXQ];
 };
 
-template <int K>
+template <int K, int F>
 __device__ __forceinline__ void dw_multi_tile_body(const DwTileArgs& p, f4* tile, float* sw, int n, int oy0, int ox0, int q0, int gn) {
-  constexpr int R = K / 2, O = 2 - R, PR = DWT_TH + 2 * R, PC = DWT_TW + 2 * R, G = cat::kDwGroup;
+  constexpr int R = K / 2, O = F / 2 - R, PS = DWT_PS<F>, PR = DWT_TH + 2 * R, PC = DWT_TW + 2 * R, G = cat::kDwGroup;
   const int tid = threadIdx.x;
   constexpr int SIT = (PR * PC * G + 255) / 256;      // all of the thread's loads in flight before the first LDS store
   f4 xv[SIT];
@@ -198,7 +205,7 @@ __device__ __forceinline__ void dw_multi_tile_body(const DwTileArgs& p, f4* tile
 #pragma unroll
   for (int it = 0; it < SIT; ++it) {
     const int i = tid + it * 256;
-    if (i < PR * PC * gn) tile[(i % gn) * DWT_PS + i / gn] = xv[it];
+    if (i < PR * PC * gn) tile[(i % gn) * PS + i / gn] = xv[it];
   }
   __syncthreads();
   const int px = tid & 127, half = tid >> 7, py = px / DWT_TW, pxx = px % DWT_TW;
@@ -207,15 +214,15 @@ __device__ __forceinline__ void dw_multi_tile_body(const DwTileArgs& p, f4* tile
   for (int k = 0; k < G / 2; ++k) {
     const int ql = half + 2 * k;
     if (ql >= gn) break;
-    const f4* pl = tile + ql * DWT_PS;
+    const f4* pl = tile + ql * PS;
     const float* wq = sw + ql * 4;
-    f4 acc = *reinterpret_cast<const f4*>(sw + 25 * DWT_GCS + ql * 4);
+    f4 acc = *reinterpret_cast<const f4*>(sw + F * F * DWT_GCS + ql * 4);
 #pragma unroll
     for (int ky = 0; ky < K; ++ky)
 #pragma unroll
       for (int kx = 0; kx < K; ++kx) {
         const f4 xq = pl[(py + ky) * PC + pxx + kx];
-        const f4 wv = *reinterpret_cast<const f4*>(wq + ((O + ky) * 5 + O + kx) * DWT_GCS);
+        const f4 wv = *reinterpret_cast<const f4*>(wq + ((O + ky) * F + O + kx) * DWT_GCS);
         acc = __builtin_elementwise_fma(xq, wv, acc);
       }
 #pragma unroll
@@ -224,25 +231,28 @@ __device__ __forceinline__ void dw_multi_tile_body(const DwTileArgs& p, f4* tile
   }
 }
 
+template <int F>
 __global__ __launch_bounds__(256) void dw_multi_tile_kernel(DwTileArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  f4* tile = reinterpret_cast<f4*>(smem);             // [G][DWT_PS] one plane per quad of the group
-  float* sw = smem + cat::kDwGroup * DWT_PS * 4;      // [25][DWT_GCS] frame, then [DWT_GCS] bias
+  constexpr int FT = F * F;
+  f4* tile = reinterpret_cast<f4*>(smem);             // [G][DWT_PS<F>] one plane per quad of the group
+  float* sw = smem + cat::kDwGroup * DWT_PS<F> * 4;      // [F * F][DWT_GCS] frame, then [DWT_GCS] bias
   int tt, grp;
   cat::dw_tile_group(blockIdx.x, p.N * p.tiles, p.ng, tt, grp);
   const int q0 = p.gq0[grp], gn = p.gnq[grp], k = p.gks[grp];
   const int n = tt / p.tiles, t = tt - n * p.tiles;
   const int oy0 = (t / p.tiles_x) * DWT_TH, ox0 = (t % p.tiles_x) * DWT_TW;
   const int cs = p.nq * 4;
-  for (int i = threadIdx.x; i < 26 * gn; i += 256) {
+  for (int i = threadIdx.x; i < (FT + 1) * gn; i += 256) {
     const int tap = i / gn, c = (q0 + i - tap * gn) * 4;
-    const f4 v = tap < 25 ? *reinterpret_cast<const f4*>(p.w25 + tap * cs + c)
+    const f4 v = tap < FT ? *reinterpret_cast<const f4*>(p.w25 + tap * cs + c)
                           : (p.bias ? *reinterpret_cast<const f4*>(p.bias + c) : f4{0.f, 0.f, 0.f, 0.f});
     *reinterpret_cast<f4*>(sw + tap * DWT_GCS + (i - tap * gn) * 4) = v;
   }
-  if (k == 1) dw_multi_tile_body<1>(p, tile, sw, n, oy0, ox0, q0, gn);
-  else if (k == 3) dw_multi_tile_body<3>(p, tile, sw, n, oy0, ox0, q0, gn);
-  else dw_multi_tile_body<5>(p, tile, sw, n, oy0, ox0, q0, gn);
+  if (k == 1) dw_multi_tile_body<1, F>(p, tile, sw, n, oy0, ox0, q0, gn);
+  else if (k == 3) dw_multi_tile_body<3, F>(p, tile, sw, n, oy0, ox0, q0, gn);
+  else if (F == 5 || k == 5) dw_multi_tile_body<5, F>(p, tile, sw, n, oy0, ox0, q0, gn);
+  else dw_multi_tile_body<F, F>(p, tile, sw, n, oy0, ox0, q0, gn);
 }
 
 // Fewest workgroups (tiles x quad groups) for which cat_dwconv2d_multi_fwd takes the tile kernel: four per CU of the 256.  Below, the tile
@@ -387,7 +397,13 @@ int cat_dwconv2d_fwd(const cat_conv_t* g, const float* x, const float* w, const 
   return cat::check_launch("dwconv2d_fwd");
 }
 
-int cat_dwconv2d_multi_fwd(const cat_dwmulti_t* g, const float* x, const float* w25, const float* bias, float* y, cat_stream_t stream) {
+}  // extern "C"
+
+namespace {
+
+// cat_dwconv2d_multi_fwd (F = 5) and cat_dwconv2d_multi7_fwd (F = 7): one routing rule, one set of limits
+template <int F>
+int dw_multi_launch(const cat_dwmulti_t* g, const float* x, const float* w25, const float* bias, float* y, cat_stream_t stream) {
   CAT_REQUIRE(g->N > 0 && g->H > 0 && g->W > 0 && g->nq > 0 && g->nq <= CAT_DWMULTI_MAXQ, "dwconv multi: bad geometry (nq=%d)", g->nq);
   CAT_REQUIRE((g->xcs & 3) == 0 && (g->ycs & 3) == 0 && g->xcs >= 4 * g->nq && g->ycs >= 4 * g->nq, "dwconv multi: pixel strides");
   DwMultiArgs a{};
@@ -399,7 +415,7 @@ int cat_dwconv2d_multi_fwd(const cat_dwmulti_t* g, const float* x, const float* 
   a.run_base[0] = 0;
   for (int q = 0; q < g->nq; ++q) {
     const int k = g->ks[q];
-    CAT_REQUIRE(k == 1 || k == 3 || k == 5, "dwconv multi: kernel size %d of quad %d", k, q);
+    CAT_REQUIRE(k == 1 || k == 3 || k == 5 || (F == 7 && k == 7), "dwconv multi: kernel size %d of quad %d", k, q);
     CAT_REQUIRE(!g->reflect || (k / 2 < g->H && k / 2 < g->W), "dwconv multi: reflect padding wider than the plane");
     taps += 4.0 * k * k;
     if (a.nrun == 0 || a.run_k[a.nrun - 1] != k) {
@@ -423,11 +439,23 @@ int cat_dwconv2d_multi_fwd(const cat_dwmulti_t* g, const float* x, const float* 
     t.x = x; t.w25 = w25; t.bias = bias; t.y = y;
     t.N = g->N; t.H = g->H; t.W = g->W; t.nq = g->nq; t.xcs = g->xcs; t.ycs = g->ycs; t.reflect = g->reflect; t.act = g->act; t.slope = g->slope;
     for (int k = 0; k < t.ng; ++k) t.gks[k] = (unsigned char)g->ks[t.gq0[k]];
-    dw_multi_tile_kernel<<<g->N * t.tiles * t.ng, 256, DWT_LDS, (hipStream_t)stream>>>(t);
+    dw_multi_tile_kernel<F><<<g->N * t.tiles * t.ng, 256, DWT_LDS<F>, (hipStream_t)stream>>>(t);
     return cat::check_launch("dwconv2d_multi_fwd");
   }
-  dw_multi_fwd_kernel<<<cat::ew_grid(npix * g->nq, kEwCap), 256, (size_t)26 * 4 * g->nq * sizeof(float), (hipStream_t)stream>>>(a);
+  dw_multi_fwd_kernel<F><<<cat::ew_grid(npix * g->nq, kEwCap), 256, (size_t)(F * F + 1) * 4 * g->nq * sizeof(float), (hipStream_t)stream>>>(a);
   return cat::check_launch("dwconv2d_multi_fwd");
+}
+
+}  // namespace
+
+extern "C" {
+
+int cat_dwconv2d_multi_fwd(const cat_dwmulti_t* g, const float* x, const float* w25, const float* bias, float* y, cat_stream_t stream) {
+  return dw_multi_launch<5>(g, x, w25, bias, y, stream);
+}
+
+int cat_dwconv2d_multi7_fwd(const cat_dwmulti_t* g, const float* x, const float* w49, const float* bias, float* y, cat_stream_t stream) {
+  return dw_multi_launch<7>(g, x, w49, bias, y, stream);
 }
 
 int cat_dwconv2d_dgrad(const cat_conv_t* g, const float* dy, const float* w, float* dx, int dxcs, cat_stream_t stream) {

@@ -16,11 +16,16 @@ collapses algebraically -- same values, different evaluation order -- into
     connection become ONE K-concatenated LDS-tile launch (csrc/conv_pk.hip): out = x + [h | hid3 | hid5] * [F ; W3 ; W5] + bias,
     written once -- on planes too small for that kernel: out = add_n(x, F, k3, k5)
 
+    3 5 7 the reference's default kernel sizes (CAT_FROZEN_K7): three wide residual branches and three depthwise ones -- A is 256 -> 132, the
+        depthwise stage one launch on a 7 x 7 filter frame (cat_dwconv2d_multi7_fwd), A and the 7 x 7, 5 x 5 and 3 x 3 first convs ONE launch
+        (cat_tstage1w7_fwd, csrc/conv_s1w7.hip); the tail is the LDS-tile launch on the wide patch (csrc/conv_pk7.hip)
+
 instead of 12 convs + 3 activations + add_n(6) + affine + add_n(2): the 42->256 1x1 layers were epilogue-bound (K = 44: 27 TFLOP/s),
 and 10 of 18 full-size tensor passes disappear.  One-time weight folding is cached per block (invalidated when a tensor changes).
 InstanceNorm teachers (CycleGAN configs) cannot be folded: the blocks a distiller owns take the forward-only fused pipeline of
 cat_amd/frozen_in.py, every other eval-mode InstanceNorm block the general path."""
 import ctypes as C
+import os
 
 import torch
 
@@ -33,6 +38,17 @@ from . import optim
 
 FROZEN = derived.slot('_cat_frozen')      # R5: the block's plan, keyed on every parameter and buffer of the block
 _STAGE1W = True      # stage 1 of the block as one launch (cat_tstage1w_fwd); A/B closed in round 6: teacher forward 11.51 -> 11.15 ms
+# Blocks with a 7 x 7 branch (the reference's parser default --kernel_sizes 3 5 7): the depthwise stage on a 7 x 7 frame
+# (cat_dwconv2d_multi7_fwd) and stage 1 as one launch (cat_tstage1w7_fwd).  CAT_FROZEN_K7=0 / set_k7(False): the launches such a block
+# issued before -- the 1 x 1 GEMM, one cat_dwconv2d_fwd per depthwise branch, one padded first conv per residual branch.  Read at every
+# forward (the plan holds both forms); blocks without a 7 x 7 branch never look at it.
+_K7 = os.environ.get('CAT_FROZEN_K7', '1') != '0'
+
+
+def set_k7(on):
+    global _K7
+    old, _K7 = _K7, bool(on)
+    return old
 
 
 _affine = cnn.bn_affine
@@ -61,6 +77,12 @@ def _plan(block):
     # weights owned by a FusedAdam change under torch's feet (raw-pointer kernels): such blocks -- a BatchNorm student run in eval mode by
     # evaluate_model between training steps -- re-fold after every optimizer step; the frozen teacher (no optimizer) folds once
     return derived.lookup(block, FROZEN, optim.weights_key(list(block.parameters()) + list(block.buffers())), lambda prev: _build_plan(block))
+
+
+def frame_row(fs, k, ky, kx):
+    """row of tap (ky, kx) of a k x k depthwise filter in the [fs * fs][C] frame of side fs: centred"""
+    o = fs // 2 - k // 2
+    return (o + ky) * fs + o + kx
 
 
 def _build_plan(block):
@@ -115,24 +137,26 @@ def _build_plan(block):
     act, slope = cnn._act_code(act_mod)
     # all depthwise convs (+ the copy of the k = 1 residual branch's hidden slice) as ONE launch (cat_dwconv2d_multi_fwd): filters in a 5 x 5
     # frame [25][hc], folded bias, kernel size per channel quad.  The copy is k = 1 with centre weight 1: act(h) = h for an activation
-    # that is idempotent (ReLU; LeakyReLU is not: slope^2 on negative values) -- anything else keeps the separate launches
+    # that is idempotent (ReLU; LeakyReLU is not: slope^2 on negative values) -- anything else keeps the separate launches.  A 7 x 7
+    # depthwise branch, and only that, makes it a 7 x 7 frame [49][hc] (cat_dwconv2d_multi7_fwd; dwm['fs'] = 7)
     dwm = None
-    if dws and hc // 4 <= L.DWMULTI_MAXQ and all(d['k'] in (1, 3, 5) for d in dws) and act in (L.ACT_RELU, L.ACT_NONE):
-        frame = torch.zeros((25, hc), device=dev)
+    if dws and hc // 4 <= L.DWMULTI_MAXQ and all(d['k'] in (1, 3, 5, 7) for d in dws) and act in (L.ACT_RELU, L.ACT_NONE):
+        fs = 7 if any(d['k'] == 7 for d in dws) else 5
+        frame = torch.zeros((fs * fs, hc), device=dev)
         fbias = torch.zeros(hc, device=dev)
         ks = [1] * (hc // 4)
         for (kind, _), (o, m, sz) in zip(slots, offs):
             if kind == 'res':
-                frame[12, o:o + m] = 1.0
+                frame[fs * fs // 2, o:o + m] = 1.0
         for d in dws:
-            k, o2 = d['k'], 2 - d['k'] // 2
+            k = d['k']
             for ky in range(k):
                 for kx in range(k):
-                    frame[(o2 + ky) * 5 + o2 + kx, d['off']:d['off'] + d['m']] = d['w'][:, 0, ky, kx]
+                    frame[frame_row(fs, k, ky, kx), d['off']:d['off'] + d['m']] = d['w'][:, 0, ky, kx]
             fbias[d['off']:d['off'] + d['m']] = d['b']
             for q in range(d['off'] // 4, (d['off'] + d['sz']) // 4):
                 ks[q] = k
-        dwm = dict(frame=frame.contiguous(), bias=fbias.contiguous(), ks=ks)
+        dwm = dict(frame=frame.contiguous(), bias=fbias.contiguous(), ks=ks, fs=fs)
     # stage 1 in one launch (cat_tstage1w_fwd): one 5 x 5 and one 3 x 3 residual branch + the concatenated 1 x 1 convs, the teacher's widths
     s1w = None
     by_k = {wd['k']: wd for wd in wides}
@@ -140,7 +164,14 @@ def _build_plan(block):
             and L.query('cat_tstage1w_supported', by_k[5]['m'], by_k[3]['m'], hc)):
         s1w = dict(packs=None, ws=[by_k[5]['wf'], by_k[3]['wf'], w_a],      # packed filter streams: built at the first launch
                    biases=[by_k[5]['bf'], by_k[3]['bf'], b_a.contiguous()], m=[by_k[5]['m'], by_k[3]['m'], hc])
-    return dict(s1w=s1w, tail_pack=None, tail_offs=None, hc=hc, dwm=dwm, w_a=w_a, b_a=b_a.contiguous(), w_f=w_f, b_f=b_f.contiguous(), dws=dws, wides=wides, act=act, slope=slope,
+    # ... and for the kernel sizes 3 5 7: the 7 x 7, 5 x 5 and 3 x 3 residual branches + the concatenated 1 x 1 convs (cat_tstage1w7_fwd)
+    s1w7 = None
+    if (len(wides) == 3 and set(by_k) == {3, 5, 7} and all(wd['act'] == (act, slope) for wd in wides)
+            and L.query('cat_tstage1w7_supported', by_k[7]['m'], by_k[5]['m'], by_k[3]['m'], hc)):
+        order = [by_k[7], by_k[5], by_k[3]]
+        s1w7 = dict(packs=None, ws=[wd['wf'] for wd in order] + [w_a], biases=[wd['bf'] for wd in order] + [b_a.contiguous()],
+                    m=[wd['m'] for wd in order] + [hc])
+    return dict(s1w=s1w, s1w7=s1w7, tail_pack=None, tail_offs=None, hc=hc, dwm=dwm, w_a=w_a, b_a=b_a.contiguous(), w_f=w_f, b_f=b_f.contiguous(), dws=dws, wides=wides, act=act, slope=slope,
                 pad_mode=pad_mode, copies=[(o, sz) for (kind, _), (o, m, sz) in zip(slots, offs) if kind == 'res'])
 
 
@@ -150,6 +181,10 @@ def block_forward(block, x):
     n, c, h, w = x.shape
     hc = p['hc']
     m_pix = n * h * w
+    refl = p['pad_mode'] == L.PAD_REFLECT
+    # the 7 x 7 forms (CAT_FROZEN_K7): a mirrored 7 x 7 window needs a plane it fits in
+    k7_ok = _K7 and (not refl or (h >= 7 and w >= 7))
+    dwm = p['dwm'] if p['dwm'] is not None and (p['dwm']['fs'] == 5 or k7_ok) else None
 
     def dw_stage(hbuf):
         # every depthwise conv (+ folded BN + activation) and the k = 1 residual branch's copy as one launch
@@ -157,9 +192,10 @@ def block_forward(block, x):
         gm = L.DwMulti()
         gm.N, gm.H, gm.W, gm.nq, gm.xcs, gm.ycs = n, h, w, hc // 4, hc, hc
         gm.reflect, gm.act, gm.slope = int(p['pad_mode'] == L.PAD_REFLECT), p['act'], p['slope']
-        for q, k in enumerate(p['dwm']['ks']):
+        for q, k in enumerate(dwm['ks']):
             gm.ks[q] = k
-        L.call('cat_dwconv2d_multi_fwd', C.byref(gm), ops._p(hbuf), ops._p(p['dwm']['frame']), ops._p(p['dwm']['bias']), ops._p(h2), ops._stream())
+        L.call('cat_dwconv2d_multi7_fwd' if dwm['fs'] == 7 else 'cat_dwconv2d_multi_fwd', C.byref(gm), ops._p(hbuf), ops._p(dwm['frame']),
+               ops._p(dwm['bias']), ops._p(h2), ops._stream())
         return h2
 
     def concat_chain(xi):
@@ -171,7 +207,7 @@ def block_forward(block, x):
             hbuf = ksum.run(aseg, p['b_a'], ops.empty_act(n, hc, h, w, xi.device), act=p['act'], slope=p['slope'])
         else:
             hbuf = ops.Conv2dFn.apply(xi, p['w_a'], p['b_a'], 1, 0, L.PAD_ZERO, p['act'], p['slope'])
-        if p['dwm'] is not None:
+        if dwm is not None:
             h2 = dw_stage(hbuf)
             if fused_tail:
                 return h2
@@ -199,8 +235,25 @@ def block_forward(block, x):
 
     fused_tail = ops.tconv_applicable(n, h, w, c, 3, 3, 1, 1) and 1 + len(p['wides']) <= L.TCONV_MAXSEG
     fns = [concat_chain] + [wide_chain(wd) for wd in p['wides']]
-    s1w = p['s1w'] if fused_tail and p['dwm'] is not None else None
-    if s1w is not None:
+    s1w = p['s1w'] if fused_tail and dwm is not None else None
+    s1w7 = p['s1w7'] if fused_tail and dwm is not None and k7_ok else None
+    if s1w7 is not None:
+        # the same for the kernel sizes 3 5 7: hid7, hid5, hid3 and the concatenated 1 x 1 hidden buffer in one launch
+        if s1w7['packs'] is None:
+            from . import tconv
+            s1w7['packs'] = [tconv.pack(wt, tconv.FWD) for wt in s1w7['ws']]
+        g = L.Stage1W7Geom()
+        g.N, g.H, g.W, g.xcs, g.cin = n, h, w, ops.act_cs(x), c
+        g.reflect, g.act, g.slope = int(refl), p['act'], p['slope']
+        bufs = [ops.empty_act(n, m, h, w, x.device) for m in s1w7['m']]
+        for k in range(4):
+            g.ycs[k], g.nvalid[k] = ops.act_cs(bufs[k]), s1w7['m'][k]
+        arr = C.c_void_p * 4
+        L.call('cat_tstage1w7_fwd', C.byref(g), ops._p(x), arr(*[t.data_ptr() for t in s1w7['packs']]), arr(*[t.data_ptr() for t in s1w7['biases']]),
+               arr(*[t.data_ptr() for t in bufs]), ops._stream())
+        hid = {7: bufs[0], 5: bufs[1], 3: bufs[2]}
+        outs = [dw_stage(bufs[3])] + [hid[wd['k']] for wd in p['wides']]
+    elif s1w is not None:
         # every first conv of the block from one staging of x: hid5, hid3 and the concatenated 1 x 1 hidden buffer in one launch
         if s1w['packs'] is None:
             from . import tconv
@@ -223,7 +276,6 @@ def block_forward(block, x):
     if not fused_tail:
         return ops.AddNFn.apply(x, *outs)
     from . import ksum, tconv
-    refl = p['pad_mode'] == L.PAD_REFLECT
     # wide output (the teacher's C = 256): the tail as ONE implicit GEMM on 128 x 128 tiles with both operands DMA-ed into LDS
     ksegs = [ksum.Segment(outs[0], p['w_f'], False)] + [ksum.Segment(hid, wd['w2'], refl) for wd, hid in zip(p['wides'], outs[1:])]
     if ksum.applicable(ksegs, n, h, w, c):

@@ -4,7 +4,8 @@ The CycleGAN-style distillation runs an InstanceNorm teacher in eval mode under 
 inception_distiller.py:100-104).  An InstanceNorm2d without running statistics computes the same function in eval() as in train(), so
 nothing folds (cat_amd/frozen.py folds BatchNorm only) -- but the block is exactly the forward of the fused training pipeline
 (cat_amd/fused_unit.py, per-sample statistics), which in eval mode serves only blocks an inference runner owns (fused_block.own_eval).
-This module is the forward-only plan of a frozen teacher's blocks, eight launches instead of ~55; its depthwise launches take
+This module is the forward-only plan of a frozen teacher's blocks, eight launches instead of ~55 (kernel sizes from {1, 3, 5, 7}; a 7 x 7
+branch under fused_block's switch CAT_FUSED_K7: stage 1 as one cat_tconv_fwd per kernel size, cat_dwm7_fwd, the cat_tconv_fwd tail); its depthwise launches take
 CAT_DWM_MAXQ quads (a plan that trains groups by CAT_DWM_MAXQ_BWD, the width of the backward kernel's argument arrays; one workgroup of
 either kernel stages one quad group, so LDS bounds neither):
 
@@ -118,7 +119,7 @@ def applicable(block, x):
     if cnn._act_code(first_act)[0] not in (L.ACT_RELU, L.ACT_LRELU):
         return False
     ks = [op[1][0].kernel_size[0] for op in block.res_ops] + [op[2][0].kernel_size[0] for op in block.dw_ops]
-    if any(k not in (1, 3, 5) for k in ks):
+    if any(k not in ((1, 3, 5, 7) if fused_block._K7 else (1, 3, 5)) for k in ks):      # 7 x 7 branches: under the fused block's own switch (CAT_FUSED_K7)
         return False
     if dw_launches([U.cs4(op[0][0].out_channels) // 4 for op in block.dw_ops]) is None:
         return False
@@ -177,7 +178,8 @@ def block_forward(block, x):
     t = ops.empty_act(n, c, h, w, dev)
     pw = block.pw_bn
     bias2 = p.bias2 if p.has_bias2 else None
-    wide = _wide_segs(block, p, z1, ss1, zd, ssd) if _TAIL == 'ksum' else None
+    # the wide tile's domain is kernel sizes 1, 3, 5: a plan with a 7 x 7 branch always takes the LDS-tile tail (conv_pk7.hip)
+    wide = _wide_segs(block, p, z1, ss1, zd, ssd) if _TAIL == 'ksum' and all(b['k'] != 7 for b in p.res) else None
     if wide is not None and ksum.norm_applicable(wide, n, h, w, c):
         partp, th, tw = ksum.run_norm(wide, bias2, t)
         ssp = torch.empty((2, n, p.cs), device=dev, dtype=torch.float32)

@@ -114,6 +114,10 @@ typedef struct {
   int ks[CAT_DWMULTI_MAXQ];
 } cat_dwmulti_t;
 int cat_dwconv2d_multi_fwd(const cat_dwmulti_t* g, const float* x, const float* w25, const float* bias, float* y, cat_stream_t stream);
+/* The same launch with a kernel size in {1, 3, 5, 7} per channel quad (the reference's default --kernel_sizes 3 5 7): the filters lie in a
+ * 7 x 7 frame w49[49][4*nq] -- tap (ky, kx) of a k x k filter at row (ky + 3 - k/2) * 7 + kx + 3 - k/2 -- and the tile kernel stages an
+ * (8 + 6) x (16 + 6) patch.  Routing, run and group limits, bias and copy convention and the arithmetic order are cat_dwconv2d_multi_fwd's. */
+int cat_dwconv2d_multi7_fwd(const cat_dwmulti_t* g, const float* x, const float* w49, const float* bias, float* y, cat_stream_t stream);
 int cat_dwconv2d_dgrad(const cat_conv_t* g, const float* dy, const float* w, float* dx, int dxcs,
                        cat_stream_t stream);
 int cat_dwconv2d_wgrad(const cat_conv_t* g, const float* x, const float* dy, float* dw, int accumulate, void* ws,
@@ -633,6 +637,23 @@ int cat_tstage1w_supported(int w5, int w3, int w1);
 int cat_tstage1w_fwd(const cat_tstage1w_t* g, const float* x, const float* const* packs, const float* const* biases, float* const* ys,
                      cat_stream_t stream);
 int cat_tstage1_dgrad(const cat_tstage1_t* g, const float* dy, const float* const* packs, float* const* dxs, const int* dxcs,
+                      cat_stream_t stream);
+/* cat_tstage1w_fwd for a frozen block with the reference's default kernel sizes 3 5 7 (csrc/conv_s1w7.hip): four slots -- the 7 x 7, 5 x 5 and
+ * 3 x 3 first convs of the residual branches and the N-concatenated 1 x 1 first convs of the depthwise branches -- from one staging of the
+ * input on an (8 + 6) x (16 + 6) patch, y_k = act(conv_k(x) + bias_k) into four buffers.  packs[k]: cat_tconv_pack streams of the (folded)
+ * filters for k = 7, 5, 3, 1; biases: NULL, or four pointers of which any may be NULL.  Reflect padding needs H, W >= 7.
+ * cat_tstage1w7_supported(w7, w5, w3, w1): 33..48 output channels per wide slot, 129..144 for the 1 x 1 slot (3 + 3 + 3 + 9 N tiles). */
+typedef struct {
+  int N, H, W;
+  int xcs, cin;        /* pixel stride / channels of x */
+  int reflect;         /* padding of the 7 x 7 / 5 x 5 / 3 x 3 convs: 1 = mirrored, 0 = zero */
+  int act;             /* epilogue activation of all four slots */
+  float slope;
+  int ycs[4];          /* pixel strides of the four outputs (multiples of 4; channels [nvalid, ycs) below 48 / 144 are written as 0) */
+  int nvalid[4];       /* output channels of the 7 x 7 / 5 x 5 / 3 x 3 / 1 x 1 slot */
+} cat_tstage1w7_t;
+int cat_tstage1w7_supported(int w7, int w5, int w3, int w1);
+int cat_tstage1w7_fwd(const cat_tstage1w7_t* g, const float* x, const float* const* packs, const float* const* biases, float* const* ys,
                       cat_stream_t stream);
 /* cat_tstage1_fwd for the WIDE block (csrc/conv_s1ws.hip): the computation of cat_tstage1w_fwd -- one staging of the input tile per 16-channel
  * chunk for the 5 x 5 conv, the 3 x 3 conv and the N-concatenated 1 x 1 convs, the teacher's widths -- with cat_tstage1_fwd's arguments and
