@@ -100,6 +100,10 @@ class Stage1Geom(C.Structure):
     _fields_ = [(n, c_i) for n in ('N', 'H', 'W', 'xcs', 'cin', 'reflect', 'ycs', 'scs')] + [('col0', c_i * 3), ('width', c_i * 3), ('nvalid', c_i * 3)]
 
 
+class Stage1S7Geom(C.Structure):      # cat_tstage1s7_t: Stage1Geom with four slots (7, 5, 3, 1)
+    _fields_ = [(n, c_i) for n in ('N', 'H', 'W', 'xcs', 'cin', 'reflect', 'ycs', 'scs')] + [('col0', c_i * 4), ('width', c_i * 4), ('nvalid', c_i * 4)]
+
+
 class Stage1WGeom(C.Structure):
     _fields_ = [(n, c_i) for n in ('N', 'H', 'W', 'xcs', 'cin', 'reflect', 'act')] + [('slope', c_f), ('ycs', c_i * 3), ('nvalid', c_i * 3)]
 
@@ -223,6 +227,8 @@ SIGNATURES = {
     'cat_tstage1w7_fwd': (c_i, [C.POINTER(Stage1W7Geom), c_p, c_p, c_p, c_p, c_p]),
     'cat_tstage1ws_supported': (c_i, [c_i, c_i, c_i]),
     'cat_tstage1ws_fwd': (c_i, [C.POINTER(Stage1Geom), c_p, c_p, c_p, c_p, c_p, c_p]),
+    'cat_tstage1ws7_supported': (c_i, [c_i, c_i, c_i, c_i]),
+    'cat_tstage1ws7_fwd': (c_i, [C.POINTER(Stage1S7Geom), c_p, c_p, c_p, c_p, c_p, c_p]),
     'cat_tstage1_dgrad': (c_i, [C.POINTER(Stage1Geom), c_p, c_p, c_p, c_p, c_p]),
     'cat_tnorm_finalize': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_p]),
     'cat_tnorm_finalize2': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_p]),

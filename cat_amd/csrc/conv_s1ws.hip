@@ -6,7 +6,8 @@
 // It serves the training forward of the wide block (cat_amd/fused_block.py) and the frozen InstanceNorm teacher (cat_amd/frozen_in.py),
 // which before issued three cat_tconv_fwd launches that each staged the same 256-channel input.
 //
-// Statistics (the formula and the reduction scheme of s1_epilogue<NT, true>, conv_pk.hip): per 8 x 16 tile and channel the sum over the
+// Statistics (conv_s1ws_epilogue.h, one text for this kernel and tstage1ws7_kernel, conv_s1ws7.hip; the formula and the reduction scheme of
+// s1_epilogue<NT, true>, conv_pk.hip): per 8 x 16 tile and channel the sum over the
 // tile's valid pixels and the sum of squared deviations from the TILE mean, two passes over the accumulators -- pixel columns rg and rows i in
 // registers, the lane quarters lq by two xor shuffles, the four waves through LDS.  Deterministic, no atomics.  The six accumulator sets
 // (5 x 5, 3 x 3, four passes of the 1 x 1 slot) take the epilogue one after the other, three N tiles each.
@@ -14,6 +15,7 @@
 // A translation unit of its own: the code generation of conv_pk.hip is pinned (tests/test_codegen.py) and stays as it is.
 #include "common.h"
 #include "conv_pk_tile.h"
+#include "conv_s1ws_epilogue.h"
 
 namespace cat_s1ws {
 
@@ -28,88 +30,8 @@ struct Args {
   int hl, tr, tc, tiles_x, tiles;
 };
 
-constexpr int NT = 3;      // N tiles per accumulator set
-
-// One accumulator set = N tiles [t0, t0 + 3) of slot k: columns col0[k] + t0 * 16 + [0, 48) as far as they lie inside the slot's width.
-// Padding columns inside the slice carry zero filters and a zero bias: plain zeros come out, in y and in the table.
-// red: [2][4][NT * 16] floats of LDS.
-__device__ __forceinline__ void epilogue(const f4 (&acc)[2][NT], const Args& p, int k, int t0, int n, int tt, int oy0, int ox0, int wave, int lr,
-                                         int lq, float* red) {
-  const int col0 = p.col0[k] + t0 * 16, width = p.width[k] - t0 * 16;      // this set's first column; columns left in the slot (may be <= 0)
-  const int cnt = min(TH, p.H - oy0) * min(16, p.W - ox0);
-  float s[NT], mean[NT], bv[NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const int co = j * 16 + lr;
-    bv[j] = (p.bias && co < width) ? p.bias[col0 + co] : 0.f;
-  }
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    float a = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const bool rowv = oy0 + 2 * wave + i < p.H;
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) a += (rowv && ox0 + lq * 4 + rg < p.W) ? acc[i][j][rg] + bv[j] : 0.f;
-    }
-    a += __shfl_xor(a, 16, 64);
-    a += __shfl_xor(a, 32, 64);
-    if (lq == 0) red[wave * NT * 16 + j * 16 + lr] = a;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const int c = j * 16 + lr;
-    s[j] = (red[c] + red[NT * 16 + c]) + (red[2 * NT * 16 + c] + red[3 * NT * 16 + c]);
-    mean[j] = s[j] / (float)cnt;
-  }
-  float* red2 = red + 4 * NT * 16;
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    float a = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const bool rowv = oy0 + 2 * wave + i < p.H;
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const float d = acc[i][j][rg] + bv[j] - mean[j];
-        a += (rowv && ox0 + lq * 4 + rg < p.W) ? d * d : 0.f;
-      }
-    }
-    a += __shfl_xor(a, 16, 64);
-    a += __shfl_xor(a, 32, 64);
-    if (lq == 0) red2[wave * NT * 16 + j * 16 + lr] = a;
-  }
-  __syncthreads();
-  if (wave == 0 && lq == 0) {
-    float* dst = p.stats + (int64_t)tt * 2 * p.scs + col0;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int c = j * 16 + lr;
-      if (c < width) {
-        dst[c] = s[j];
-        dst[p.scs + c] = (red2[c] + red2[NT * 16 + c]) + (red2[2 * NT * 16 + c] + red2[3 * NT * 16 + c]);
-      }
-    }
-  }
-  __syncthreads();   // red is reused by the next accumulator set
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int oy = oy0 + 2 * wave + i;
-    if (oy >= p.H) continue;
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      const int ox = ox0 + lq * 4 + rg;
-      if (ox >= p.W) continue;
-      float* yo = p.y + (((int64_t)n * p.H + oy) * p.W + ox) * p.ycs + col0;
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int co = j * 16 + lr;
-        if (co < width) yo[co] = acc[i][j][rg] + bv[j];
-      }
-    }
-  }
-}
+using cat_s1ws_epi::NT;      // N tiles per accumulator set
+using cat_s1ws_epi::epilogue;      // conv_s1ws_epilogue.h, shared with tstage1ws7_kernel (conv_s1ws7.hip)
 
 template <int N5, int N3, int N1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void tstage1ws_kernel(const Args p) {

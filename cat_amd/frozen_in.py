@@ -5,11 +5,13 @@ inception_distiller.py:100-104).  An InstanceNorm2d without running statistics c
 nothing folds (cat_amd/frozen.py folds BatchNorm only) -- but the block is exactly the forward of the fused training pipeline
 (cat_amd/fused_unit.py, per-sample statistics), which in eval mode serves only blocks an inference runner owns (fused_block.own_eval).
 This module is the forward-only plan of a frozen teacher's blocks, eight launches instead of ~55 (kernel sizes from {1, 3, 5, 7}; a 7 x 7
-branch under fused_block's switch CAT_FUSED_K7: stage 1 as one cat_tconv_fwd per kernel size, cat_dwm7_fwd, the cat_tconv_fwd tail); its depthwise launches take
+branch under fused_block's switch CAT_FUSED_K7: stage 1 as one cat_tstage1ws7_fwd at the teacher's widths, else one cat_tconv_fwd per kernel
+size, cat_dwm7_fwd, the cat_tconv_fwd tail); its depthwise launches take
 CAT_DWM_MAXQ quads (a plan that trains groups by CAT_DWM_MAXQ_BWD, the width of the backward kernel's argument arrays; one workgroup of
 either kernel stages one quad group, so LDS bounds neither):
 
-    stage 1   first convs of all branches -> Z1 + tile statistics                 (fused_unit.stage1: cat_tstage1ws_fwd; CAT_STAGE1WS=0: cat_tconv_fwd)
+    stage 1   first convs of all branches -> Z1 + tile statistics                 (fused_unit.stage1: cat_tstage1ws_fwd, at kernel sizes 3 5 7
+                                                                                  cat_tstage1ws7_fwd; CAT_STAGE1WS=0 / CAT_STAGE1WS7=0: cat_tconv_fwd)
     finalize  per-sample scale / shift of every stage-1 norm                      (cat_tnorm_finalize, G = N)
     dw        the depthwise convs, normalise + activation applied while staging, in BRANCH-ALIGNED launches of at most CAT_DWM_MAXQ
               channel quads (the teacher's 3 x 11 quads: 22 + 11)                 (cat_dwm_fwd)

@@ -7,6 +7,8 @@ x 3, add_n, ...), most of them a few microseconds of HBM-bound work between depe
 
     stage 1   one LDS-tile conv launch per first-conv kernel size (the 1x1 convs of all branches as ONE N-concatenated GEMM) writing
               channel slices of one pre-norm buffer Z1 and the per-tile statistics of every branch           (cat_tconv_fwd + stats)
+              -- or ONE launch for all sizes where fused_unit.stage1 has a kernel for the plan's widths (cat_tstage1_fwd; the full-width
+              blocks of CAT_FUSED_WIDE: cat_tstage1ws_fwd at kernel sizes 1 3 5, cat_tstage1ws7_fwd at 3 5 7)
     finalize  scale / shift of all stage-1 norms + their running statistics                                   (cat_tnorm_finalize)
     dw        all depthwise convs as one launch; normalise + ReLU of stage 1 applied while staging            (cat_dwm_fwd; cat_dwm7_fwd
               when a depthwise branch is 7 x 7: kernel sizes from {1, 3, 5, 7}, CAT_FUSED_K7)

@@ -1,6 +1,6 @@
 """The fused inception block (cat_amd/fused_block.py) and the fused six-branch SPADE unit (cat_amd/fused_spade.py) are ONE pipeline
 
-    stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tstage1ws_fwd / cat_tconv_fwd)
+    stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tstage1ws_fwd / cat_tstage1ws7_fwd / cat_tconv_fwd)
     finalize  scale / shift of all stage-1 norms + their running statistics                               (cat_tnorm_finalize)
     dw        all depthwise convs (one launch per <= 18 / 24 channel quads), norm + activation of stage 1 applied while staging   (cat_dwm_fwd;
               cat_dwm7_fwd for a plan with a 7 x 7 depthwise branch)
@@ -49,6 +49,18 @@ _STAGE1WS = os.environ.get('CAT_STAGE1WS', '1') != '0'
 def set_stage1_wide(on):
     global _STAGE1WS
     old, _STAGE1WS = _STAGE1WS, bool(on)
+    return old
+
+
+# The same for the kernel sizes 3 5 7 (first convs {1, 3, 5, 7}; the full-width widths 44 / 44 / 44 / 132): ONE cat_tstage1ws7_fwd launch
+# (csrc/conv_s1ws7.hip) instead of four cat_tconv_fwd.  Independent of CAT_STAGE1WS.  CAT_STAGE1WS7=0 / set_stage1ws7(False): the four
+# launches (measurements: profiles/stage1ws7_bench.txt)
+_STAGE1WS7 = os.environ.get('CAT_STAGE1WS7', '1') != '0'
+
+
+def set_stage1ws7(on):
+    global _STAGE1WS7
+    old, _STAGE1WS7 = _STAGE1WS7, bool(on)
     return old
 
 
@@ -374,22 +386,26 @@ def prepare_plans(plans, group, backward=False):
 # ---------------------------------------------------------------------------------------------------------------- forward stages
 def stage1(p, x, z1, part1, reflect=False):
     """First convs of all branches: x -> channel slices of Z1 (pre-norm) + tile statistics into part1.  part1 None: the eval form, no
-    statistics (always one launch per kernel size).  The one-launch kernels take exactly the kernel sizes 5, 3 and 1: a plan with another
-    set (a 7 x 7 first conv, or fewer sizes) runs one launch per size."""
+    statistics (always one launch per kernel size).  The one-launch kernels take exactly the kernel sizes 5, 3 and 1, or -- the wide
+    widths only -- 7, 5, 3 and 1: a plan with another set (fewer sizes; a 7 x 7 first conv at narrow widths) runs one launch per size."""
     n, c, h, w = x.shape
     by_k = {g['k']: g for g in p.groups}
-    widths = [by_k[k]['width'] for k in (5, 3, 1)] if part1 is not None and set(by_k) == {1, 3, 5} else None
-    entry = None
+    sizes = (5, 3, 1)
+    widths = [by_k[k]['width'] for k in sizes] if part1 is not None and set(by_k) == {1, 3, 5} else None
+    entry, geom = None, L.Stage1Geom
     if widths is not None and L.query('cat_tstage1_supported', *widths):
         entry = 'cat_tstage1_fwd'
     elif widths is not None and _STAGE1WS and L.query('cat_tstage1ws_supported', *widths):
         entry = 'cat_tstage1ws_fwd'      # the wide block's widths: the same arguments and output contract
+    elif part1 is not None and _STAGE1WS7 and set(by_k) == {1, 3, 5, 7} and (not reflect or (h >= 7 and w >= 7)) and \
+            L.query('cat_tstage1ws7_supported', *[by_k[k]['width'] for k in (7, 5, 3, 1)]):
+        entry, geom, sizes = 'cat_tstage1ws7_fwd', L.Stage1S7Geom, (7, 5, 3, 1)      # ... with one more slot
     if entry is not None:
-        # one launch: the three kernel sizes share every staged input tile
-        gs = L.Stage1Geom()
+        # one launch: the kernel sizes share every staged input tile
+        gs = geom()
         gs.N, gs.H, gs.W, gs.xcs, gs.cin, gs.reflect, gs.ycs, gs.scs = n, h, w, ops.act_cs(x), c, int(reflect), p.hc1, p.hc1
-        packs = (C.c_void_p * 3)()
-        for slot, k in enumerate((5, 3, 1)):
+        packs = (C.c_void_p * len(sizes))()
+        for slot, k in enumerate(sizes):
             g = by_k[k]
             gs.col0[slot], gs.width[slot], gs.nvalid[slot] = g['off'], g['width'], sum(b['m'] for b in g['branches'])
             packs[slot] = g['pack'].data_ptr()

@@ -664,6 +664,23 @@ int cat_tstage1w7_fwd(const cat_tstage1w7_t* g, const float* x, const float* con
 int cat_tstage1ws_supported(int w5, int w3, int w1);
 int cat_tstage1ws_fwd(const cat_tstage1_t* g, const float* x, const float* const* packs, const float* bias, float* y, float* stats,
                       cat_stream_t stream);
+/* cat_tstage1ws_fwd for a wide block with the reference's default kernel sizes 3 5 7 (csrc/conv_s1ws7.hip): the computation of
+ * cat_tstage1w7_fwd -- one staging of the input tile per 16-channel chunk on an (8 + 6) x (16 + 6) patch for the 7 x 7, 5 x 5 and 3 x 3 first
+ * convs and the N-concatenated 1 x 1 convs -- with the output contract of cat_tstage1ws_fwd: slot k (order 7, 5, 3, 1) writes columns
+ * [col0[k], col0[k] + width[k]) of the pre-norm buffer y (pixel stride g->ycs; bias added, no activation; padding columns of a slice, whose
+ * filters and bias are zero, come out as 0) and its per-tile statistics (sum, squared deviations from the tile mean) into the same columns
+ * of `stats` (rows of g->scs floats, the table cat_tnorm_finalize reads).  packs[k]: the slot's filter stream with Nn = width[k]; bias:
+ * concatenated over y's columns or NULL.  Zero and reflect padding; reflect needs H, W >= 7.
+ * cat_tstage1ws7_supported(slot widths): 33..48 columns per wide slot, 129..144 for the 1 x 1 slot (3 + 3 + 3 + 9 N tiles). */
+typedef struct {
+  int N, H, W, xcs, cin;
+  int reflect;
+  int ycs, scs;
+  int col0[4], width[4], nvalid[4];
+} cat_tstage1s7_t;
+int cat_tstage1ws7_supported(int w7, int w5, int w3, int w1);
+int cat_tstage1ws7_fwd(const cat_tstage1s7_t* g, const float* x, const float* const* packs, const float* bias, float* y, float* stats,
+                       cat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Quad-granule LDS-tile convolution (csrc/conv_q.hip, round 4): the same K-segment model as cat_tconv_fwd on v_mfma_f32_4x4x1_16B_f32 --
