@@ -78,7 +78,7 @@ __device__ __forceinline__ void ksum_body(const Args& p, const NArgs* nx) {
   float* sN = reinterpret_cast<float*>(tabX + BM * 8);             // NORM: [2][ntab] scale / shift rows of this tile's sample
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
-  const int ntn = (p.Cout + BN - 1) / BN;
+  const int ntn = (p.ycw + BN - 1) / BN;      // (ycw >= Cout here: N tiles beyond Cout own only the zero columns [Cout, ycw))
   const int bid = cat::xcd_remap(blockIdx.x, gridDim.x);
   const int m0 = (bid / ntn) * BM, n0 = (bid % ntn) * BN;
   const int HW = p.H * p.W;
@@ -496,7 +496,9 @@ static int ksum_launch(const cat_ksum_t* g, const cat_ksum_norm_t* nm, const flo
   // 96-wide N tiles where they pad less than 128-wide ones (176 output channels: 192 instead of 256 columns)
   const bool n96 = cat::cdiv(g->Cout, 96) * 96 < cat::cdiv(g->Cout, 128) * 128;
   const int bn = n96 ? 96 : 128;
-  const int64_t grid = (int64_t)cat::cdiv(M, cat_ks::BM) * cat::cdiv(g->Cout, bn);
+  // N tiles up to max(ycw, Cout): the zero columns [Cout, ycw) may reach past the last tile of Cout (filter rows beyond Cout read as zero).
+  // ycw <= cs_for(Cout), as the models pass it, lies inside that tile: the same grid
+  const int64_t grid = (int64_t)cat::cdiv(M, cat_ks::BM) * cat::cdiv(a.ycw, bn);
   CAT_REQUIRE(grid < (int64_t)2147483647, "conv ksum: grid too large");
   size_t lds = (size_t)2 * (cat_ks::BM + bn) * 32 * sizeof(float) + (size_t)2 * cat_ks::BM * 8 * sizeof(int);
   cat_ks::NArgs na{};

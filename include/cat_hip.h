@@ -441,7 +441,8 @@ typedef struct {
   int scs;             /* floats per statistics row (>= the columns this launch owns; `stats` points at its first column) */
   int N, H, W;         /* source planes (all segments) */
   int Ho, Wo;          /* output plane */
-  int Nn, ycs, ycw;    /* output channels, pixel stride, channels [Nn, ycw) are written as 0 */
+  int Nn, ycs, ycw;    /* output channels, pixel stride, channels [Nn, ycw) are written as 0 -- inside the last 16-wide N tile of Nn: the
+                        * filter pack holds ceil(Nn / 16) tiles, columns of y (and of `stats`) from 16 * ceil(Nn / 16) on are never written */
   int nvalid;          /* output channels that are real (N-concatenated launches carry zero-filter padding columns): FLOP accounting only; 0 = Nn */
   int act;             /* epilogue activation */
   float slope;
@@ -475,7 +476,7 @@ typedef struct {
 } cat_ksum_seg_t;
 typedef struct {
   int N, H, W;         /* planes (input = output size) */
-  int Cout, ycs, ycw;  /* output channels, pixel stride, channels [Cout, ycw) are written as 0 */
+  int Cout, ycs, ycw;  /* output channels, pixel stride, channels [Cout, ycw) are written as 0 (N tiles are launched up to max(ycw, Cout)) */
   int rcs;             /* pixel stride of res */
   int act;             /* epilogue activation (before the residual) */
   float slope;

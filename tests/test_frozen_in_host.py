@@ -40,6 +40,7 @@ def test_ownership_is_weak_and_writes_nothing_on_the_module():
     from cat_amd import frozen_in
     blk, other = _block(), _block()
     before = {k: set(vars(m)) for k, m in blk.named_modules()}
+    gc.collect()      # (owned blocks of earlier tests that are garbage already must not be counted: the collection below would take them too)
     count = len(frozen_in._OWNED)
     frozen_in.own(blk, 3)
     assert frozen_in.owned(blk) and not frozen_in.owned(other) and frozen_in._OWNED[blk] == (3,)
