@@ -229,6 +229,9 @@ SIGNATURES = {
     'cat_tstage1ws_fwd': (c_i, [C.POINTER(Stage1Geom), c_p, c_p, c_p, c_p, c_p, c_p]),
     'cat_tstage1ws7_supported': (c_i, [c_i, c_i, c_i, c_i]),
     'cat_tstage1ws7_fwd': (c_i, [C.POINTER(Stage1S7Geom), c_p, c_p, c_p, c_p, c_p, c_p]),
+    'cat_tstage1n7_supported': (c_i, [c_i, c_i, c_i, c_i]),
+    'cat_tstage1n7_fwd': (c_i, [C.POINTER(Stage1S7Geom), c_p, c_p, c_p, c_p, c_p, c_p]),
+    'cat_tstage1n7_dgrad': (c_i, [C.POINTER(Stage1S7Geom), c_p, c_p, c_p, c_p, c_p]),
     'cat_tstage1_dgrad': (c_i, [C.POINTER(Stage1Geom), c_p, c_p, c_p, c_p, c_p]),
     'cat_tnorm_finalize': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_p]),
     'cat_tnorm_finalize2': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_p]),

@@ -25,6 +25,7 @@
 // its issue slots with the fp32 MFMA).  Filters of trainable layers are re-packed once per optimizer step.
 #include "common.h"
 #include "conv_pk_tile.h"
+#include "conv_s1_epilogue.h"
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -55,88 +56,7 @@ struct S1Args {
   int hl, tr, tc, tiles_x, tiles;
 };
 
-template <int NT, bool STATS>
-__device__ __forceinline__ void s1_epilogue(f4 (&acc)[2][NT], const S1Args& p, int k, int n, int tt, int oy0, int ox0, int wave, int lr, int lq,
-                                            float* red) {
-  const int col0 = p.col0[k], width = p.width[k], nv = width;   // padding columns inside the slice carry zero filters: plain zeros come out
-  const int cnt = min(TH, p.H - oy0) * min(16, p.W - ox0);
-  float s[NT], mean[NT], bv[NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const int co = j * 16 + lr;
-    bv[j] = (p.bias && co < nv) ? p.bias[col0 + co] : 0.f;
-  }
-  if constexpr (STATS) {     // per-tile statistics; the input-gradient use of the kernel has none
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      float a = 0.f;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const bool rowv = oy0 + 2 * wave + i < p.H;
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) a += (rowv && ox0 + lq * 4 + rg < p.W) ? acc[i][j][rg] + bv[j] : 0.f;
-      }
-      a += __shfl_xor(a, 16, 64);
-      a += __shfl_xor(a, 32, 64);
-      if (lq == 0) red[wave * NT * 16 + j * 16 + lr] = a;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int c = j * 16 + lr;
-      s[j] = (red[c] + red[NT * 16 + c]) + (red[2 * NT * 16 + c] + red[3 * NT * 16 + c]);
-      mean[j] = s[j] / (float)cnt;
-    }
-    float* red2 = red + 4 * NT * 16;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      float a = 0.f;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const bool rowv = oy0 + 2 * wave + i < p.H;
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const float d = acc[i][j][rg] + bv[j] - mean[j];
-          a += (rowv && ox0 + lq * 4 + rg < p.W) ? d * d : 0.f;
-        }
-      }
-      a += __shfl_xor(a, 16, 64);
-      a += __shfl_xor(a, 32, 64);
-      if (lq == 0) red2[wave * NT * 16 + j * 16 + lr] = a;
-    }
-    __syncthreads();
-    if (wave == 0 && lq == 0) {
-      float* dst = p.stats + (int64_t)tt * 2 * p.scs + col0;
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int c = j * 16 + lr;
-        if (c < width) {
-          const bool cv = c < nv;
-          dst[c] = cv ? s[j] : 0.f;
-          dst[p.scs + c] = cv ? (red2[c] + red2[NT * 16 + c]) + (red2[2 * NT * 16 + c] + red2[3 * NT * 16 + c]) : 0.f;
-        }
-      }
-    }
-    __syncthreads();   // red is reused by the next sub-convolution
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int oy = oy0 + 2 * wave + i;
-    if (oy >= p.H) continue;
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      const int ox = ox0 + lq * 4 + rg;
-      if (ox >= p.W) continue;
-      float* yo = p.ys[k] + (((int64_t)n * p.H + oy) * p.W + ox) * p.ycs3[k] + col0;
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int co = j * 16 + lr;
-        if (co < nv) yo[co] = acc[i][j][rg] + bv[j];
-        else if (co < width) yo[co] = 0.f;
-      }
-    }
-  }
-}
+// s1_epilogue (the column-slice + statistics epilogue of a slot): conv_s1_epilogue.h, shared with tstage1n7_kernel (conv_s1n7.hip)
 
 template <int NA, int NB, int NC, bool STATS>
 __global__ __launch_bounds__(256) void tstage1_kernel(const S1Args p) {

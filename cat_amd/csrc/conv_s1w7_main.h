@@ -6,7 +6,9 @@
 //     the A-offset tables; a kernel may append to it);
 //   * inside the kernel, without it: the main loop, A FUNCTION-BODY FRAGMENT moved here verbatim from tstage1w7_kernel -- every line up to its
 //     store calls -- so that either kernel compiles to exactly what it would with the text in place (the precedent and the reason:
-//     conv_pk_s1w_main.h; the code generation of conv_s1w7.hip is pinned, tests/golden/codegen_conv_s1w7.json).
+//     conv_pk_s1w_main.h; the code generation of conv_s1w7.hip is pinned, tests/golden/codegen_conv_s1w7.json).  Its first half, the tile
+//     origin and the staging of a chunk, is conv_s1w7_stage.h (included below where the text stood), which the narrow four-slot kernel
+//     (tstage1n7_kernel, csrc/conv_s1n7.hip) includes on its own.
 //
 // The fragment expects, in scope: template parameters NW, P1; the kernel argument `p` with x, pack[4], xcs, c4, N, H, W, reflect, tiles_x,
 // tiles; g_zero (four zero floats in global memory); cat_pk's TH, PITCH, mma_groups, wload, wmma; the declarations below.  It leaves the
@@ -25,58 +27,7 @@ __host__ __device__ constexpr int slot_ks(int k) { return 7 - 2 * k; }      // s
 
   constexpr int MT = 2, N1 = 3 * P1;
   static_assert(NW >= 1 && NW <= 3 && P1 == 3, "tile counts");
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* tile0 = smem;
-  int* tab0 = reinterpret_cast<int*>(smem + 2 * TILE_FLOATS);      // [buf][slot][KTAB]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lr = lane & 15, lq = lane >> 4;
-  const int tt = cat::xcd_remap(blockIdx.x, gridDim.x);
-  const int n = tt / p.tiles, t = tt - n * p.tiles;
-  const int oy0 = (t / p.tiles_x) * TH, ox0 = (t % p.tiles_x) * TW;
-  const int quad = tid & 3;
-  unsigned soff[MAXIT], smask = 0;
-#pragma unroll
-  for (int it = 0; it < MAXIT; ++it) {
-    const int pix = (tid + it * 256) >> 2;
-    const int r = pix / TC;
-    int iy = oy0 - HL + r, ix = ox0 - HL + (pix - r * TC);
-    bool v = tid + it * 256 < SLOTS;
-    if (p.reflect) {
-      v = v && iy > -p.H && iy < 2 * p.H - 1 && ix > -p.W && ix < 2 * p.W - 1;      // beyond a ragged tile's mirror range: never read
-      iy = cat::reflect_idx(iy, p.H);
-      ix = cat::reflect_idx(ix, p.W);
-    } else {
-      v = v && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-    }
-    smask |= v ? (1u << it) : 0u;
-    soff[it] = v ? ((unsigned)(n * p.H + iy) * (unsigned)p.W + (unsigned)ix) * (unsigned)p.xcs + quad * 4 : 0u;
-  }
-  f4 sreg[MAXIT];
-  auto gload = [&](int c0) {
-    const bool qv = c0 + quad * 4 < p.c4;
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) sreg[it] = *reinterpret_cast<const f4*>((((smask >> it) & 1u) && qv) ? p.x + soff[it] + c0 : g_zero);
-  };
-  auto sstore = [&](int buf, int c0) {
-    float* tile = tile0 + buf * TILE_FLOATS;
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) {
-      const int idx = tid + it * 256;
-      if (idx < SLOTS) *reinterpret_cast<f4*>(tile + (idx >> 2) * PITCH + quad * 4) = sreg[it];
-    }
-    const int nq = min(4, (p.c4 - c0) >> 2);
-    const int tap = tid / nq, qd = tid - tap * nq;      // 256 threads, KTAB entries: one each
-#pragma unroll
-    for (int k = 0; k < NSLOT; ++k) {
-      const int ks = slot_ks(k), taps = ks * ks;
-      int off = 0;
-      if (tid < ((taps * nq + 3) >> 2) * 4 && tap < taps) {
-        const int ky = tap / ks, kx = tap - ky * ks, d = HL - (ks >> 1);
-        off = ((d + ky) * TC + d + kx) * PITCH + qd * 4;
-      }
-      tab0[(buf * NSLOT + k) * KTAB + tid] = off;
-    }
-  };
+#include "conv_s1w7_stage.h"      // the tile origin and the staging of a chunk, shared with tstage1n7_kernel (conv_s1n7.hip)
   const f4 zero4 = {0.f, 0.f, 0.f, 0.f};
   f4 acc7[MT][NW], acc5[MT][NW], acc3[MT][NW], accA[MT][3], accB[MT][3], accC[MT][3];      // the 1 x 1 slot: passes A..C of 3 tiles
 #pragma unroll

@@ -8,7 +8,8 @@ block's shortcut).  The per-layer path launches ~45 kernels per unit (12 convs, 
 hidden tensors of 1..13 channels on planes of up to 256 x 512 pixels.  Here a unit is the pipeline of cat_amd/fused_unit.py -- layout, operand
 preparation and the stage sequence, forward and backward, defined once there and shared with the fused inception block:
 
-    stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tconv_fwd)
+    stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tconv_fwd;
+              cat_tstage1n7_fwd for a unit with kernel sizes 3 5 7 under CAT_FUSED_SPADE_K7)
     finalize  scale / shift of all stage-1 norms + their running statistics                               (cat_tnorm_finalize)
     dw        all depthwise convs as one launch, norm + ReLU of stage 1 applied while staging             (cat_dwm_fwd)
     finalize
@@ -42,6 +43,13 @@ _ONLY = os.environ.get('CAT_FUSED_SPADE', '1') if os.environ.get('CAT_FUSED_SPAD
 
 _SYNC_FUSED = os.environ.get('CAT_FUSED_SPADE_SYNC', '1') != '0'      # fused units under SynchronizedBatchNorm over several ranks (round 4)
 _S1_DGRAD = os.environ.get('CAT_FUSED_SPADE_S1_DGRAD', '1') != '0'     # A/B switch: the second convs' input gradients as one launch
+# Units with a 7 x 7 branch (the reference's parser default --kernel_sizes 3 5 7) take this path under CAT_FUSED_SPADE_K7=1 / set_k7(True), in
+# both forms: their 7 x 7 convs on the wide-patch LDS-tile kernels (csrc/conv_pk7.hip), their depthwise stage on the 7 x 7 frame
+# (cat_dwm7_fwd / cat_dwm7_bwd), stage 1 and the second convs' input gradients as ONE launch each where the widths allow
+# (cat_tstage1n7_fwd / cat_tstage1n7_dgrad, csrc/conv_s1n7.hip).  With it off such units run layer by layer, as they always did, and
+# `applicable` is the function it was.  On by default: the graphed GauGAN distillation step with kernel sizes 3 5 7 at 512 x 256, batch 4,
+# measured 73.52 ms on this path against 81.86 ms layer by layer (the parent commit), spreads 1.47 and 2.47 ms (profiles/spade_k7_bench.txt)
+_K7 = os.environ.get('CAT_FUSED_SPADE_K7', '1') != '0'
 _UNITS = os.environ.get('CAT_FUSED_SPADE_UNITS', 'all')      # A/B switch: 'gb' / 'main' = only the gamma|beta nets / only the main units
 STATS = {'train_fwd': 0, 'frozen_fwd': 0, 'bwd': 0, 'collectives': 0}      # calls per form; statistics exchanges issued (tests / diagnostics)
 
@@ -49,6 +57,12 @@ STATS = {'train_fwd': 0, 'frozen_fwd': 0, 'bwd': 0, 'collectives': 0}      # cal
 def set_enabled(on):
     global _ENABLED
     _ENABLED = bool(on)
+
+
+def set_k7(on):
+    global _K7
+    old, _K7 = _K7, bool(on)
+    return old
 
 
 def _conv_of(m):
@@ -113,7 +127,7 @@ def applicable(res_ops, dw_ops, x, training):
             return False
         k2 = 1 if dw else b['k']
         ks = [b['k'], b.get('kd', 1), b['conv2'].kernel_size[0]]
-        if any(k not in (1, 3, 5) for k in ks) or b['conv2'].kernel_size[0] != k2:
+        if any(k not in ((1, 3, 5, 7) if _K7 else (1, 3, 5)) for k in ks) or b['conv2'].kernel_size[0] != k2:
             return False
         if b['conv1'].padding[0] != (b['k'] - 1) // 2 or b['conv2'].padding[0] != (k2 - 1) // 2:
             return False
@@ -143,12 +157,20 @@ class _Plan(U.Plan):
                 if id(q) not in seen:
                     seen.add(id(q))
                     params.append(q)
+        # fused_unit.stage1 takes the narrow one-launch 3 5 7 kernel (cat_tstage1n7_fwd) only for plans that carry this
+        self.stage1_n7 = _K7
         super().__init__(res, dws, cin, cout, dev, params)
 
     def _merges_dw_dgrad(self):
         """The second convs' input gradients as ONE launch (cat_tstage1_dgrad: dT is staged once for the 5 x 5 and the 3 x 3 residual branch
-        and the N-concatenated 1 x 1 second convs of the depthwise branches) where a kernel exists for the widths."""
+        and the N-concatenated 1 x 1 second convs of the depthwise branches; cat_tstage1n7_dgrad: the same with exactly one 7 x 7, one 5 x 5
+        and one 3 x 3 residual branch, `s1d7`) where a kernel exists for the widths."""
         r5, r3 = [b for b in self.res if b['k'] == 5], [b for b in self.res if b['k'] == 3]
+        r7 = [b for b in self.res if b['k'] == 7]
+        if _S1_DGRAD and len(r7) == 1 and len(r5) == 1 and len(r3) == 1 and self.dws and \
+                L.query('cat_tstage1n7_supported', r7[0]['w1'], r5[0]['w1'], r3[0]['w1'], self.hcd):
+            self.s1d7 = (r7[0], r5[0], r3[0])      # ... with one more slot: cat_tstage1n7_dgrad (p.s1d stays None)
+            return True
         if _S1_DGRAD and len(r5) == 1 and len(r3) == 1 and self.dws and L.query('cat_tstage1_dgrad_supported', r5[0]['w1'], r3[0]['w1'], self.hcd):
             self.s1d = (r5[0], r3[0])
         return self.s1d is not None

@@ -1,6 +1,6 @@
 """The fused inception block (cat_amd/fused_block.py) and the fused six-branch SPADE unit (cat_amd/fused_spade.py) are ONE pipeline
 
-    stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tstage1ws_fwd / cat_tstage1ws7_fwd / cat_tconv_fwd)
+    stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tstage1ws_fwd / cat_tstage1ws7_fwd / cat_tstage1n7_fwd / cat_tconv_fwd)
     finalize  scale / shift of all stage-1 norms + their running statistics                               (cat_tnorm_finalize)
     dw        all depthwise convs (one launch per <= 18 / 24 channel quads), norm + activation of stage 1 applied while staging   (cat_dwm_fwd;
               cat_dwm7_fwd for a plan with a 7 x 7 depthwise branch)
@@ -23,9 +23,9 @@ each a plan property or an argument, never "which caller":
                       a generator over those exchanges; whoever drives it performs them)
     drop              an optional dropout ticket: the stage-2 operands are then materialised with their masks
 
-plus, in the backward pass, p.s1d (the second convs' input gradients as one cat_tstage1_dgrad launch), p.wgrad_batch (weight-gradient
-partials reduced by one launch when there are no branch streams) and `skip_grad` (a skip connection's share of the input gradient).  The
-callers keep their stage-2 launch and tail (the block's closing pw_bn and residual; the unit's epilogue addend), their plan subclass and
+plus, in the backward pass, p.s1d / p.s1d7 (the second convs' input gradients as one cat_tstage1_dgrad / cat_tstage1n7_dgrad launch),
+p.wgrad_batch (weight-gradient partials reduced by one launch when there are no branch streams) and `skip_grad` (a skip connection's share
+of the input gradient).  The callers keep their stage-2 launch and tail (the block's closing pw_bn and residual; the unit's epilogue addend), their plan subclass and
 the autograd Functions."""
 import ctypes as C
 import os
@@ -103,7 +103,8 @@ class Plan:
     branches' 1 x 1 second convs get an N-concatenated input-gradient filter stream (`dpack2_dw`).  What the pipeline reads beyond the
     layout, with the defaults a subclass overrides: `reflect` / `instance` / `affine` (padding, per-sample statistics, norms with
     gamma / beta), `s1d` (the two residual branches whose second-conv input gradients join the depthwise ones in ONE cat_tstage1_dgrad
-    launch, or None) and `wgrad_batch` (on one stream the weight-gradient partial sums are reduced by one launch, ops.WgradBatch)."""
+    launch, or None), `s1d7` (the same for the three residual branches 7 x 7, 5 x 5, 3 x 3 of a 3 5 7 unit: ONE cat_tstage1n7_dgrad) and
+    `wgrad_batch` (on one stream the weight-gradient partial sums are reduced by one launch, ops.WgradBatch)."""
     what = 'fused unit'
     GAMMA0 = 0.0
     reflect = instance = False
@@ -114,6 +115,7 @@ class Plan:
         return self.instance or self.shards > 1
     affine = True
     s1d = None
+    s1d7 = None
     wgrad_batch = False
 
     def __init__(self, res, dws, cin, cout, dev, params, dw_maxq=L.DWM_MAXQ_BWD):
@@ -386,8 +388,10 @@ def prepare_plans(plans, group, backward=False):
 # ---------------------------------------------------------------------------------------------------------------- forward stages
 def stage1(p, x, z1, part1, reflect=False):
     """First convs of all branches: x -> channel slices of Z1 (pre-norm) + tile statistics into part1.  part1 None: the eval form, no
-    statistics (always one launch per kernel size).  The one-launch kernels take exactly the kernel sizes 5, 3 and 1, or -- the wide
-    widths only -- 7, 5, 3 and 1: a plan with another set (fewer sizes; a 7 x 7 first conv at narrow widths) runs one launch per size."""
+    statistics (always one launch per kernel size).  The one-launch kernels take exactly the kernel sizes 5, 3 and 1, or 7, 5, 3 and 1 -- at
+    the wide widths, or at narrow widths for a plan that carries `stage1_n7` (the GauGAN units under CAT_FUSED_SPADE_K7; the plans of
+    fused_block.py and frozen_in.py do not carry it: their narrow 3 5 7 launch order, one launch per size, is pinned by their tests, and
+    adopting the narrow kernel there is a later, measured decision).  A plan with another set of sizes runs one launch per size."""
     n, c, h, w = x.shape
     by_k = {g['k']: g for g in p.groups}
     sizes = (5, 3, 1)
@@ -400,6 +404,9 @@ def stage1(p, x, z1, part1, reflect=False):
     elif part1 is not None and _STAGE1WS7 and set(by_k) == {1, 3, 5, 7} and (not reflect or (h >= 7 and w >= 7)) and \
             L.query('cat_tstage1ws7_supported', *[by_k[k]['width'] for k in (7, 5, 3, 1)]):
         entry, geom, sizes = 'cat_tstage1ws7_fwd', L.Stage1S7Geom, (7, 5, 3, 1)      # ... with one more slot
+    elif getattr(p, 'stage1_n7', False) and part1 is not None and set(by_k) == {1, 3, 5, 7} and (not reflect or (h >= 7 and w >= 7)) and \
+            L.query('cat_tstage1n7_supported', *[by_k[k]['width'] for k in (7, 5, 3, 1)]):
+        entry, geom, sizes = 'cat_tstage1n7_fwd', L.Stage1S7Geom, (7, 5, 3, 1)       # the narrow widths of a plan that asks for it
     if entry is not None:
         # one launch: the kernel sizes share every staged input tile
         gs = geom()
@@ -769,7 +776,7 @@ def backward_g(p, dt, x, z1, ss1, mr1, zd, ssd, mrd, *, need_dx, skip_grad=None,
             return ops._conv_geom(n, h, w, m, scs_, h, w, p.Cout, p.cso, k2, k2, 1, pad2, mode2, wcs=ops._grad_wcs(dst_)), xptr, ops._p(dt)
         if res or not p.merge2:
             put_wgrad(b['conv2'].weight, kw)
-        if (not res and p.dpack2_dw is not None) or (p.s1d is not None and any(b is r for r in p.s1d)):
+        if (not res and p.dpack2_dw is not None) or any(b is r for r in (p.s1d or ()) + (p.s1d7 or ())):
             continue            # input gradient: the merged launch below
         seg_pad = k2 - 1 - (0 if mode2 == L.PAD_REFLECT else pad2)
         seg = tconv.Segment(None, k2, seg_pad, False, b['d2off'], c4=p.cso, cin=p.Cout, xcs=p.cso, ptr=dt.data_ptr())
@@ -780,19 +787,19 @@ def backward_g(p, dt, x, z1, ss1, mr1, zd, ssd, mrd, *, need_dx, skip_grad=None,
         else:
             tconv.run([seg], p.dpack2, None, None, m, n, h, w, h, w, ycs=dcs, ycw=w1, yptr=dst.data_ptr() + 4 * o)
     # ---- 4. merged second-conv input gradients: dT staged once for the 5 x 5 and the 3 x 3 residual branch and the N-concatenated 1 x 1
-    # second convs of the depthwise branches (p.s1d), or those 1 x 1 convs alone as ONE launch over dT into dAd
+    # second convs of the depthwise branches (p.s1d; p.s1d7: and the 7 x 7 one), or those 1 x 1 convs alone as ONE launch over dT into dAd
     nvalid_dw = sum(b['m'] for b in p.dws)
-    if p.s1d is not None:
-        r5, r3 = p.s1d
-        gs = L.Stage1Geom()
+    if p.s1d is not None or p.s1d7 is not None:
+        rs, geom, entry = (p.s1d, L.Stage1Geom, 'cat_tstage1_dgrad') if p.s1d is not None else (p.s1d7, L.Stage1S7Geom, 'cat_tstage1n7_dgrad')
+        ns = len(rs) + 1
+        gs = geom()
         gs.N, gs.H, gs.W, gs.xcs, gs.cin, gs.reflect, gs.ycs, gs.scs = n, h, w, p.cso, p.Cout, 0, 0, 0
-        packs, dxs, dxcs = (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_int * 3)(p.hc1, p.hc1, p.hcd)
-        for slot, (col0, width, nvalid, pk, dst) in enumerate(((r5['o1'], r5['w1'], r5['m'], p.dpack2.data_ptr() + 4 * r5['d2off'], da1),
-                                                               (r3['o1'], r3['w1'], r3['m'], p.dpack2.data_ptr() + 4 * r3['d2off'], da1),
-                                                               (0, p.hcd, nvalid_dw, p.dpack2_dw.data_ptr(), dad))):
+        packs, dxs, dxcs = (C.c_void_p * ns)(), (C.c_void_p * ns)(), (C.c_int * ns)(*([p.hc1] * len(rs) + [p.hcd]))
+        slots = [(r['o1'], r['w1'], r['m'], p.dpack2.data_ptr() + 4 * r['d2off'], da1) for r in rs] + [(0, p.hcd, nvalid_dw, p.dpack2_dw.data_ptr(), dad)]
+        for slot, (col0, width, nvalid, pk, dst) in enumerate(slots):
             gs.col0[slot], gs.width[slot], gs.nvalid[slot] = col0, width, nvalid
             packs[slot], dxs[slot] = pk, dst.data_ptr()
-        L.call('cat_tstage1_dgrad', C.byref(gs), ops._p(dt), packs, dxs, dxcs, ops._stream())
+        L.call(entry, C.byref(gs), ops._p(dt), packs, dxs, dxcs, ops._stream())
     elif p.dws and p.dpack2_dw is not None:
         seg = tconv.Segment(None, 1, 0, False, 0, c4=p.cso, cin=p.Cout, xcs=p.cso, ptr=dt.data_ptr())
         tconv.run([seg], p.dpack2_dw, None, None, p.hcd, n, h, w, h, w, ycs=p.hcd, ycw=p.hcd, yptr=dad.data_ptr(), nvalid=nvalid_dw)

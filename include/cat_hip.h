@@ -682,6 +682,21 @@ typedef struct {
 int cat_tstage1ws7_supported(int w7, int w5, int w3, int w1);
 int cat_tstage1ws7_fwd(const cat_tstage1s7_t* g, const float* x, const float* const* packs, const float* bias, float* y, float* stats,
                        cat_stream_t stream);
+/* The NARROW one-launch stage 1 for the kernel sizes 3 5 7 (csrc/conv_s1n7.hip): cat_tstage1_fwd with one more slot, for the pruned / student
+ * widths of the GauGAN generator's six-branch units (inception_modules.py:428-505, 648-700).  Slot order 7, 5, 3, 1; arguments and output
+ * contract of cat_tstage1ws7_fwd (column slices of the pre-norm buffer y, bias added, no activation, padding columns of a slice as 0, the
+ * per-tile statistics into the same columns of `stats`, which is required).  Zero and reflect padding; reflect needs H, W >= 7.
+ * cat_tstage1n7_supported(slot widths): every width > 0, at most 32 columns (2 N tiles) per wide slot and 64 (4 N tiles) for the 1 x 1
+ * slot -- every combination has a kernel. */
+int cat_tstage1n7_supported(int w7, int w5, int w3, int w1);
+int cat_tstage1n7_fwd(const cat_tstage1s7_t* g, const float* x, const float* const* packs, const float* bias, float* y, float* stats,
+                      cat_stream_t stream);
+/* cat_tstage1_dgrad with four slots: the same kernel reading dy -- slots 0..2 = the 7 x 7, 5 x 5 and 3 x 3 residual branch, slot 3 = the
+ * N-concatenated 1 x 1 second convs of the depthwise branches -- with transposed / flipped filter streams (cat_prep_run kind 0 mode 1);
+ * slot k writes columns [col0[k], col0[k] + width[k]) of its OWN buffer dxs[k] with pixel stride dxcs[k].  Zero padding only (g->reflect
+ * must be 0); g->ycs / scs are ignored (no statistics, no bias).  Widths: cat_tstage1n7_supported. */
+int cat_tstage1n7_dgrad(const cat_tstage1s7_t* g, const float* dy, const float* const* packs, float* const* dxs, const int* dxcs,
+                        cat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Quad-granule LDS-tile convolution (csrc/conv_q.hip, round 4): the same K-segment model as cat_tconv_fwd on v_mfma_f32_4x4x1_16B_f32 --
