@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libcat_hip.so')
-SOURCES = ['runtime.hip', 'conv_igemm.hip', 'conv_smallco.hip', 'conv_pk.hip', 'conv_pk7.hip', 'conv_s1ws.hip', 'conv_s1w7.hip', 'conv_s1ws7.hip', 'conv_s1n7.hip', 'conv_ksum.hip', 'conv_q.hip', 'conv_split.hip', 'conv_twgrad.hip', 'conv_pwgrad.hip', 'block_norm.hip', 'dwconv.hip', 'norm.hip', 'elementwise.hip', 'ka_loss.hip', 'loss_multi.hip', 'spade.hip', 'eval_ops.hip', 'seg_ops.hip', 'dropout.hip', 'kid_ops.hip', 'fid_ops.hip', 'pixel_d.hip', 'image_ops.hip', 'image_pool.hip', 'data_ops.hip']
+SOURCES = ['runtime.hip', 'conv_igemm.hip', 'conv_smallco.hip', 'conv_pk.hip', 'conv_pk7.hip', 'conv_s1ws.hip', 'conv_s1w7.hip', 'conv_s1ws7.hip', 'conv_s1n7.hip', 'conv_ksum.hip', 'conv_q.hip', 'conv_split.hip', 'conv_twgrad.hip', 'conv_pwgrad.hip', 'block_norm.hip', 'dwconv.hip', 'norm.hip', 'norm_resident.hip', 'elementwise.hip', 'ka_loss.hip', 'loss_multi.hip', 'spade.hip', 'eval_ops.hip', 'seg_ops.hip', 'dropout.hip', 'kid_ops.hip', 'fid_ops.hip', 'pixel_d.hip', 'image_ops.hip', 'image_pool.hip', 'data_ops.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 
 
@@ -34,7 +34,7 @@ def build(force=False, verbose=True, diag=False):
     """diag=True: the DIAGNOSTIC build (-DCAT_DIAG, common.h kDiag) into lib/libcat_hip_diag.so -- per-phase shader clocks and the
     ablation switches that make results wrong by design; only tools/debug/* load it (CAT_LIB=diag).  Never built by build() / the driver."""
     os.makedirs(LIBDIR, exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in ('common.h', 'mfma_f64.h', 'conv_pk_tile.h', 'conv_pk_s1w_main.h', 'conv_pk_tconv_main.h', 'conv_s1w7_main.h', 'conv_s1w7_stage.h', 'conv_s1ws_epilogue.h', 'conv_s1_epilogue.h')] + [ os.path.join(HERE, '..', 'include', 'cat_hip.h')]
+    hdrs = [os.path.join(CSRC, h) for h in ('common.h', 'norm_plan.h', 'mfma_f64.h', 'conv_pk_tile.h', 'conv_pk_s1w_main.h', 'conv_pk_tconv_main.h', 'conv_s1w7_main.h', 'conv_s1w7_stage.h', 'conv_s1ws_epilogue.h', 'conv_s1_epilogue.h')] + [ os.path.join(HERE, '..', 'include', 'cat_hip.h')]
     hipcc = _hipcc()
     objs, jobs = [], []
     for s in SOURCES:

@@ -265,6 +265,9 @@ SIGNATURES = {
     'cat_norm_ws_bytes': (C.c_size_t, [_NG]),
     'cat_norm_fwd': (c_i, [_NG, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     'cat_norm_bwd': (c_i, [_NG, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    'cat_norm_launches': (c_i, [_NG, c_i, c_i]),
+    'cat_norm_resident_max_pixels': (c_i, [c_i]),
+    'cat_norm_set_resident': (c_i, [c_i]),
     'cat_bn_fold': (c_i, [c_p, c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_p]),
     'cat_affine_act_fwd': (c_i, [c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_f, c_p]),
     'cat_act_fwd': (c_i, [c_p, c_p, c_l, c_i, c_f, c_p]),

@@ -1,41 +1,19 @@
 // InstanceNorm2d / BatchNorm2d (training statistics) fused with the following activation, NHWC, gfx950.
-// HBM-bound: forward = 2 reads + 1 write of the activation, backward = 4 reads + 1 write.
+// HBM-bound: forward = 2 reads + 1 write of the activation, backward = 4 reads + 1 write.  Groups small enough for one workgroup's registers
+// take the one-launch kernels of norm_resident.hip instead (cat_norm_launches tells which).
 //   pass 1  per-(group, channel) shifted sums   sum(x - x0), sum((x - x0)^2)   -> deterministic partials in ws
 //   pass 2  finalize: mean / rstd (biased var, eps inside the sqrt), running stats, per-(group,channel) scale+shift
 //   pass 3  y = act(x * scale + shift), float4 per lane
 // Reduction layout and block combine of pass 1: cat::ColPlan / col_lanes / col_block_store (common.h); the pass-3 pixel walks use the same lanes.
-#include "common.h"
+#include "norm_plan.h"
 #include <limits.h>
 #include <stdlib.h>
 
 namespace {
 using cat::cdiv;
 
-struct NormPlan : cat::ColPlan {
-  int G, Pg, Ptot;      // Ptot = all pixels: a sharded batch norm's last group may hold fewer than Pg
-  size_t part_off, scale_off, shift_off, c1_off, c2_off, bytes;
-};
-
-NormPlan plan(const cat_norm_t* g) {
-  int G = g->mode == CAT_NORM_INSTANCE ? g->N : 1, Pg = g->mode == CAT_NORM_INSTANCE ? g->HW : g->N * g->HW;
-  if (g->mode == CAT_NORM_BATCH && g->shards > 1) {      // torch.chunk(batch, shards): groups of ceil(N / shards) consecutive samples
-    const int per = cdiv(g->N, g->shards);
-    G = cdiv(g->N, per);
-    Pg = per * g->HW;
-  }
-  NormPlan p{cat::col_plan(Pg, g->cs, G, 2048, 16, 1024)};   // stats: ~2048 workgroups, at most 1024 per group, >= 16 pixels per pixel lane
-  p.G = G;
-  p.Pg = Pg;
-  p.Ptot = g->N * g->HW;
-  size_t off = 0;
-  p.part_off = off; off += (size_t)p.G * p.nb * 2 * g->cs;
-  p.scale_off = off; off += (size_t)p.G * g->cs;
-  p.shift_off = off; off += (size_t)p.G * g->cs;
-  p.c1_off = off; off += (size_t)p.G * g->cs;
-  p.c2_off = off; off += (size_t)p.G * g->cs;
-  p.bytes = off * sizeof(float);
-  return p;
-}
+using cat::NormPlan;
+NormPlan plan(const cat_norm_t* g) { return cat::norm_plan(g); }      // norm_plan.h: shared with the one-launch kernels of norm_resident.hip
 
 // MODE 0: forward stats of x.  MODE 1: backward stats: sum(g), sum(g * xhat) with g = dy * act'(pre).
 template <int MODE>
@@ -409,10 +387,20 @@ int cat_norm_fwd(const cat_norm_t* g, const float* x, const float* gamma, const 
                  cat_stream_t stream) {
   CAT_REQUIRE(g->cs % 4 == 0 && g->cs >= g->C && g->N > 0 && g->HW > 0, "norm: bad geometry");
   CAT_REQUIRE(ws && save_mean && save_rstd, "norm fwd: workspace / save buffers required");
-  cat::ProfScope prof("norm_fwd", 0.0, 3 * 4.0 * (double)g->N * g->HW * g->cs, stream);
   const NormPlan p = plan(g);
+  const cat::ResidentPlan res = cat::norm_resident_plan(p, g->cs, 0);
+  cat::ProfScope prof("norm_fwd", 0.0, (res.ok ? 2 : 3) * 4.0 * (double)g->N * g->HW * g->cs, stream);
   float* w = (float*)ws;
   hipStream_t s = (hipStream_t)stream;
+  if (res.ok) {      // a small group: statistics and apply in one launch (norm_resident.hip), the workspace stays untouched
+    const bool bn = g->mode == CAT_NORM_BATCH;
+    cat::norm_resident_fwd(g, p, res, x, gamma, beta, y, save_mean, save_rstd, bn ? running_mean : nullptr, bn ? running_var : nullptr,
+                           bn ? num_batches_tracked : nullptr, s);
+    if (!bn && running_mean && running_var)
+      in_running_kernel<<<cdiv(g->C, 256), 256, 0, s>>>(save_mean, save_rstd, running_mean, running_var, p.G, p.Pg, g->C, g->eps, g->momentum,
+                                                         num_batches_tracked);
+    return cat::check_launch("norm_fwd");
+  }
   norm_stats_kernel<0><<<dim3(p.nb, p.G, p.nz), 256, 0, s>>>(x, nullptr, nullptr, nullptr, nullptr, nullptr, w + p.part_off, p.Pg,
                                                               p.Ptot, g->C, g->cs, p.zq, p.ppl, p.nb, 0, 0.f);
   norm_fwd_finalize_kernel<<<dim3(cdiv(g->cs, 4), p.G), 256, 0, s>>>(x, w + p.part_off, gamma, beta, save_mean, save_rstd,
@@ -438,10 +426,19 @@ int cat_norm_bwd(const cat_norm_t* g, const float* x, const float* dy, const flo
                  const float* save_rstd, float* dx, float* dgamma, float* dbeta, int accumulate, void* ws, cat_stream_t stream) {
   CAT_REQUIRE(g->cs % 4 == 0 && g->cs >= g->C && g->N > 0 && g->HW > 0, "norm: bad geometry");
   CAT_REQUIRE(ws, "norm bwd: workspace required");
-  cat::ProfScope prof("norm_bwd", 0.0, 5 * 4.0 * (double)g->N * g->HW * g->cs, stream);
   const NormPlan p = plan(g);
+  const cat::ResidentPlan res = cat::norm_resident_plan(p, g->cs, 1);
+  cat::ProfScope prof("norm_bwd", 0.0, (res.ok ? 3 : 5) * 4.0 * (double)g->N * g->HW * g->cs, stream);
   float* w = (float*)ws;
   hipStream_t s = (hipStream_t)stream;
+  if (res.ok) {      // one launch (norm_resident.hip); with several groups the parameter gradients still sum the per-group means in a second one
+    const bool params = p.G > 1 && (dgamma || dbeta);
+    cat::norm_resident_bwd(g, p, res, x, dy, gamma, beta, save_mean, save_rstd, dx, params ? w + p.c1_off : nullptr,
+                           params ? w + p.c2_off : nullptr, p.G == 1 ? dgamma : nullptr, p.G == 1 ? dbeta : nullptr, accumulate, s);
+    if (params)
+      norm_bwd_param_kernel<<<cdiv(g->C, 256), 256, 0, s>>>(w + p.c1_off, w + p.c2_off, dgamma, dbeta, p.G, p.Pg, p.Ptot, g->C, g->cs, accumulate);
+    return cat::check_launch("norm_bwd");
+  }
   norm_stats_kernel<1><<<dim3(p.nb, p.G, p.nz), 256, 0, s>>>(x, dy, gamma, beta, save_mean, save_rstd, w + p.part_off, p.Pg, p.Ptot, g->C, g->cs,
                                                               p.zq, p.ppl, p.nb, g->act, g->slope);
   const bool one_group = p.G == 1;

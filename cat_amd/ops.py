@@ -692,6 +692,12 @@ class DwConv2dFn(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------------- normalisation
+def set_norm_resident(on):
+    """Switch the one-launch kernels of small statistic groups (csrc/norm_resident.hip, cat_norm_set_resident; initial value: CAT_NORM_RESIDENT)
+    on or off for every cat_norm_fwd / cat_norm_bwd of this process; returns the previous value."""
+    return bool(L.query('cat_norm_set_resident', int(bool(on))))
+
+
 class NormActFn(torch.autograd.Function):
     """InstanceNorm2d / BatchNorm2d with batch statistics, fused with the activation behind it."""
 

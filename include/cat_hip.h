@@ -164,6 +164,18 @@ int cat_norm_fwd(const cat_norm_t* g, const float* x, const float* gamma, const 
 int cat_norm_bwd(const cat_norm_t* g, const float* x, const float* dy, const float* gamma, const float* beta,
                  const float* save_mean, const float* save_rstd, float* dx, float* dgamma, float* dbeta,
                  int accumulate, void* ws, cat_stream_t stream);
+/* Small statistic groups run cat_norm_fwd / cat_norm_bwd in ONE launch (csrc/norm_resident.hip): a workgroup keeps every pixel of a group for
+ * a slab of channels in registers, so the activation is read once and the workspace is not touched.  The domain follows from the geometry
+ * alone: at most cat_norm_resident_max_pixels(backward) pixels per group (a sample for InstanceNorm, the batch or a shard for BatchNorm);
+ * a forward whose groups need one-quad slabs (more than 2048 pixels) of a pixel wider than 4 channels keeps the three launches when the
+ * activation is larger than 12 MiB (measured slower there, profiles/norm_resident_bench.txt).
+ * cat_norm_launches: kernels the call issues for this geometry under the current switch -- forward 1 or 3 (an InstanceNorm with running
+ * statistics adds its update launch, which depends on the arguments and is not counted); backward 1 or 3, plus the parameter-gradient launch
+ * when with_param_grads and there is more than one group.  All three are pure host functions.
+ * cat_norm_set_resident: switch the one-launch kernels on / off, returns the previous value (initial value: CAT_NORM_RESIDENT, default 0). */
+int cat_norm_launches(const cat_norm_t* g, int backward, int with_param_grads);
+int cat_norm_resident_max_pixels(int backward);
+int cat_norm_set_resident(int on);
 /* Inference-mode norm: y = act(x * scale[c] + shift[c]) (BatchNorm eval with running stats folded by
  * cat_bn_fold; used by the frozen teacher, distillers/base_inception_distiller.py:168). */
 int cat_bn_fold(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
