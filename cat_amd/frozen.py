@@ -171,8 +171,13 @@ def _build_plan(block):
         order = [by_k[7], by_k[5], by_k[3]]
         s1w7 = dict(packs=None, ws=[wd['wf'] for wd in order] + [w_a], biases=[wd['bf'] for wd in order] + [b_a.contiguous()],
                     m=[wd['m'] for wd in order] + [hc])
+    # the k = 1 res slots come first and are contiguous from lane 0: ONE copy of their whole range.  cat_slice_channels writes all ycs lanes
+    # of every pixel, so a copy per slot into h2 + 4 * o zeroed o floats of the next pixel (the slots before it) and, behind the last pixel,
+    # o floats past the buffer
+    res_w = sum(sz for (kind, _), (o, m, sz) in zip(slots, offs) if kind == 'res')
+    assert all(o < res_w for (kind, _), (o, m, sz) in zip(slots, offs) if kind == 'res')
     return dict(s1w=s1w, s1w7=s1w7, tail_pack=None, tail_offs=None, hc=hc, dwm=dwm, w_a=w_a, b_a=b_a.contiguous(), w_f=w_f, b_f=b_f.contiguous(), dws=dws, wides=wides, act=act, slope=slope,
-                pad_mode=pad_mode, copies=[(o, sz) for (kind, _), (o, m, sz) in zip(slots, offs) if kind == 'res'])
+                pad_mode=pad_mode, copies=[(0, res_w)] if res_w else [])
 
 
 def block_forward(block, x):
