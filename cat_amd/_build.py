@@ -1,5 +1,6 @@
 """Build libcat_hip.so (gfx950) in-tree with hipcc.  No cmake / torch extension machinery: the library is a
 plain C-ABI shared object (include/cat_hip.h) that ctypes loads."""
+import glob
 import os
 import subprocess
 import sys
@@ -34,7 +35,7 @@ def build(force=False, verbose=True, diag=False):
     """diag=True: the DIAGNOSTIC build (-DCAT_DIAG, common.h kDiag) into lib/libcat_hip_diag.so -- per-phase shader clocks and the
     ablation switches that make results wrong by design; only tools/debug/* load it (CAT_LIB=diag).  Never built by build() / the driver."""
     os.makedirs(LIBDIR, exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in ('common.h', 'norm_plan.h', 'mfma_f64.h', 'conv_pk_tile.h', 'conv_pk_s1w_main.h', 'conv_pk_tconv_main.h', 'conv_s1w7_main.h', 'conv_s1w7_stage.h', 'conv_s1ws_epilogue.h', 'conv_s1_epilogue.h')] + [ os.path.join(HERE, '..', 'include', 'cat_hip.h')]
+    hdrs = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + [os.path.join(HERE, '..', 'include', 'cat_hip.h')]   # every object depends on every header
     hipcc = _hipcc()
     objs, jobs = [], []
     for s in SOURCES:

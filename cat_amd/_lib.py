@@ -96,20 +96,16 @@ class NSlice(C.Structure):
     _fields_ = [('c0', c_i), ('c', c_i), ('running_mean', c_p), ('running_var', c_p), ('num_batches', c_p)]
 
 
-class Stage1Geom(C.Structure):
-    _fields_ = [(n, c_i) for n in ('N', 'H', 'W', 'xcs', 'cin', 'reflect', 'ycs', 'scs')] + [('col0', c_i * 3), ('width', c_i * 3), ('nvalid', c_i * 3)]
+def _stage1_geom(name, slots, slices):
+    """Geometry of a one-launch stage 1 with `slots` kernel sizes (3: 5 3 1; 4: 7 5 3 1).  slices: the column-slice contract (cat_tstage1_t /
+    cat_tstage1s7_t: slices of one buffer + statistics), else one buffer per slot + activation (cat_tstage1w_t / cat_tstage1w7_t)."""
+    head = [(n, c_i) for n in ('N', 'H', 'W', 'xcs', 'cin', 'reflect')]
+    tail = [('ycs', c_i), ('scs', c_i), ('col0', c_i * slots), ('width', c_i * slots)] if slices else [('act', c_i), ('slope', c_f), ('ycs', c_i * slots)]
+    return type(name, (C.Structure,), {'_fields_': head + tail + [('nvalid', c_i * slots)]})
 
 
-class Stage1S7Geom(C.Structure):      # cat_tstage1s7_t: Stage1Geom with four slots (7, 5, 3, 1)
-    _fields_ = [(n, c_i) for n in ('N', 'H', 'W', 'xcs', 'cin', 'reflect', 'ycs', 'scs')] + [('col0', c_i * 4), ('width', c_i * 4), ('nvalid', c_i * 4)]
-
-
-class Stage1WGeom(C.Structure):
-    _fields_ = [(n, c_i) for n in ('N', 'H', 'W', 'xcs', 'cin', 'reflect', 'act')] + [('slope', c_f), ('ycs', c_i * 3), ('nvalid', c_i * 3)]
-
-
-class Stage1W7Geom(C.Structure):
-    _fields_ = [(n, c_i) for n in ('N', 'H', 'W', 'xcs', 'cin', 'reflect', 'act')] + [('slope', c_f), ('ycs', c_i * 4), ('nvalid', c_i * 4)]
+Stage1Geom, Stage1S7Geom = _stage1_geom('Stage1Geom', 3, True), _stage1_geom('Stage1S7Geom', 4, True)
+Stage1WGeom, Stage1W7Geom = _stage1_geom('Stage1WGeom', 3, False), _stage1_geom('Stage1W7Geom', 4, False)
 
 
 class DwmGeom(C.Structure):

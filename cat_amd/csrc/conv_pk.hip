@@ -26,6 +26,8 @@
 #include "common.h"
 #include "conv_pk_tile.h"
 #include "conv_s1_epilogue.h"
+#include "conv_s1_host.h"
+#include "conv_s1w_store.h"
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -48,7 +50,8 @@ __global__ __launch_bounds__(256) void tconv_kernel(const cat_tconv_t g, const f
 // All first convs of an InvertedResidualChannels block (inception_modules.py:135-147,150-165: the 5x5, the 3x3 and the N-concatenated
 // 1x1 convs of every branch) from ONE staging of the input tile per 16-channel chunk: three accumulator sets (NA / NB / NC 16-wide
 // tiles), three filter streams, outputs = three channel slices of the pre-norm buffer + their per-tile statistics.  The narrow convs
-// alone cannot hide their own staging latency (a 3x3 chunk is ~1 us of MFMA work); together a chunk carries ~7 us.
+// alone cannot hide their own staging latency (a 3x3 chunk is ~1 us of MFMA work); together a chunk carries ~7 us.  This kernel, the
+// frozen teacher's below and their siblings in conv_s1*.hip side by side: docs/CONV_VARIANTS.md, "Stage 1 in one launch".
 struct S1Args {
   const float* x; const float* pack[3]; const float* bias; float* ys[3]; float* stats;   // ys / ycs3: output buffer and pixel stride per slot
   int xcs, c4, N, H, W, reflect, ycs3[3], scs;
@@ -193,26 +196,7 @@ struct S1WArgs {
   int hl, tr, tc, tiles_x, tiles;
 };
 
-template <int NT>
-__device__ __forceinline__ void s1w_store(const f4 (&acc)[2][NT], const S1WArgs& p, int k, int t0, int n, int oy0, int ox0, int wave, int lr, int lq) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int oy = oy0 + 2 * wave + i;
-    if (oy >= p.H) continue;
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      const int ox = ox0 + lq * 4 + rg;
-      if (ox >= p.W) continue;
-      float* yo = p.y[k] + (((int64_t)n * p.H + oy) * p.W + ox) * p.ycs[k];
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int co = (t0 + j) * 16 + lr;
-        if (co < p.nvalid[k]) yo[co] = cat::apply_act(acc[i][j][rg] + (p.bias[k] ? p.bias[k][co] : 0.f), p.act, p.slope);
-        else if (co < p.ycs[k]) yo[co] = 0.f;
-      }
-    }
-  }
-}
+// s1w_store (bias + activation into the slot's buffer): conv_s1w_store.h, shared with tstage1w7_kernel (conv_s1w7.hip)
 
 template <int N5, int N3, int N1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void tstage1w_kernel(const S1WArgs p) {
@@ -376,38 +360,28 @@ int cat_tconv_fwd(const cat_tconv_t* g, const float* pack, const float* bias, fl
 
 static int tstage1_launch(const cat_tstage1_t* g, const float* x, const float* const* packs, const float* bias, float* const* ys,
                           const int* ycs3, float* stats, const char* what, cat_stream_t stream) {
-  CAT_REQUIRE(g->N > 0 && g->H > 0 && g->W > 0 && g->cin > 0 && (g->xcs & 3) == 0 && g->xcs >= g->cin, "tstage1: bad input geometry");
-  CAT_REQUIRE((int64_t)g->N * g->H * g->W * g->xcs < (int64_t)4294967295LL, "tstage1: source larger than 2^32 elements");
   cat_pk::S1Args a{};
-  a.x = x; a.bias = bias; a.stats = stats;
-  a.xcs = g->xcs; a.c4 = (g->cin + 3) & ~3; a.N = g->N; a.H = g->H; a.W = g->W; a.reflect = g->reflect; a.scs = g->scs;
+  a.bias = bias; a.stats = stats; a.scs = g->scs;
   int nt[3];
-  double kflops = 0.0;
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < 3; ++k) {      // a slot of width 0 is left out
     nt[k] = g->width[k] > 0 ? cat::cdiv(g->width[k], 16) : 0;
     a.pack[k] = nt[k] ? packs[k] : x;     // a valid address for the (unused) buffer resource
     a.ys[k] = ys[k]; a.ycs3[k] = ycs3[k];
     a.nt_total[k] = nt[k]; a.col0[k] = g->col0[k]; a.width[k] = g->width[k]; a.nvalid[k] = g->nvalid[k];
     CAT_REQUIRE(nt[k] == 0 || (packs[k] && ys[k] && (ycs3[k] & 3) == 0 && g->col0[k] + g->width[k] <= ycs3[k] && g->nvalid[k] <= g->width[k]),
                 "tstage1: slice %d", k);
-    const int ks = k == 0 ? 5 : (k == 1 ? 3 : 1);
-    kflops += (double)g->nvalid[k] * ks * ks;
   }
-  a.hl = nt[0] ? 2 : (nt[1] ? 1 : 0);
-  CAT_REQUIRE(!g->reflect || (2 * a.hl + 1 <= g->H && 2 * a.hl + 1 <= g->W), "tstage1: reflect padding wider than the plane");
-  a.tr = cat_pk::TH + 2 * a.hl;
-  a.tc = 16 + 2 * a.hl;
-  a.tiles_x = cat::cdiv(g->W, 16);
-  a.tiles = a.tiles_x * cat::cdiv(g->H, cat_pk::TH);
-  const int64_t grid = (int64_t)g->N * a.tiles;
+  const int hl = nt[0] ? 2 : (nt[1] ? 1 : 0);
+  int grid;
+  if (int rc = cat_s1::input(a, g, x, 2 * hl + 1, "tstage1", &grid)) return rc;
   const int nmax = nt[0] > nt[1] ? (nt[0] > nt[2] ? nt[0] : nt[2]) : (nt[1] > nt[2] ? nt[1] : nt[2]);
-  const size_t lds = (size_t)2 * a.tr * a.tc * cat_pk::PITCH * sizeof(float) + 6 * cat_pk::TABN * sizeof(int) + (size_t)8 * nmax * 16 * sizeof(float);
+  const size_t lds = cat_s1::patch(a, hl) + (size_t)8 * nmax * 16 * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-  cat::ProfScope prof(what, 2.0 * (double)g->N * g->H * g->W * g->cin * kflops, 0.0, stream);
+  cat::ProfScope prof(what, cat_s1::flops<3>(g), 0.0, stream);
 #define CAT_S1(NA, NB, NC)                                                                        \
   if (nt[0] == NA && nt[1] == NB && nt[2] == NC) {                                                \
-    if (stats) cat_pk::tstage1_kernel<NA, NB, NC, true><<<(int)grid, 256, lds, s>>>(a);           \
-    else cat_pk::tstage1_kernel<NA, NB, NC, false><<<(int)grid, 256, lds, s>>>(a);                \
+    if (stats) cat_pk::tstage1_kernel<NA, NB, NC, true><<<grid, 256, lds, s>>>(a);                \
+    else cat_pk::tstage1_kernel<NA, NB, NC, false><<<grid, 256, lds, s>>>(a);                     \
     return cat::check_launch(what);                                                               \
   }
   CAT_S1(1, 1, 1) CAT_S1(2, 1, 1) CAT_S1(1, 2, 1) CAT_S1(2, 2, 1)
@@ -426,36 +400,20 @@ int cat_tstage1_fwd(const cat_tstage1_t* g, const float* x, const float* const* 
   return tstage1_launch(g, x, packs, bias, ys, ycs3, stats, "conv_tstage1", stream);
 }
 
-int cat_tstage1w_supported(int w5, int w3, int w1) {
-  return w5 > 32 && w5 <= 48 && w3 > 32 && w3 <= 48 && w1 > 160 && w1 <= 176;      // the instantiation that exists: 3 + 3 + 11 tiles (m = 42)
-}
+int cat_tstage1w_supported(int w5, int w3, int w1) { return cat_s1::wide_531(w5, w3, w1); }
 
 int cat_tstage1w_fwd(const cat_tstage1w_t* g, const float* x, const float* const* packs, const float* const* biases, float* const* ys,
                      cat_stream_t stream) {
-  CAT_REQUIRE(g->N > 0 && g->H > 0 && g->W > 0 && g->cin > 0 && (g->xcs & 3) == 0 && g->xcs >= g->cin, "tstage1w: bad input geometry");
-  CAT_REQUIRE((int64_t)g->N * g->H * g->W * g->xcs < (int64_t)4294967295LL, "tstage1w: source larger than 2^32 elements");
+  cat_pk::S1WArgs a{};
+  int grid;
+  if (int rc = cat_s1::input(a, g, x, 5, "tstage1w", &grid)) return rc;
   CAT_REQUIRE(cat_tstage1w_supported(g->nvalid[0], g->nvalid[1], g->nvalid[2]), "tstage1w: no kernel for %d / %d / %d output channels", g->nvalid[0],
               g->nvalid[1], g->nvalid[2]);
-  CAT_REQUIRE(!g->reflect || (5 <= g->H && 5 <= g->W), "tstage1w: reflect padding wider than the plane");
-  cat_pk::S1WArgs a{};
-  a.x = x; a.xcs = g->xcs; a.c4 = (g->cin + 3) & ~3; a.N = g->N; a.H = g->H; a.W = g->W; a.reflect = g->reflect; a.act = g->act; a.slope = g->slope;
-  double kflops = 0.0;
-  for (int k = 0; k < 3; ++k) {
-    CAT_REQUIRE(packs[k] && ys[k] && (g->ycs[k] & 3) == 0 && g->ycs[k] >= g->nvalid[k] && g->ycs[k] <= (k == 2 ? 176 : 48), "tstage1w: slot %d", k);
-    a.pack[k] = packs[k]; a.bias[k] = biases ? biases[k] : nullptr; a.y[k] = ys[k]; a.ycs[k] = g->ycs[k]; a.nvalid[k] = g->nvalid[k];
-    const int ks = k == 0 ? 5 : (k == 1 ? 3 : 1);
-    kflops += (double)g->nvalid[k] * ks * ks;
-  }
-  a.hl = 2;
-  a.tr = cat_pk::TH + 4;
-  a.tc = 16 + 4;
-  a.tiles_x = cat::cdiv(g->W, 16);
-  a.tiles = a.tiles_x * cat::cdiv(g->H, cat_pk::TH);
-  const int64_t grid = (int64_t)g->N * a.tiles;
-  CAT_REQUIRE(grid < (int64_t)2147483647, "tstage1w: grid too large");
-  const size_t lds = (size_t)2 * a.tr * a.tc * cat_pk::PITCH * sizeof(float) + 6 * cat_pk::TABN * sizeof(int);
-  cat::ProfScope prof("conv_tstage1w", 2.0 * (double)g->N * g->H * g->W * g->cin * kflops, 0.0, stream);
-  cat_pk::tstage1w_kernel<3, 3, 11><<<(int)grid, 256, lds, (hipStream_t)stream>>>(a);
+  const int ycs_max[3] = {48, 48, 176};      // the kernel zeroes the columns [nvalid, ycs) of its own tiles only
+  if (int rc = cat_s1::buffers<3>(a, g, x, packs, biases, ys, ycs_max, "tstage1w")) return rc;
+  const size_t lds = cat_s1::patch(a, 2);
+  cat::ProfScope prof("conv_tstage1w", cat_s1::flops<3>(g), 0.0, stream);
+  cat_pk::tstage1w_kernel<3, 3, 11><<<grid, 256, lds, (hipStream_t)stream>>>(a);
   return cat::check_launch("tstage1w_fwd");
 }
 

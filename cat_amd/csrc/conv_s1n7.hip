@@ -1,11 +1,7 @@
-// Stage 1 of a NARROW six-branch unit with the reference's default kernel sizes 3 5 7 in one launch (cat_tstage1n7_fwd), and the input
-// gradients of such a unit's second convs in one launch (cat_tstage1n7_dgrad): tstage1_kernel (csrc/conv_pk.hip) with one more slot.  The
-// 7 x 7, 5 x 5 and 3 x 3 convs of the residual branches and the N-concatenated 1 x 1 convs of the depthwise branches (inception_modules.py:
-// 428-505: SPADEInvertedResidualChannels; :648-700: the gamma|beta net of InceptionSPADE) share ONE staging of the source tile per
-// 16-channel chunk on the (8 + 6) x (16 + 6) patch of conv_pk7.hip / conv_s1w7_main.h: four A-offset tables, four accumulator sets walked one
-// after the other per chunk (mma_groups, conv_pk_tile.h), four filter streams in cat_tconv_pack / cat_prep_run kind 0 order.  Before, a
-// pruned 3 5 7 unit staged its input with four cat_tconv_fwd launches and its output gradient with four more; on a gamma|beta net (a
-// 36-channel segmentation map, three chunks) each of those launches is almost entirely overhead.
+// cat_tstage1n7_fwd / cat_tstage1n7_dgrad: the narrow 7 5 3 1 stage 1 and the input gradients of such a unit's second convs (the entries
+// side by side: docs/CONV_VARIANTS.md, "Stage 1 in one launch"): tstage1_kernel (csrc/conv_pk.hip) with one more slot on the
+// (8 + 6) x (16 + 6) patch of conv_pk7.hip / conv_s1w7_main.h: four A-offset tables, four accumulator sets walked one after the other per
+// chunk (mma_groups, conv_pk_tile.h), four filter streams in cat_tconv_pack / cat_prep_run kind 0 order.
 //
 // Workgroup = 256 threads = 8 x 16 output pixels, wave w owns rows 2w, 2w + 1.  Epilogue = s1_epilogue (conv_s1_epilogue.h, shared with
 // tstage1_kernel): slot k writes columns [col0[k], col0[k] + width[k]) of its output buffer, bias added, no activation, padding columns as
@@ -20,6 +16,7 @@
 #include "common.h"
 #include "conv_pk_tile.h"
 #include "conv_s1_epilogue.h"
+#include "conv_s1_host.h"
 
 namespace cat_s1n7 {
 
@@ -120,35 +117,25 @@ __global__ __launch_bounds__(256) void tstage1n7_kernel(const Args p) {
 
 static int launch(const cat_tstage1s7_t* g, const float* x, const float* const* packs, const float* bias, float* const* ys, const int* ycs,
                   float* stats, const char* what, const char* family, cat_stream_t stream) {
-  CAT_REQUIRE(g->N > 0 && g->H > 0 && g->W > 0 && g->cin > 0 && (g->xcs & 3) == 0 && g->xcs >= g->cin, "%s: bad input geometry", what);
-  CAT_REQUIRE((int64_t)g->N * g->H * g->W * g->xcs < (int64_t)4294967295LL, "%s: source larger than 2^32 elements", what);
+  Args a{};
+  int grid;
+  if (int rc = cat_s1::input(a, g, x, 7, what, &grid)) return rc;
   CAT_REQUIRE(cat_tstage1n7_supported(g->width[0], g->width[1], g->width[2], g->width[3]), "%s: no kernel for slot widths %d / %d / %d / %d", what,
               g->width[0], g->width[1], g->width[2], g->width[3]);
-  CAT_REQUIRE(!g->reflect || (7 <= g->H && 7 <= g->W), "%s: reflect padding wider than the plane", what);
   CAT_REQUIRE(x && packs && ys && ycs, "%s: null argument", what);
-  Args a{};
-  a.x = x; a.bias = bias; a.stats = stats;
-  a.xcs = g->xcs; a.c4 = (g->cin + 3) & ~3; a.N = g->N; a.H = g->H; a.W = g->W; a.reflect = g->reflect; a.scs = g->scs;
+  if (int rc = cat_s1::slices<NSLOT>(a, g, packs, ys, ycs, stats, what)) return rc;
+  a.bias = bias; a.stats = stats; a.scs = g->scs;
   int nt[NSLOT];
-  double kflops = 0.0;
   for (int k = 0; k < NSLOT; ++k) {
-    CAT_REQUIRE(packs[k] && ys[k] && (ycs[k] & 3) == 0 && g->col0[k] >= 0 && g->col0[k] + g->width[k] <= ycs[k] &&
-                    (!stats || g->col0[k] + g->width[k] <= g->scs) && g->nvalid[k] <= g->width[k],
-                "%s: slice %d", what, k);
     nt[k] = cat::cdiv(g->width[k], 16);
-    a.pack[k] = packs[k]; a.ys[k] = ys[k]; a.ycs3[k] = ycs[k]; a.col0[k] = g->col0[k]; a.width[k] = g->width[k];
-    kflops += (double)g->nvalid[k] * slot_ks(k) * slot_ks(k);
+    a.ys[k] = ys[k]; a.ycs3[k] = ycs[k];
   }
-  a.tiles_x = cat::cdiv(g->W, TW);
-  a.tiles = a.tiles_x * cat::cdiv(g->H, TH);
-  const int64_t grid = (int64_t)g->N * a.tiles;
-  CAT_REQUIRE(grid < (int64_t)2147483647, "%s: grid too large", what);
   hipStream_t s = (hipStream_t)stream;
-  cat::ProfScope prof(family, 2.0 * (double)g->N * g->H * g->W * g->cin * kflops, 0.0, stream);
+  cat::ProfScope prof(family, cat_s1::flops<NSLOT>(g), 0.0, stream);
 #define CAT_N7(A, B, C, D)                                                                             \
   if (nt[0] == A && nt[1] == B && nt[2] == C && nt[3] == D) {                                          \
-    if (stats) tstage1n7_kernel<A, B, C, D, true><<<(int)grid, 256, LDS_BYTES, s>>>(a);                \
-    else tstage1n7_kernel<A, B, C, D, false><<<(int)grid, 256, LDS_BYTES, s>>>(a);                     \
+    if (stats) tstage1n7_kernel<A, B, C, D, true><<<grid, 256, LDS_BYTES, s>>>(a);                     \
+    else tstage1n7_kernel<A, B, C, D, false><<<grid, 256, LDS_BYTES, s>>>(a);                          \
     return cat::check_launch(what);                                                                    \
   }
 #define CAT_N7_1(A, B, C) CAT_N7(A, B, C, 1) CAT_N7(A, B, C, 2) CAT_N7(A, B, C, 3) CAT_N7(A, B, C, 4)

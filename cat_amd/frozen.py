@@ -157,20 +157,9 @@ def _build_plan(block):
             for q in range(d['off'] // 4, (d['off'] + d['sz']) // 4):
                 ks[q] = k
         dwm = dict(frame=frame.contiguous(), bias=fbias.contiguous(), ks=ks, fs=fs)
-    # stage 1 in one launch (cat_tstage1w_fwd): one 5 x 5 and one 3 x 3 residual branch + the concatenated 1 x 1 convs, the teacher's widths
-    s1w = None
-    by_k = {wd['k']: wd for wd in wides}
-    if (_STAGE1W and len(wides) == 2 and set(by_k) == {3, 5} and all(wd['act'] == (act, slope) for wd in wides)
-            and L.query('cat_tstage1w_supported', by_k[5]['m'], by_k[3]['m'], hc)):
-        s1w = dict(packs=None, ws=[by_k[5]['wf'], by_k[3]['wf'], w_a],      # packed filter streams: built at the first launch
-                   biases=[by_k[5]['bf'], by_k[3]['bf'], b_a.contiguous()], m=[by_k[5]['m'], by_k[3]['m'], hc])
-    # ... and for the kernel sizes 3 5 7: the 7 x 7, 5 x 5 and 3 x 3 residual branches + the concatenated 1 x 1 convs (cat_tstage1w7_fwd)
-    s1w7 = None
-    if (len(wides) == 3 and set(by_k) == {3, 5, 7} and all(wd['act'] == (act, slope) for wd in wides)
-            and L.query('cat_tstage1w7_supported', by_k[7]['m'], by_k[5]['m'], by_k[3]['m'], hc)):
-        order = [by_k[7], by_k[5], by_k[3]]
-        s1w7 = dict(packs=None, ws=[wd['wf'] for wd in order] + [w_a], biases=[wd['bf'] for wd in order] + [b_a.contiguous()],
-                    m=[wd['m'] for wd in order] + [hc])
+    # stage 1 in one launch: exactly one residual branch per wide kernel size + the concatenated 1 x 1 convs, the teacher's widths
+    s1w = _stage1_plan('s1w', wides, (act, slope), w_a, b_a, hc) if _STAGE1W else None
+    s1w7 = _stage1_plan('s1w7', wides, (act, slope), w_a, b_a, hc)
     # the k = 1 res slots come first and are contiguous from lane 0: ONE copy of their whole range.  cat_slice_channels writes all ycs lanes
     # of every pixel, so a copy per slot into h2 + 4 * o zeroed o floats of the next pixel (the slots before it) and, behind the last pixel,
     # o floats past the buffer
@@ -178,6 +167,45 @@ def _build_plan(block):
     assert all(o < res_w for (kind, _), (o, m, sz) in zip(slots, offs) if kind == 'res')
     return dict(s1w=s1w, s1w7=s1w7, tail_pack=None, tail_offs=None, hc=hc, dwm=dwm, w_a=w_a, b_a=b_a.contiguous(), w_f=w_f, b_f=b_f.contiguous(), dws=dws, wides=wides, act=act, slope=slope,
                 pad_mode=pad_mode, copies=[(0, res_w)] if res_w else [])
+
+
+# The one-launch stage 1 of a frozen block, by plan key: (entry, width query, geometry struct, kernel sizes of the wide slots; the last
+# slot is the concatenated 1 x 1 convs).  docs/CONV_VARIANTS.md, "Stage 1 in one launch"
+_STAGE1 = {'s1w': ('cat_tstage1w_fwd', 'cat_tstage1w_supported', L.Stage1WGeom, (5, 3)),
+           's1w7': ('cat_tstage1w7_fwd', 'cat_tstage1w7_supported', L.Stage1W7Geom, (7, 5, 3))}
+
+
+def _stage1_plan(key, wides, act, w_a, b_a, hc):
+    """The plan entry of _STAGE1[key], or None: the wide branches in slot order + the concatenated 1 x 1 convs (folded filters, folded
+    biases, output channels; the packed filter streams are built at the first launch)."""
+    _, query, _, sizes = _STAGE1[key]
+    by_k = {wd['k']: wd for wd in wides}
+    if len(wides) != len(sizes) or set(by_k) != set(sizes) or any(wd['act'] != act for wd in wides) or \
+            not L.query(query, *[by_k[k]['m'] for k in sizes], hc):
+        return None
+    order = [by_k[k] for k in sizes]
+    return dict(packs=None, ws=[wd['wf'] for wd in order] + [w_a], biases=[wd['bf'] for wd in order] + [b_a.contiguous()],
+                m=[wd['m'] for wd in order] + [hc])
+
+
+def _stage1_launch(key, p, x, refl):
+    """Issues _STAGE1[key] on the plan entry p[key] -> (the concatenated 1 x 1 hidden buffer, {k: hidden buffer of the k x k branch})."""
+    entry, _, geom, sizes = _STAGE1[key]
+    s1 = p[key]
+    if s1['packs'] is None:
+        from . import tconv
+        s1['packs'] = [tconv.pack(wt, tconv.FWD) for wt in s1['ws']]
+    n, c, h, w = x.shape
+    g = geom()
+    g.N, g.H, g.W, g.xcs, g.cin = n, h, w, ops.act_cs(x), c
+    g.reflect, g.act, g.slope = int(refl), p['act'], p['slope']
+    bufs = [ops.empty_act(n, m, h, w, x.device) for m in s1['m']]
+    for k, buf in enumerate(bufs):
+        g.ycs[k], g.nvalid[k] = ops.act_cs(buf), s1['m'][k]
+    arr = C.c_void_p * len(bufs)
+    L.call(entry, C.byref(g), ops._p(x), arr(*[t.data_ptr() for t in s1['packs']]), arr(*[t.data_ptr() for t in s1['biases']]),
+           arr(*[t.data_ptr() for t in bufs]), ops._stream())
+    return bufs[-1], dict(zip(sizes, bufs))
 
 
 def block_forward(block, x):
@@ -240,40 +268,11 @@ def block_forward(block, x):
 
     fused_tail = ops.tconv_applicable(n, h, w, c, 3, 3, 1, 1) and 1 + len(p['wides']) <= L.TCONV_MAXSEG
     fns = [concat_chain] + [wide_chain(wd) for wd in p['wides']]
-    s1w = p['s1w'] if fused_tail and dwm is not None else None
-    s1w7 = p['s1w7'] if fused_tail and dwm is not None and k7_ok else None
-    if s1w7 is not None:
-        # the same for the kernel sizes 3 5 7: hid7, hid5, hid3 and the concatenated 1 x 1 hidden buffer in one launch
-        if s1w7['packs'] is None:
-            from . import tconv
-            s1w7['packs'] = [tconv.pack(wt, tconv.FWD) for wt in s1w7['ws']]
-        g = L.Stage1W7Geom()
-        g.N, g.H, g.W, g.xcs, g.cin = n, h, w, ops.act_cs(x), c
-        g.reflect, g.act, g.slope = int(refl), p['act'], p['slope']
-        bufs = [ops.empty_act(n, m, h, w, x.device) for m in s1w7['m']]
-        for k in range(4):
-            g.ycs[k], g.nvalid[k] = ops.act_cs(bufs[k]), s1w7['m'][k]
-        arr = C.c_void_p * 4
-        L.call('cat_tstage1w7_fwd', C.byref(g), ops._p(x), arr(*[t.data_ptr() for t in s1w7['packs']]), arr(*[t.data_ptr() for t in s1w7['biases']]),
-               arr(*[t.data_ptr() for t in bufs]), ops._stream())
-        hid = {7: bufs[0], 5: bufs[1], 3: bufs[2]}
-        outs = [dw_stage(bufs[3])] + [hid[wd['k']] for wd in p['wides']]
-    elif s1w is not None:
-        # every first conv of the block from one staging of x: hid5, hid3 and the concatenated 1 x 1 hidden buffer in one launch
-        if s1w['packs'] is None:
-            from . import tconv
-            s1w['packs'] = [tconv.pack(wt, tconv.FWD) for wt in s1w['ws']]
-        g = L.Stage1WGeom()
-        g.N, g.H, g.W, g.xcs, g.cin = n, h, w, ops.act_cs(x), c
-        g.reflect, g.act, g.slope = int(p['pad_mode'] == L.PAD_REFLECT), p['act'], p['slope']
-        bufs = [ops.empty_act(n, m, h, w, x.device) for m in s1w['m']]
-        for k in range(3):
-            g.ycs[k], g.nvalid[k] = ops.act_cs(bufs[k]), s1w['m'][k]
-        arr = C.c_void_p * 3
-        L.call('cat_tstage1w_fwd', C.byref(g), ops._p(x), arr(*[t.data_ptr() for t in s1w['packs']]), arr(*[t.data_ptr() for t in s1w['biases']]),
-               arr(*[t.data_ptr() for t in bufs]), ops._stream())
-        hid = {5: bufs[0], 3: bufs[1]}
-        outs = [dw_stage(bufs[2])] + [hid[wd['k']] for wd in p['wides']]
+    s1 = 's1w7' if p['s1w7'] is not None and k7_ok else 's1w'
+    if fused_tail and dwm is not None and p[s1] is not None:
+        # every first conv of the block from one staging of x: the wide hidden buffers and the concatenated 1 x 1 one in one launch
+        h1, hid = _stage1_launch(s1, p, x, refl)
+        outs = [dw_stage(h1)] + [hid[wd['k']] for wd in p['wides']]
     elif ops.branch_streams_enabled() and len(fns) > 1:
         outs = ops.run_on_side_streams(fns, [x] * len(fns))
     else:

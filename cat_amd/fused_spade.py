@@ -164,16 +164,13 @@ class _Plan(U.Plan):
     def _merges_dw_dgrad(self):
         """The second convs' input gradients as ONE launch (cat_tstage1_dgrad: dT is staged once for the 5 x 5 and the 3 x 3 residual branch
         and the N-concatenated 1 x 1 second convs of the depthwise branches; cat_tstage1n7_dgrad: the same with exactly one 7 x 7, one 5 x 5
-        and one 3 x 3 residual branch, `s1d7`) where a kernel exists for the widths."""
-        r5, r3 = [b for b in self.res if b['k'] == 5], [b for b in self.res if b['k'] == 3]
-        r7 = [b for b in self.res if b['k'] == 7]
-        if _S1_DGRAD and len(r7) == 1 and len(r5) == 1 and len(r3) == 1 and self.dws and \
-                L.query('cat_tstage1n7_supported', r7[0]['w1'], r5[0]['w1'], r3[0]['w1'], self.hcd):
-            self.s1d7 = (r7[0], r5[0], r3[0])      # ... with one more slot: cat_tstage1n7_dgrad (p.s1d stays None)
-            return True
-        if _S1_DGRAD and len(r5) == 1 and len(r3) == 1 and self.dws and L.query('cat_tstage1_dgrad_supported', r5[0]['w1'], r3[0]['w1'], self.hcd):
-            self.s1d = (r5[0], r3[0])
-        return self.s1d is not None
+        and one 3 x 3 residual branch, `s1d7`) where a kernel exists for the widths (fused_unit.STAGE1_DGRAD)."""
+        for _, query, sizes, _, attr in U.STAGE1_DGRAD if _S1_DGRAD else ():
+            rs = [[b for b in self.res if b['k'] == k] for k in sizes]
+            if all(len(r) == 1 for r in rs) and self.dws and L.query(query, *[r[0]['w1'] for r in rs], self.hcd):
+                setattr(self, attr, tuple(r[0] for r in rs))      # p.s1d7 / p.s1d: the residual branches of the launch, in slot order
+                return True
+        return False
 
     def prepare(self, backward=False):
         gref = getattr(self, 'group', None)      # weak reference to the generator that owns this unit (no cycle through the cached plans)

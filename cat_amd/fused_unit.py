@@ -1,6 +1,7 @@
 """The fused inception block (cat_amd/fused_block.py) and the fused six-branch SPADE unit (cat_amd/fused_spade.py) are ONE pipeline
 
-    stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (cat_tstage1_fwd / cat_tstage1ws_fwd / cat_tstage1ws7_fwd / cat_tstage1n7_fwd / cat_tconv_fwd)
+    stage 1   first convs of all branches -> one concatenated pre-norm buffer Z1 + per-tile statistics   (one launch: the first STAGE1_FWD row that applies -- cat_tstage1_fwd /
+              cat_tstage1ws_fwd / cat_tstage1ws7_fwd / cat_tstage1n7_fwd; else one cat_tconv_fwd per kernel size)
     finalize  scale / shift of all stage-1 norms + their running statistics                               (cat_tnorm_finalize)
     dw        all depthwise convs (one launch per <= 18 / 24 channel quads), norm + activation of stage 1 applied while staging   (cat_dwm_fwd;
               cat_dwm7_fwd for a plan with a 7 x 7 depthwise branch)
@@ -62,6 +63,24 @@ def set_stage1ws7(on):
     global _STAGE1WS7
     old, _STAGE1WS7 = _STAGE1WS7, bool(on)
     return old
+
+
+# The one-launch stage-1 kernels (docs/CONV_VARIANTS.md, "Stage 1 in one launch"), in priority order: (entry, width query, kernel size of
+# each slot, geometry struct, gate read at every call or None, smallest plane of a mirrored window tested here -- the 5 3 1 entries refuse
+# theirs themselves).  All share one argument list and one output contract: column slices of Z1 + per-tile statistics.
+STAGE1_FWD = (
+    ('cat_tstage1_fwd', 'cat_tstage1_supported', (5, 3, 1), L.Stage1Geom, None, 0),
+    ('cat_tstage1ws_fwd', 'cat_tstage1ws_supported', (5, 3, 1), L.Stage1Geom, lambda p: _STAGE1WS, 0),      # the wide block's widths
+    ('cat_tstage1ws7_fwd', 'cat_tstage1ws7_supported', (7, 5, 3, 1), L.Stage1S7Geom, lambda p: _STAGE1WS7, 7),      # ... with one more slot
+    ('cat_tstage1n7_fwd', 'cat_tstage1n7_supported', (7, 5, 3, 1), L.Stage1S7Geom, lambda p: getattr(p, 'stage1_n7', False), 7),      # narrow widths
+)
+# The second convs' input gradients in one launch, first match wins: (entry, width query, kernel sizes of the residual slots -- exactly
+# one branch each; the last slot is the depthwise branches' N-concatenated 1 x 1 convs --, geometry struct, the plan attribute that holds
+# the residual branches).  Read by the planner (fused_spade.py) and by backward_g.
+STAGE1_DGRAD = (
+    ('cat_tstage1n7_dgrad', 'cat_tstage1n7_supported', (7, 5, 3), L.Stage1S7Geom, 's1d7'),
+    ('cat_tstage1_dgrad', 'cat_tstage1_dgrad_supported', (5, 3), L.Stage1Geom, 's1d'),
+)
 
 
 def cs4(c):
@@ -388,26 +407,17 @@ def prepare_plans(plans, group, backward=False):
 # ---------------------------------------------------------------------------------------------------------------- forward stages
 def stage1(p, x, z1, part1, reflect=False):
     """First convs of all branches: x -> channel slices of Z1 (pre-norm) + tile statistics into part1.  part1 None: the eval form, no
-    statistics (always one launch per kernel size).  The one-launch kernels take exactly the kernel sizes 5, 3 and 1, or 7, 5, 3 and 1 -- at
+    statistics (always one launch per kernel size).  The one-launch kernels (STAGE1_FWD: the first row whose sizes, gate, plane and width
+    query all hold) take exactly the kernel sizes 5, 3 and 1, or 7, 5, 3 and 1 -- at
     the wide widths, or at narrow widths for a plan that carries `stage1_n7` (the GauGAN units under CAT_FUSED_SPADE_K7; the plans of
     fused_block.py and frozen_in.py do not carry it: their narrow 3 5 7 launch order, one launch per size, is pinned by their tests, and
     adopting the narrow kernel there is a later, measured decision).  A plan with another set of sizes runs one launch per size."""
     n, c, h, w = x.shape
     by_k = {g['k']: g for g in p.groups}
-    sizes = (5, 3, 1)
-    widths = [by_k[k]['width'] for k in sizes] if part1 is not None and set(by_k) == {1, 3, 5} else None
-    entry, geom = None, L.Stage1Geom
-    if widths is not None and L.query('cat_tstage1_supported', *widths):
-        entry = 'cat_tstage1_fwd'
-    elif widths is not None and _STAGE1WS and L.query('cat_tstage1ws_supported', *widths):
-        entry = 'cat_tstage1ws_fwd'      # the wide block's widths: the same arguments and output contract
-    elif part1 is not None and _STAGE1WS7 and set(by_k) == {1, 3, 5, 7} and (not reflect or (h >= 7 and w >= 7)) and \
-            L.query('cat_tstage1ws7_supported', *[by_k[k]['width'] for k in (7, 5, 3, 1)]):
-        entry, geom, sizes = 'cat_tstage1ws7_fwd', L.Stage1S7Geom, (7, 5, 3, 1)      # ... with one more slot
-    elif getattr(p, 'stage1_n7', False) and part1 is not None and set(by_k) == {1, 3, 5, 7} and (not reflect or (h >= 7 and w >= 7)) and \
-            L.query('cat_tstage1n7_supported', *[by_k[k]['width'] for k in (7, 5, 3, 1)]):
-        entry, geom, sizes = 'cat_tstage1n7_fwd', L.Stage1S7Geom, (7, 5, 3, 1)       # the narrow widths of a plan that asks for it
-    if entry is not None:
+    for entry, query, sizes, geom, gate, plane in STAGE1_FWD if part1 is not None else ():
+        if set(by_k) != set(sizes) or (gate is not None and not gate(p)) or (reflect and min(h, w) < plane) or \
+                not L.query(query, *[by_k[k]['width'] for k in sizes]):
+            continue
         # one launch: the kernel sizes share every staged input tile
         gs = geom()
         gs.N, gs.H, gs.W, gs.xcs, gs.cin, gs.reflect, gs.ycs, gs.scs = n, h, w, ops.act_cs(x), c, int(reflect), p.hc1, p.hc1
@@ -789,8 +799,9 @@ def backward_g(p, dt, x, z1, ss1, mr1, zd, ssd, mrd, *, need_dx, skip_grad=None,
     # ---- 4. merged second-conv input gradients: dT staged once for the 5 x 5 and the 3 x 3 residual branch and the N-concatenated 1 x 1
     # second convs of the depthwise branches (p.s1d; p.s1d7: and the 7 x 7 one), or those 1 x 1 convs alone as ONE launch over dT into dAd
     nvalid_dw = sum(b['m'] for b in p.dws)
-    if p.s1d is not None or p.s1d7 is not None:
-        rs, geom, entry = (p.s1d, L.Stage1Geom, 'cat_tstage1_dgrad') if p.s1d is not None else (p.s1d7, L.Stage1S7Geom, 'cat_tstage1n7_dgrad')
+    s1d = [(getattr(p, attr), geom, entry) for entry, _, _, geom, attr in STAGE1_DGRAD if getattr(p, attr) is not None]
+    if s1d:
+        rs, geom, entry = s1d[0]
         ns = len(rs) + 1
         gs = geom()
         gs.N, gs.H, gs.W, gs.xcs, gs.cin, gs.reflect, gs.ycs, gs.scs = n, h, w, p.cso, p.Cout, 0, 0, 0
